@@ -19,6 +19,11 @@ rows in once, the rows of changed nodes out once) / kernel time / 8 TB/s — alw
 Contract: `python bench.py --gpus N --steps K --warmup W`; for N>1 the driver launches it under torch.distributed.run
 (one rank per GPU, RCCL).  Rank 0 prints ONE JSON line.  `--mode search` runs BASELINE config 5 instead (the sharded
 open-node worklist over RCCL, nodes/s).
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the line.  `--full` adds everything else
+(the CPU baseline and its parity check, the side legs, the config-5 legs, per-launch probe times, the box ceilings of `roofline`).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_step_outputs); the inputs are the same in
+every run with the same arguments.
 """
 import argparse
 import json
@@ -198,6 +203,38 @@ def node_bytes(V, words, explicit):
     return 8 * V + (8 * words if explicit else 0)
 
 
+DUMP_ROWS = 4096       # --dump-outputs: nodes whose rows are written (a fixed sample of a larger batch)
+DUMP_BYTES = 60 << 20  # --dump-outputs: bytes of all files of all ranks together, at most
+
+
+def save_outputs(out_dir, arrays, rank=0):
+    """--dump-outputs: every array as out_dir/<name>.npy (rank r > 0: <name>_rank<r>.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
+
+
+def dump_step_outputs(out_dir, rows, t_status, rank, world):
+    """--dump-outputs of the propagate mode: what the last timed step handed back to its caller, i.e. the status of every node and its
+    rows, written in place.  status.npy [nodes] float32 (0 false, 1 true, 2 unknown); the rows of a fixed sample of the nodes (seed 0: the
+    same nodes in every run with the same --nodes and --n), rows.npy [k] float64 = which nodes, lb.npy / ub.npy [k, n] float32 (exact below
+    2**24), and for explicit nodes active.npy [k, words, 2] float64 = the low and high 32 bits of every word of the `active` rows."""
+    import torch
+    lb, ub, act = rows
+    nodes, V = lb.shape
+    row_bytes = 8 * V + (0 if act is None else 16 * (act.numel() // nodes))
+    k = int(max(1, min(nodes, DUMP_ROWS, (DUMP_BYTES // world - 4 * nodes) // row_bytes)))
+    pick = np.sort(np.random.default_rng(0).choice(nodes, size=k, replace=False))
+    idx = torch.from_numpy(pick).to(lb.device)
+    out = {"status": t_status.cpu().numpy().astype(np.float32), "rows": pick.astype(np.float64),
+           "lb": lb.index_select(0, idx).cpu().numpy().astype(np.float32), "ub": ub.index_select(0, idx).cpu().numpy().astype(np.float32)}
+    if act is not None:
+        a = act.reshape(nodes, -1).index_select(0, idx).cpu().numpy().view(np.uint64)
+        out["active"] = np.stack([(a & np.uint64(0xFFFFFFFF)).astype(np.float64), (a >> np.uint64(32)).astype(np.float64)], axis=-1)
+    save_outputs(out_dir, out, rank)
+
+
 def run_search_mode(args, torch, dist, world, rank, dev):
     """BASELINE config 5: N-queens-n parallel subtree search, the open-node worklist sharded over the ranks and balanced
     GPU-to-GPU over RCCL (pcp_amd.distributed.parallel_search_device), on a fixed node budget."""
@@ -240,6 +277,8 @@ def run_search_mode(args, torch, dist, world, rank, dev):
     if world > 1:
         dist.all_reduce(t_dt, op=dist.ReduceOp.MAX)
     dt = float(t_dt.item())
+    if rank == 0 and args.dump_outputs:  # the search's totals: nodes, solutions, failed nodes, filter steps executed, reference-equivalent steps
+        save_outputs(args.dump_outputs, {"totals": np.array([nodes, sols, fails, info.get("evaluated", 0), steps], np.float64)})
     if rank == 0:
         _flush_c_stdio()
         emit_json({
@@ -382,6 +421,8 @@ def run_forest_mode(args, torch, dist, world, rank, dev, ctx, lb0, ub0, set_mode
         dist.all_reduce(t_dt, op=dist.ReduceOp.MAX)
     dt = float(t_dt.item())
     nodes, sols, fails, evaluated, steps, ntrees, err = (int(x) for x in tot.tolist())
+    if rank == 0 and args.dump_outputs:  # the search's totals, all ranks: nodes, solutions, failed nodes, filter steps executed, reference-equivalent steps
+        save_outputs(args.dump_outputs, {"totals": np.array([nodes, sols, fails, evaluated, steps], np.float64)})
     if rank == 0:
         _flush_c_stdio()
         emit_json({
@@ -500,10 +541,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--n", type=int, default=1000, help="N-queens size (BASELINE config: 1000)")
     ap.add_argument("--nodes", type=int, default=16384, help="open nodes per GPU per step")
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU baseline work (rank 0, N=1 only; 0 = skip)")
+    ap.add_argument("--cpu-budget", type=float, default=None, help="seconds of CPU baseline work (rank 0, N=1 only; 0 = skip; default 20 with --full, else 0)")
     ap.add_argument("--active", choices=["implicit", "explicit"], default="implicit",
                     help="node format of the headline leg: domains only (liveness derived) or domains + `active` rows")
-    ap.add_argument("--legs", default="auto", help="'auto' = all side legs at N=1, 'none', or a comma list of: cells,wide,mix,explicit,c2,forest,deep500,deep3000,set,setsearch,c3,c4,f4")
+    ap.add_argument("--legs", default="auto", help="'auto' = all side legs at N=1 with --full and none without, 'none', or a comma list of: cells,wide,mix,explicit,c2,forest,deep500,deep3000,set,setsearch,c3,c4,f4")
     ap.add_argument("--share", type=int, default=-1, help="which share of the frontier this process runs (default: its rank)")
     ap.add_argument("--nodes-per-block", type=int, default=0)
     ap.add_argument("--block-threads", type=int, default=1024)
@@ -512,8 +553,8 @@ def main():
     ap.add_argument("--search-batch", type=int, default=16384, help="worklist engine: open nodes per round and GPU (4096: 2.0e7 nodes/s on one MI355X, 16384: 3.4e7, 65536: 5.1e7 — a round is two launches and one 20-byte read-back)")
     ap.add_argument("--rounds-per-exchange", type=int, default=4)
     ap.add_argument("--c5-timeout", type=float, default=240.0, help="seconds after which the config-5 legs are given up and the headline line is printed without them")
-    ap.add_argument("--c5-single", action="store_true", help="(default since round 6; kept so that old command lines still parse) run the config-5 legs on one GPU too")
-    ap.add_argument("--no-c5", action="store_true", help="skip the config-5 legs (worklist engine through RCCL, interval forest with cross-rank refill); by default they run "
+    ap.add_argument("--c5-single", action="store_true", help="run the config-5 legs behind the headline, also without --full and on one GPU (through a one-rank RCCL group)")
+    ap.add_argument("--no-c5", action="store_true", help="skip the config-5 legs (worklist engine through RCCL, interval forest with cross-rank refill); with --full they run "
                                                          "behind the headline at every --gpus N, on one GPU through a one-rank RCCL group")
     ap.add_argument("--c5-budget", type=int, default=2097152,
                     help="--gpus N > 1: nodes of the short config-5 leg appended to the headline run (worklist engine; the forest leg runs 8x as many); 0 = skip")
@@ -527,9 +568,18 @@ def main():
     ap.add_argument("--domains", choices=["interval", "set"], default="interval",
                     help="--mode search: Interval<i32> domains, or IntervalSet<i32> (the reference's FDSpace: what example/src/nqueens.rs runs)")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE", help="(experiments) pcp_set_option on the context after the model is set, e.g. --opt neq_persist=0; repeatable")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the CPU baseline and its parity check, the side legs (--legs auto), the config-5 legs, the untimed "
+                         "per-launch probe steps (config.kernel_ms_per_launch) and the box ceilings of `roofline`.  A plain run sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64): the status of every node "
+                         "and the lb / ub rows of a fixed, seeded sample of the nodes (see dump_step_outputs)")
     ap.add_argument("--spawn-dry-run", action="store_true",
                     help="(tests) the self-spawned ranks only bring up a gloo group on CPU, all_reduce their ranks and rank 0 prints a small JSON line: checks the launcher without a GPU")
     args = ap.parse_args()
+    if args.cpu_budget is None:
+        args.cpu_budget = 20.0 if args.full else 0.0
 
     # `python bench.py --gpus N` by itself (no torchrun: WORLD_SIZE unset) starts its own N ranks, one process per device; under
     # torch.distributed.run the environment is already there and this process IS a rank.
@@ -593,7 +643,7 @@ def main():
     t_act_in = None if A is None else torch.from_numpy(A.view(np.int64)).to(dev)
     t_status = torch.zeros(args.nodes, dtype=torch.uint8, device=dev)
     stream = torch.cuda.current_stream().cuda_stream
-    n_probe = min(args.steps, 10)  # untimed steps after the timed ones, for the per-launch HIP-event times
+    n_probe = min(args.steps, 10) if args.full else 0  # untimed steps after the timed ones, for the per-launch HIP-event times (--full)
     total_steps = args.warmup + args.steps + n_probe
     # In place, as the reference's Store::consistency(&mut vstore) works and as the search loop calls the engine: every
     # step gets its OWN copy of the frontier, staged in HBM before the timed region.  If K exceeds what fits, the pool is
@@ -633,9 +683,11 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     region_ms = ev0.elapsed_time(ev1) / args.steps  # HIP events over the timed region: the kernel's average launch duration, back to back
-    ctx.set_option("time_kernels", 1)
+    if args.dump_outputs:  # before the probe steps below, which reuse the pool and the status buffer
+        dump_step_outputs(args.dump_outputs, pool[(step_no[0] - 1) % len(pool)], t_status, rank, world)
     # HIP-event time of the fixpoint kernel of each step would need a sync per step; take it from a second, untimed pass
-    # over the same steps so that the timed region stays free of host syncs.
+    # over the same steps so that the timed region stays free of host syncs (--full only).
+    ctx.set_option("time_kernels", 1)
     kernel_ms = []
     for _ in range(n_probe):
         step()
@@ -658,12 +710,12 @@ def main():
     status = t_status.cpu().numpy()
     out, flat, legs = None, {}, []
     if rank == 0:
-        k_med = float(np.median(kernel_ms))  # one event pair around each of the probe launches (a pair costs the queue a few microseconds)
+        k_med = float(np.median(kernel_ms)) if kernel_ms else None  # one event pair around each of the probe launches (a pair costs the queue a few microseconds)
         k_ms = region_ms                     # the roofline's duration: HIP events over the timed region / launches
         compulsory = args.nodes * node_bytes(V, words, not implicit) + 8 * V * min(args.nodes, per_step["narrowings"])
         tr = profiled_traffic({"n": n, "nodes_per_launch": args.nodes, "active": args.active})
         achieved = compulsory / (k_ms * 1e-3) / 1e9
-        box = box_ceilings(torch, pool[0][0], pool[0][1], stream) if world == 1 else {}
+        box = box_ceilings(torch, pool[0][0], pool[0][1], stream) if world == 1 and args.full else {}
         out = {
             "metric": "propagator filter-steps/sec to fixpoint, N-queens-1000",
             "value": eval_all / dt_max,
@@ -699,7 +751,7 @@ def main():
                 "fixpoint_waves_per_node": per_step["waves"] / args.nodes,
                 "status_counts_false_true_unknown": np.bincount(status, minlength=3)[:3].tolist(),
                 "kernel_ms_per_launch": {"min": float(min(kernel_ms)), "median": k_med, "max": float(max(kernel_ms)), "launches": len(kernel_ms),
-                                         "note": "untimed probe launches, each bracketed by its own pair of HIP events"},
+                                         "note": "untimed probe launches, each bracketed by its own pair of HIP events"} if kernel_ms else None,
                 "kernel_ms_timed_region": region_ms,
                 "parallelism": f"nodes sharded over {world} GPU(s), no data-path collective",
             },
@@ -721,7 +773,7 @@ def main():
         }
         legs_req = args.legs
         if legs_req == "auto":
-            legs_req = "cells,wide,mix,explicit,c2,forest,deep500,deep3000,set,setsearch,c3,c4,f4" if world == 1 else "none"
+            legs_req = "cells,wide,mix,explicit,c2,forest,deep500,deep3000,set,setsearch,c3,c4,f4" if world == 1 and args.full else "none"
         legs = []
         if world == 1 and args.cpu_budget > 0:
             out["cpu_baseline"], ref = cpu_baseline(n, props, L, U, A, args.cpu_budget)
@@ -794,7 +846,7 @@ def main():
     # collective hangs (this path cannot be run on more than one GPU where it was written), rank 0 still prints the headline line, with
     # `c5_error` in place of the c5 keys, and every rank leaves.
     c5 = {}
-    if args.c5_budget > 0 and not args.no_c5 and (world > 1 or args.c5_single or args.legs == "auto"):
+    if args.c5_budget > 0 and not args.no_c5 and (args.c5_single or (args.full and (world > 1 or args.legs == "auto"))):
         import threading
 
         def finish(extra):

@@ -1,14 +1,14 @@
 #!/bin/bash
 # A/B of two builds of the library on the headline launch, alternating on ONE box (run through gpurun):
 #   bash tools/ab_headline.sh <tag> <variant.so> [rounds]
-# prints the median HIP-event kernel time of `bench.py --legs none --cpu-budget 0` per run; PCP_HIP_LIB selects the build.
+# prints the median HIP-event kernel time of `bench.py --full --legs none --cpu-budget 0` per run; PCP_HIP_LIB selects the build.
 set -u
 TAG=$1; VAR=$2; R=${3:-3}
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 for i in $(seq 1 $R); do
   for which in default variant; do
     if [ $which = variant ]; then export PCP_HIP_LIB=$PWD/$VAR; else unset PCP_HIP_LIB; fi
-    timeout 200 python bench.py --legs none --cpu-budget 0 --steps 20 > $OUT/ab_${which}_$i.json 2> $OUT/ab_${which}_$i.err
+    timeout 200 python bench.py --full --legs none --cpu-budget 0 --steps 20 > $OUT/ab_${which}_$i.json 2> $OUT/ab_${which}_$i.err
     python - "$OUT/ab_${which}_$i.json" "$which" "$i" <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

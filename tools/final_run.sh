@@ -4,10 +4,11 @@
 set -u
 T=$1
 mkdir -p gpurun_out/$T
+OUT=$_  # the folder just made
 if [ "${2:-}" != "notests" ]; then
   timeout 1500 python -m pytest tests -m gpu -q > gpurun_out/$T/gputests.log 2>&1; echo "pytest exit $?" >> gpurun_out/$T/gputests.log
 fi
-timeout 600 python bench.py > gpurun_out/$T/bench.json 2> gpurun_out/$T/bench.err
+timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cp gpurun_out/bench_legs.json gpurun_out/$T/bench_legs.json 2>/dev/null
 timeout 200 python bench.py --mode search > gpurun_out/$T/search_interval.json 2> gpurun_out/$T/search_interval.err
 timeout 200 python bench.py --mode search --engine worklist > gpurun_out/$T/search_worklist.json 2> gpurun_out/$T/search_worklist.err

@@ -7,7 +7,7 @@ OUT=gpurun_out/$TAG; mkdir -p $OUT; : > $OUT/summary.txt
 i=0
 for CTRS in "$@"; do
   i=$((i+1))
-  timeout 150 rocprofv3 --pmc $CTRS -d $OUT/pmc$i -o p -- python bench.py --steps 5 --warmup 1 --cpu-budget 0 ${BENCH_ARGS:-} > $OUT/pmc$i.log 2>&1
+  timeout 150 rocprofv3 --pmc $CTRS -d $OUT/pmc$i -o p -- python bench.py --full --steps 5 --warmup 1 --cpu-budget 0 ${BENCH_ARGS:-} > $OUT/pmc$i.log 2>&1
   echo "# --pmc $CTRS" >> $OUT/summary.txt
   python tools/rocpd_summary.py $OUT/pmc$i/p_results.db fixpoint_kernelILi16ELb0ELb1ELb1 >> $OUT/summary.txt 2>&1
 done

@@ -6,7 +6,7 @@
 set -u
 TAG=${1:-prof}
 shift || true
-BENCH="python bench.py --steps 5 --warmup 1 --cpu-budget 0 $*"
+BENCH="python bench.py --full --steps 5 --warmup 1 --cpu-budget 0 $*"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG
 mkdir -p $OUT

@@ -6,7 +6,7 @@
 # The text summary goes to gpurun_out/<tag>/<name>_summary.txt; copy what is to be kept into profiles/.
 set -u
 TAG=$1; NAME=$2; FILT=$3; shift 3
-BENCH="python bench.py --cpu-budget 0 $*"
+BENCH="python bench.py --full --cpu-budget 0 $*"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
