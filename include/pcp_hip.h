@@ -264,6 +264,40 @@ int32_t pcp_propagate_device(pcp_ctx* ctx, uint32_t n_nodes, const pcp_device_ba
  * operation on `bits`.) */
 int32_t pcp_propagate_device_units(pcp_ctx* ctx, uint32_t n_nodes, const pcp_device_batch* batch, const uint32_t* node_unit_off,
                                    const pcp_prop* node_units, void* hip_stream);
+/* Branch and bound — the reference's minimize / maximize (search/branch_and_bound.rs:64-84).  Once a solution is known, every node entered
+ * gets one extra unary propagator before its propagation: Minimize  XLessY(var, Constant(best))  (var < best), Maximize  x_greater_y(var,
+ * Constant(best))  (var > best).  It narrows its variable once and is then entailed, so it is folded into the node's domain, like
+ * BinarySplit's branch constraints.  On a Satisfiable node the incumbent becomes  var.lower()  in BOTH modes.
+ *   var       : the objective variable (an Identity view, < n_vars)
+ *   mode      : PCP_MINIMIZE / PCP_MAXIMIZE
+ *   best      : device int32[1], in/out: the incumbent.  "No solution yet" is PCP_BOUND_MAX + 1 (minimize) or -(PCP_BOUND_MAX + 1)
+ *               (maximize): the fold is then a no-op.
+ *   best_lb / best_ub : device [n_vars] or NULL: receive the lb_out / ub_out row of the node that set the incumbent
+ *   best_bits : set mode, device [n_vars][set_words] or NULL: that node's sets
+ *   improved  : device uint32[1] or NULL: +1 per call that improved the incumbent (accumulated, the caller zeroes it)
+ * pcp_propagate_device_bnb has the contract of pcp_propagate_device, plus, enqueued on hip_stream with no host synchronisation:
+ *   FOLD   before the fixpoint, the incumbent read on the device tightens each node's objective domain (interval mode: one bound; set mode:
+ *          the objective's values >= best resp. <= best are cleared).  Rows in place (*_in == *_out) cost one column per node; otherwise the
+ *          rows are copied to *_out first and propagated there.
+ *   EMPTY  a node whose objective domain the fold empties is left as it was (a valid row: no hull check, no sticky flag) and comes out
+ *          PCP_FALSE on every path.  pcp_stats counts the fixpoint launch as it ran.
+ *   REDUCE after the fixpoint, the PCP_TRUE node with the best lb_out[var] (minimize: smallest, maximize: largest; a tie goes to the lowest
+ *          node index) replaces the incumbent if it beats it: *best, the rows above and *improved are updated.
+ * dirty_var is IGNORED: every node is propagated from scratch — the fold may narrow another variable than the hinted one, which breaks the
+ * hint's promise.  cell_format PCP_CELLS_PACKED16: PCP_ERR_UNSUPPORTED.  var >= n_vars or an unknown mode: PCP_ERR_ARG. */
+#define PCP_MINIMIZE 0u
+#define PCP_MAXIMIZE 1u
+typedef struct {
+  uint32_t var;
+  uint32_t mode;
+  int32_t* best;
+  int32_t* best_lb;
+  int32_t* best_ub;
+  uint64_t* best_bits;
+  uint32_t* improved;
+  uint32_t reserved;
+} pcp_objective;
+int32_t pcp_propagate_device_bnb(pcp_ctx* ctx, uint32_t n_nodes, const pcp_device_batch* batch, const pcp_objective* obj, void* hip_stream);
 /* One context = one queue of launches: the device-side scratch behind a launch (counters, team words, `active` scratch, the tile tickets of the
  * persistent kernels) belongs to the context, so the launches of one context must not overlap on the device — enqueue them on one stream, or order
  * the streams; concurrent launches take one context each (the model is uploaded per context).  The tile tickets are guarded at run time as well:

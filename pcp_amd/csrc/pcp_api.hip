@@ -85,6 +85,7 @@ struct pcp_ctx {
   uint64_t* d_live = nullptr; size_t cap_live = 0;       // working live mask when the caller passes none
   uint32_t* d_child_base = nullptr; size_t cap_child_base = 0;  // branching scratch
   uint32_t* d_team = nullptr; size_t cap_team = 0;       // team-mode scratch (u32 words)
+  uint8_t* d_bnb_empty = nullptr; size_t cap_bnb_empty = 0;  // pcp_propagate_device_bnb: per node, 1 = the incumbent's fold emptied it
   // host-buffer path staging
   void* d_stage = nullptr; size_t cap_stage = 0;
 
@@ -731,7 +732,7 @@ void pcp_ctx_destroy(pcp_ctx* c) {
   if (!c) return;
   hipError_t e = hipSetDevice(c->device);
   (void)e;
-  void* ptrs[] = {c->d_fnodes, c->d_unit_root, c->d_ad_tab, c->d_ad_vars, c->d_ad_mask, c->d_brec, c->d_badj, c->d_adjp4, c->d_seed_always, c->d_mul_off, c->d_gdesc, c->d_sum_off, c->d_sum_mem, c->d_recs, c->d_adj_off, c->d_adj, c->d_const, c->d_stats, c->d_live, c->d_team, c->d_stage, c->d_rec_unit, c->d_unit_first, c->d_recs8, c->d_child_base, c->d_retry, c->d_tile_ctr, c->d_dbg, c->d_wdesc, c->d_adjp};
+  void* ptrs[] = {c->d_fnodes, c->d_unit_root, c->d_ad_tab, c->d_ad_vars, c->d_ad_mask, c->d_brec, c->d_badj, c->d_adjp4, c->d_seed_always, c->d_mul_off, c->d_gdesc, c->d_sum_off, c->d_sum_mem, c->d_recs, c->d_adj_off, c->d_adj, c->d_const, c->d_stats, c->d_live, c->d_team, c->d_stage, c->d_rec_unit, c->d_unit_first, c->d_recs8, c->d_child_base, c->d_bnb_empty, c->d_retry, c->d_tile_ctr, c->d_dbg, c->d_wdesc, c->d_adjp};
   for (void* p : ptrs)
     if (p) { e = hipFree(p); (void)e; }
   if (c->ev_start) { e = hipEventDestroy(c->ev_start); (void)e; }
@@ -1579,6 +1580,45 @@ int32_t pcp_propagate_device_units(pcp_ctx* c, uint32_t n_nodes, const pcp_devic
   const int32_t rc = pcp_propagate_device(c, n_nodes, bt, hip_stream);
   c->cur_nu_off = nullptr; c->cur_nu = nullptr;
   return rc;
+}
+
+// Branch and bound (pcp_bnb.hip): fold the incumbent into the objective's domain, the fixpoint of pcp_propagate_device on the folded rows,
+// then force the emptied nodes to PCP_FALSE and reduce the batch's PCP_TRUE nodes into the incumbent.  Rows not in place are copied to
+// *_out first: the fold narrows the rows the fixpoint then runs on in place.
+int32_t pcp_propagate_device_bnb(pcp_ctx* c, uint32_t n_nodes, const pcp_device_batch* bt, const pcp_objective* obj, void* hip_stream) {
+  if (!c || !bt || !obj) return PCP_ERR_ARG;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  HIP_TRY(c, hipSetDevice(c->device));
+  int32_t rc = finalize_model(c);
+  if (rc) return rc;
+  if (bt->cell_format == PCP_CELLS_PACKED16) return fail(c, PCP_ERR_UNSUPPORTED, "branch and bound: int32 rows only (cell_format PCP_CELLS_PACKED16 is refused)");
+  if (obj->mode > PCP_MAXIMIZE || obj->reserved) return fail(c, PCP_ERR_ARG, "branch and bound: unknown mode (or reserved != 0)");
+  if (obj->var >= c->n_vars) return fail(c, PCP_ERR_ARG, "branch and bound: the objective variable is not a variable of the model");
+  if (!obj->best) return fail(c, PCP_ERR_ARG, "branch and bound: best must not be null");
+  if (n_nodes == 0) return pcp_propagate_device(c, 0, bt, hip_stream);
+  if (!bt->status) return fail(c, PCP_ERR_ARG, "status must not be null");
+  const uint32_t V = c->n_vars, sw = c->set_words;
+  pcp_device_batch b = *bt;
+  b.dirty_var = nullptr;  // the fold may narrow another variable than the hinted one: every node is propagated from scratch
+  if (sw) {
+    if (!c->hull_set) return fail(c, PCP_ERR_CONTRACT, "set mode needs the hull of the initial domains (pcp_model_set_hull): value v is bit v - lo");
+    if (!bt->bits_in || !bt->bits_out || !bt->lb_out || !bt->ub_out) return fail(c, PCP_ERR_ARG, "set mode: bits_in, bits_out, lb_out and ub_out must not be null");
+    if (bt->bits_in != bt->bits_out)
+      HIP_TRY(c, hipMemcpyAsync(bt->bits_out, bt->bits_in, (size_t)n_nodes * V * sw * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+    b.bits_in = bt->bits_out;
+  } else {
+    if (!bt->lb_in || !bt->ub_in || !bt->lb_out || !bt->ub_out) return fail(c, PCP_ERR_ARG, "domain pointers must not be null");
+    if (bt->lb_in != bt->lb_out) HIP_TRY(c, hipMemcpyAsync(bt->lb_out, bt->lb_in, (size_t)n_nodes * V * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
+    if (bt->ub_in != bt->ub_out) HIP_TRY(c, hipMemcpyAsync(bt->ub_out, bt->ub_in, (size_t)n_nodes * V * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
+    b.lb_in = bt->lb_out; b.ub_in = bt->ub_out;
+  }
+  if ((rc = ensure(c, c->d_bnb_empty, c->cap_bnb_empty, n_nodes))) return rc;
+  HIP_TRY(c, launch_bnb_fold(n_nodes, V, obj->var, obj->mode, obj->best, sw ? nullptr : b.lb_out, sw ? nullptr : b.ub_out, sw ? b.bits_out : nullptr, sw,
+                             c->hull_lo, c->d_bnb_empty, stream));
+  if ((rc = pcp_propagate_device(c, n_nodes, &b, hip_stream))) return rc;
+  HIP_TRY(c, launch_bnb_reduce(n_nodes, V, obj->var, obj->mode, c->d_bnb_empty, b.status, b.lb_out, b.ub_out, sw ? b.bits_out : nullptr, sw, obj->best,
+                               obj->best_lb, obj->best_ub, sw ? obj->best_bits : nullptr, obj->improved, stream));
+  return PCP_OK;
 }
 
 int32_t pcp_branch_device(pcp_ctx* c, uint32_t n_nodes, const int32_t* lb, const int32_t* ub, const uint64_t* active,

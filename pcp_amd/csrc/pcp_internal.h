@@ -213,4 +213,13 @@ hipError_t launch_branch(uint32_t n_nodes, uint32_t n_vars, uint32_t words, cons
                          const uint8_t* status, int32_t* child_lb, int32_t* child_ub, uint64_t* child_active, uint32_t* child_dirty, uint32_t* child_base,
                          uint32_t* counts, uint32_t reverse, hipStream_t stream);
 
+// Branch and bound (pcp_bnb.hip, pcp_propagate_device_bnb): the incumbent folded into each node's objective domain before the fixpoint
+// (empty[i] = 1: the fold would empty node i, its row is left as it was), then the empty nodes forced to PCP_FALSE and the best PCP_TRUE node
+// of the batch taken as the new incumbent if it beats it.  Interval mode: lb / ub rows; set mode: bits rows (lb / ub ignored by the fold).
+hipError_t launch_bnb_fold(uint32_t n_nodes, uint32_t n_vars, uint32_t var, uint32_t mode, const int32_t* best, int32_t* lb, int32_t* ub, uint64_t* bits,
+                           uint32_t set_words, int32_t base, uint8_t* empty, hipStream_t stream);
+hipError_t launch_bnb_reduce(uint32_t n_nodes, uint32_t n_vars, uint32_t var, uint32_t mode, const uint8_t* empty, uint8_t* status, const int32_t* lb_out,
+                             const int32_t* ub_out, const uint64_t* bits_out, uint32_t set_words, int32_t* best, int32_t* best_lb, int32_t* best_ub,
+                             uint64_t* best_bits, uint32_t* improved, hipStream_t stream);
+
 }  // namespace pcp

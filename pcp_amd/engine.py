@@ -25,7 +25,7 @@ ERRORS = {-1: "PCP_ERR_ARG", -2: "PCP_ERR_CONTRACT", -3: "PCP_ERR_HIP", -4: "PCP
 ABI_SYMBOLS = [
     "pcp_ctx_create", "pcp_ctx_destroy", "pcp_last_error", "pcp_strerror", "pcp_abi_version",
     "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull",
-    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
+    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
 ]
 
 
@@ -48,6 +48,24 @@ class DeviceBatch(C.Structure):
     _fields_ = [("lb_in", C.c_void_p), ("ub_in", C.c_void_p), ("lb_out", C.c_void_p), ("ub_out", C.c_void_p),
                 ("active_in", C.c_void_p), ("active_out", C.c_void_p), ("status", C.c_void_p), ("bits_in", C.c_void_p), ("bits_out", C.c_void_p),
                 ("dirty_var", C.c_void_p), ("cell_format", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Objective(C.Structure):
+    """pcp_objective: the objective of pcp_propagate_device_bnb (branch and bound)."""
+    _fields_ = [("var", C.c_uint32), ("mode", C.c_uint32), ("best", C.c_void_p), ("best_lb", C.c_void_p), ("best_ub", C.c_void_p),
+                ("best_bits", C.c_void_p), ("improved", C.c_void_p), ("reserved", C.c_uint32)]
+
+
+pcp_objective = Objective
+MINIMIZE, MAXIMIZE = 0, 1
+BOUND_MAX = 0x1FFFFFFF  # PCP_BOUND_MAX
+OBJ_MODES = {"min": MINIMIZE, "max": MAXIMIZE}
+
+
+def no_incumbent(mode) -> int:
+    """The `best` of pcp_objective before any solution: PCP_BOUND_MAX + 1 (minimize) or -(PCP_BOUND_MAX + 1) (maximize)."""
+    m = OBJ_MODES.get(mode, mode)
+    return BOUND_MAX + 1 if m == MINIMIZE else -(BOUND_MAX + 1)
 
 
 class DfsState(C.Structure):
@@ -114,6 +132,7 @@ def load_library():
     L.pcp_model_set_hull.argtypes = [vp, i32, i32]
     L.pcp_propagate.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
     L.pcp_propagate_device.argtypes = [vp, u32, C.POINTER(DeviceBatch), vp]
+    L.pcp_propagate_device_bnb.argtypes = [vp, u32, C.POINTER(DeviceBatch), C.POINTER(Objective), vp]
     L.pcp_branch_device.argtypes = [vp, u32] + [vp] * 9
     L.pcp_branch_device_hint.argtypes = [vp, u32] + [vp] * 10
     L.pcp_pack_rows.argtypes = [vp, u32, vp, vp, vp, vp]
@@ -131,7 +150,7 @@ def load_library():
     L.pcp_last_plan.argtypes = [vp, C.POINTER(PcpPlan)]
     L.pcp_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
     for f in ("pcp_ctx_create", "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull", "pcp_model_set_hull",
-              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
+              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
         getattr(L, f).restype = i32
     _lib = L
     return L
@@ -307,6 +326,24 @@ class Context:
             return None if t is None else C.c_void_p(t.data_ptr())
         bt = DeviceBatch(p(lb_in), p(ub_in), p(lb_out), p(ub_out), p(active_in), p(active_out), p(status), None, None, None, 0, 0)
         self._check(self._L.pcp_propagate_device_units(self._h, n_nodes, C.byref(bt), p(unit_off), p(units), C.c_void_p(stream_ptr)))
+
+    def propagate_device_bnb(self, n_nodes: int, lb_in, ub_in, lb_out, ub_out, active_in, active_out, status, objective, stream_ptr: int = 0,
+                             bits_in=None, bits_out=None):
+        """pcp_propagate_device_bnb: `propagate_device` with the incumbent of a branch and bound folded into every node's objective domain
+        first and the batch's best PCP_TRUE node reduced into it afterwards, all on the device.  objective: a dict with `var`, `mode`
+        ("min" / "max" or MINIMIZE / MAXIMIZE), `best` (int32 [1] tensor) and optionally `best_lb`, `best_ub`, `best_bits`, `improved`
+        (int32 tensors [n_vars], int64 [n_vars, set_words], int32 [1]); or an Objective.  No hint (dirty) is taken: nodes are propagated
+        from scratch."""
+        def p(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+        if isinstance(objective, Objective):
+            ob = objective
+        else:
+            g = objective.get
+            ob = Objective(int(g("var")), int(OBJ_MODES.get(g("mode"), g("mode"))), p(g("best")), p(g("best_lb")), p(g("best_ub")), p(g("best_bits")),
+                           p(g("improved")), 0)
+        bt = DeviceBatch(p(lb_in), p(ub_in), p(lb_out), p(ub_out), p(active_in), p(active_out), p(status), p(bits_in), p(bits_out), None, 0, 0)
+        self._check(self._L.pcp_propagate_device_bnb(self._h, n_nodes, C.byref(bt), C.byref(ob), C.c_void_p(stream_ptr)))
 
     def pack_rows(self, lb, ub, cells=None, stream_ptr: int = 0):
         """pcp_pack_rows: int32 bounds rows [n,V] -> rows of packed cells (an int32 [n,V] tensor whose bits are the cells)."""

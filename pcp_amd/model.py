@@ -598,3 +598,10 @@ def golomb(m: int = 10, length: int = 80):
     cs.alloc(Distinct(list(diffs.values())))
     cs.alloc(XLessY(diffs[(0, 1)], diffs[(m - 2, m - 1)]))
     return vs, cs
+
+
+def golomb_ruler(m: int = 10, length: int = 80):
+    """The optimisation problem config 4 comes from: the shortest Golomb ruler with m marks.  Returns the golomb(m, length) model and its
+    objective variable, the last mark (index m - 1), to be minimised (search.dfs / DeviceSearch with objective=(var, "min"))."""
+    vs, cs = golomb(m, length)
+    return vs, cs, m - 1

@@ -13,6 +13,13 @@ A branch constraint is a var-vs-constant ``XLessY`` that narrows its one variabl
 entailed and unlinked (x_less_y.rs:87-93, propagation/store.rs:171), so it is folded into the child's bounds
 (SURVEY.md §8b "per-node propagators"); children inherit the parent's ``active`` row, exactly the cstore label
 ``(len, active.clone())`` of propagation/store.rs:315-317.
+
+Branch and bound (``objective=(var, "min" | "max")``, search/branch_and_bound.rs:64-84): once a solution is known every node
+entered gets one more unary propagator, ``var < best`` (Minimize) or ``var > best`` (Maximize); it narrows ``var`` once and
+is then entailed, so it is folded into the node's domain before propagation like a branch constraint.  A Satisfiable node
+makes ``var.lower()`` the incumbent (both modes).  With a batch, every node of the batch is folded against the incumbent as
+it stands, and the best Satisfiable node of the batch (ties: the first in pop order) replaces it if it beats it.  The
+search then runs to the end (the reference's AllSolution<OneSolution<BranchAndBound<..>>>).
 """
 from __future__ import annotations
 
@@ -64,6 +71,35 @@ class SearchStats:
     launches: int = 0
     filter_steps: int = 0
     solutions: List[np.ndarray] = field(default_factory=list)
+    best: Optional[int] = None                  # branch and bound: the incumbent (None: no solution)
+    best_solution: Optional[np.ndarray] = None  # the lb row of the node that set it
+    incumbents: List[int] = field(default_factory=list)  # every improvement, in order
+
+
+def _objective(objective):
+    """(var, "min" | "max") -> (var, minimize?) or None."""
+    if objective is None:
+        return None
+    var, mode = objective
+    if mode not in ("min", "max"):
+        raise ValueError(f"objective mode must be 'min' or 'max', not {mode!r}")
+    return int(var), mode == "min"
+
+
+def _improve(st: SearchStats, obj, lb: np.ndarray, status: np.ndarray):
+    """The reduce of a propagated batch: the Satisfiable row with the best lb[var] (ties: the lowest row) becomes the incumbent if it
+    beats it."""
+    var, minimize = obj
+    rows = np.nonzero(status == TRUE)[0]
+    if not len(rows):
+        return
+    vals = lb[rows, var].astype(np.int64)
+    r = rows[vals.argmin() if minimize else vals.argmax()]  # argmin / argmax: the first of equal values
+    v = int(lb[r, var])
+    if st.best is None or (v < st.best if minimize else v > st.best):
+        st.best = v
+        st.best_solution = lb[r].copy()
+        st.incumbents.append(v)
 
 
 def bfs_frontier(ctx, lb0: np.ndarray, ub0: np.ndarray, n_open: int, max_rounds: int = 64, active0: Optional[np.ndarray] = None,
@@ -103,12 +139,17 @@ def bfs_frontier(ctx, lb0: np.ndarray, ub0: np.ndarray, n_open: int, max_rounds:
     return L[ok][:n_open], U[ok][:n_open], (None if A is None else A[ok][:n_open]), st
 
 
-def dfs(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = False, node_limit: int = 0, batch: int = 1) -> SearchStats:
+def dfs(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = False, node_limit: int = 0, batch: int = 1, objective=None) -> SearchStats:
     """Depth-first search with a LIFO stack of open nodes (gcollections::VectorStack in the reference).  With
     ``batch=1`` the node order is exactly the reference's left-first DFS (one_solution.rs:46-51, 92-105); with
-    ``batch>1`` the top ``batch`` open nodes are propagated in one launch (batched subtree propagation)."""
+    ``batch>1`` the top ``batch`` open nodes are propagated in one launch (batched subtree propagation).
+    ``objective=(var, "min" | "max")``: branch and bound on that variable (module docstring); the search runs to the end
+    whatever ``all_solutions`` says, and ``best`` / ``best_solution`` / ``incumbents`` of the result report it."""
     from .engine import full_active
     st = SearchStats()
+    obj = _objective(objective)
+    if obj is not None:
+        all_solutions = True
     stack: List[Tuple[np.ndarray, np.ndarray, np.ndarray]] = [
         (np.ascontiguousarray(lb0, np.int32), np.ascontiguousarray(ub0, np.int32), full_active(1, ctx.n_units)[0])
     ]
@@ -122,6 +163,11 @@ def dfs(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = False, node
         L = np.stack([t[0] for t in take])
         U = np.stack([t[1] for t in take])
         A = np.stack([t[2] for t in take])
+        if obj is not None and st.best is not None:  # the bound propagator, folded (an emptied node fails without a launch)
+            if obj[1]:
+                U[:, obj[0]] = np.minimum(U[:, obj[0]], st.best - 1)
+            else:
+                L[:, obj[0]] = np.maximum(L[:, obj[0]], st.best + 1)
         ok = (L <= U).all(axis=1)
         lb, ub, act, status = L.copy(), U.copy(), A.copy(), np.zeros(L.shape[0], np.uint8)
         if ok.any():
@@ -142,6 +188,8 @@ def dfs(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = False, node
             st.solutions.append(lb[r].copy())
             if not all_solutions:
                 done = True
+        if obj is not None:
+            _improve(st, obj, lb, status)
         if done or (node_limit and st.num_nodes >= node_limit):
             break
         unk = np.nonzero(status == UNKNOWN)[0]
@@ -191,12 +239,16 @@ def branch_set(bits: np.ndarray, lb: np.ndarray, ub: np.ndarray, base: int, acti
 
 
 def dfs_set(ctx, lb0: np.ndarray, ub0: np.ndarray, base: int, all_solutions: bool = False, node_limit: int = 0, batch: int = 1,
-            implicit: bool = True) -> SearchStats:
+            implicit: bool = True, objective=None) -> SearchStats:
     """Depth-first search over set-mode nodes (FDSpace): the variables are allocated as IntervalSet::new(lb0, ub0)
-    (example/src/nqueens.rs:32-35); with batch = 1 the node order is the reference's left-first DFS."""
+    (example/src/nqueens.rs:32-35); with batch = 1 the node order is the reference's left-first DFS.  ``objective``: as in dfs;
+    the bound clears the objective's values >= best (min) or <= best (max) from its set."""
     from .engine import full_active
     from .model import interval_bits
     st = SearchStats()
+    obj = _objective(objective)
+    if obj is not None:
+        all_solutions = True
     sw = ctx.set_words
     root = interval_bits(np.asarray(lb0), np.asarray(ub0), sw, base)
     stack: List[Tuple[np.ndarray, Optional[np.ndarray]]] = [(root, None if implicit else full_active(1, ctx.n_units)[0])]
@@ -209,6 +261,10 @@ def dfs_set(ctx, lb0: np.ndarray, ub0: np.ndarray, base: int, all_solutions: boo
                 break
         Bt = np.stack([t[0] for t in take])
         A = None if implicit else np.stack([t[1] for t in take])
+        if obj is not None and st.best is not None:
+            top = base + 64 * sw - 1
+            keep = interval_bits(base, min(st.best - 1, top), sw, base) if obj[1] else interval_bits(max(st.best + 1, base), top, sw, base)
+            Bt[:, obj[0]] &= keep
         ok = Bt.any(axis=2).all(axis=1)  # a folded branch can empty a set: that child is failed without a launch
         status = np.zeros(Bt.shape[0], np.uint8)
         lb = np.ones(Bt.shape[:2], np.int32); ub = np.zeros(Bt.shape[:2], np.int32)
@@ -232,6 +288,8 @@ def dfs_set(ctx, lb0: np.ndarray, ub0: np.ndarray, base: int, all_solutions: boo
             st.solutions.append(lb[r].copy())
             if not all_solutions:
                 done = True
+        if obj is not None:
+            _improve(st, obj, lb, status)
         if done or at_limit:
             break
         unk = np.nonzero(status == UNKNOWN)[0]

@@ -5,12 +5,15 @@ Per round: the top ``batch`` open nodes of the stack are propagated in place (`p
 node is branched on the device (`pcp_branch_device`: FirstSmallestVar / MiddleVal / BinarySplit, folded, children
 inherit the parent's `active` row), the batch is popped and the children are pushed.  With ``batch=1`` the node order
 is exactly the reference's left-first DFS (search/engine/one_solution.rs:46-51, 92-105).
+With ``objective=(var, "min" | "max")`` the round propagates through `pcp_propagate_device_bnb` instead (branch and bound,
+search/branch_and_bound.rs:64-84): the incumbent stays on the device, is folded into every node of the batch before the fixpoint
+and replaced by the batch's best Satisfiable node after it; it comes back in the same copy as the counts.
 PyTorch provides the device buffers; every kernel is this repository's.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 
@@ -27,6 +30,9 @@ class DeviceSearchStats:
     evaluated: int = 0
     max_open: int = 0
     solutions: List[np.ndarray] = field(default_factory=list)
+    best: Optional[int] = None                  # branch and bound: the incumbent (None: no solution)
+    best_solution: Optional[np.ndarray] = None  # the lb row of the node that set it
+    incumbents: List[int] = field(default_factory=list)  # every improvement, one per round at most
 
 
 class DeviceSearch:
@@ -35,7 +41,7 @@ class DeviceSearch:
     the children straight above them, in reverse order, as a new segment: nothing is copied or reordered.  The popped
     parents leave a hole below the new segment; it is reclaimed when that segment is used up (LIFO)."""
 
-    def __init__(self, ctx, batch: int = 1024, capacity: int = 0, device=None, implicit: bool = False, hints=None, cells: bool = False):
+    def __init__(self, ctx, batch: int = 1024, capacity: int = 0, device=None, implicit: bool = False, hints=None, cells: bool = False, objective=None):
         import torch
         self.torch = torch
         self.ctx = ctx
@@ -50,6 +56,17 @@ class DeviceSearch:
         self.cells = bool(cells)
         if self.cells and (not implicit or getattr(ctx, "set_words", 0)):
             raise ValueError("cells=True needs implicit nodes in interval mode")
+        # objective=(var, "min" | "max"): branch and bound (pcp_propagate_device_bnb); the search then always runs to the end
+        self.objective = None
+        if objective is not None:
+            var, mode = objective
+            if mode not in ("min", "max"):
+                raise ValueError(f"objective mode must be 'min' or 'max', not {mode!r}")
+            if self.cells:
+                raise ValueError("branch and bound runs on int32 rows: cells=True cannot take an objective")
+            if not 0 <= int(var) < ctx.n_vars:
+                raise ValueError(f"objective variable {var} is not a variable of the model")
+            self.objective = (int(var), mode)
         self.lb = torch.empty((self.cap, V), dtype=i32, device=self.dev)
         self.ub = None if self.cells else torch.empty((self.cap, V), dtype=i32, device=self.dev)
         # implicit: a node record is its domains only — no `active` rows are kept, the engine derives liveness from the
@@ -64,10 +81,17 @@ class DeviceSearch:
         # one hint per open node (pcp_device_batch.dirty_var): a child is its parent's fixpoint with ONE variable branched on, so the engine
         # may start the child's propagation from that variable alone; the root has none (-1).  Interval mode, implicit nodes, an engine
         # that knows the field (the CPU stand-in of the tests does not).
-        want = bool(getattr(ctx, "supports_hints", False)) and self.implicit and not self.set_words
+        want = bool(getattr(ctx, "supports_hints", False)) and self.implicit and not self.set_words and self.objective is None  # (bnb: no hints)
         self.dirty = torch.full((self.cap,), -1, dtype=i32, device=self.dev) if (want if hints is None else (hints and want)) else None
         self.status = torch.zeros(self.batch, dtype=u8, device=self.dev)
         self.counts = torch.zeros(5, dtype=i32, device=self.dev)
+        if self.objective is not None:
+            # counts, the incumbent and the improvement count side by side: the round's one copy to the host reads all three
+            self.round_buf = torch.zeros(7, dtype=i32, device=self.dev)
+            self.counts, self.best, self.improved = self.round_buf[:5], self.round_buf[5:6], self.round_buf[6:7]
+            self.best_lb = torch.zeros(V, dtype=i32, device=self.dev)
+            self.best_ub = torch.zeros(V, dtype=i32, device=self.dev)
+            self.best_bits = torch.zeros((V, self.set_words), dtype=i64, device=self.dev) if self.set_words else None
         self.segs: List[List[int]] = []  # [start, length], bottom to top
         self.stats = DeviceSearchStats()
 
@@ -143,6 +167,11 @@ class DeviceSearch:
             self.dirty[0] = -1  # the root is propagated from scratch
         self.segs = [[0, 1]]
         self.stats = DeviceSearchStats()
+        if self.objective is not None:
+            from .engine import no_incumbent
+            self.best.fill_(no_incumbent(self.objective[1]))
+            self.improved.zero_()
+            self._improved_seen = 0
         ctx.stats_reset(self._stream())
 
     def advance(self, all_solutions: bool = True, node_limit: int = 0, max_rounds: int = 0, keep_solutions: int = 0, batch: int = 0, stop_at: int = 0) -> bool:
@@ -150,8 +179,14 @@ class DeviceSearch:
         found.  Returns True when the search is over (stack empty or solution found).
         ``node_limit`` is the search's StopNode limit (stop_node.rs:47-62): the node that reaches it is counted as a node and as nothing
         else.  ``stop_at`` only ends this call after that many nodes in total (a caller's chunk of a larger budget, e.g. one rank's share
-        between two exchanges of parallel_search_device): every node's status counts."""
+        between two exchanges of parallel_search_device): every node's status counts.
+        With an objective, ``all_solutions`` is ignored: branch and bound runs to the end of the search."""
         torch, ctx, st = self.torch, self.ctx, self.stats
+        bnb = self.objective is not None
+        if bnb:
+            all_solutions = True
+            obj = {"var": self.objective[0], "mode": self.objective[1], "best": self.best, "best_lb": self.best_lb, "best_ub": self.best_ub,
+                   "best_bits": self.best_bits, "improved": self.improved}
         stream = self._stream()
         batch = min(int(batch) if batch else self.batch, self.batch)
         rounds = 0
@@ -186,6 +221,14 @@ class DeviceSearch:
                 dirty = None if self.dirty is None else self.dirty[lo:top]
                 ctx.propagate_device(n, lb, None, lb, None, None, None, status, stream, dirty=dirty, cells=True)
                 ctx.branch_device_cells(n, lb, status, self.lb[top:], self.counts, stream, child_dirty=None if self.dirty is None else self.dirty[top:])
+            elif bnb and self.bits is None:
+                ctx.propagate_device_bnb(n, lb, ub, lb, ub, act, act, status, obj, stream)
+                ctx.branch_device(n, lb, ub, act, status, self.lb[top:], self.ub[top:], None if self.act is None else self.act[top:],
+                                  self.counts, stream)
+            elif bnb:
+                bits = self.bits[lo:top]
+                ctx.propagate_device_bnb(n, None, None, lb, ub, act, act, status, obj, stream, bits_in=bits, bits_out=bits)
+                ctx.branch_device_set(n, bits, lb, ub, act, status, self.bits[top:], None if self.act is None else self.act[top:], self.counts, stream)
             elif self.bits is None and self.dirty is not None:
                 ctx.propagate_device(n, lb, ub, lb, ub, act, act, status, stream, dirty=self.dirty[lo:top])
                 ctx.branch_device(n, lb, ub, act, status, self.lb[top:], self.ub[top:], None if self.act is None else self.act[top:],
@@ -198,7 +241,14 @@ class DeviceSearch:
                 bits = self.bits[lo:top]
                 ctx.propagate_device(n, None, None, lb, ub, act, act, status, stream, bits_in=bits, bits_out=bits)
                 ctx.branch_device_set(n, bits, lb, ub, act, status, self.bits[top:], None if self.act is None else self.act[top:], self.counts, stream)
-            n_children, n_true, n_false, _, n_other = (int(x) for x in self.counts.cpu().tolist())  # the round's only D2H sync
+            if bnb:
+                n_children, n_true, n_false, _, n_other, best, improved = (int(x) for x in self.round_buf.cpu().tolist())  # the round's only D2H sync
+                if improved != self._improved_seen:
+                    self._improved_seen = improved
+                    st.best = best
+                    st.incumbents.append(best)
+            else:
+                n_children, n_true, n_false, _, n_other = (int(x) for x in self.counts.cpu().tolist())  # the round's only D2H sync
             if n_other:
                 raise RuntimeError(f"{n_other} nodes were refused by the engine (bounds outside the declared hull): the search cannot continue")
             rounds += 1
@@ -233,6 +283,8 @@ class DeviceSearch:
                 self.segs.append([top, n_children])
             st.max_open = max(st.max_open, self.size)
         ctx.set_option("branch_reverse", 0)
+        if bnb and st.best is not None:
+            st.best_solution = self.best_lb.cpu().numpy().copy()
         s = ctx.stats_read(stream)
         st.filter_steps = s["steps"] + s["steps3"]
         st.evaluated = s.get("evaluated", 0)
