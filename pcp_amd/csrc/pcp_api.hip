@@ -1,71 +1,51 @@
-// pcp_api.hip — the C ABI of libpcp_hip.so (include/pcp_hip.h): context, model lowering, launches.
+// pcp_api.hip — the C ABI of libpcp_hip.so (include/pcp_hip.h): context, upload of the lowered model (pcp_lower.hip), launches.
 // Host code only; the kernels are in pcp_kernels.hip.  No CPU fallback exists anywhere in this library.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "pcp_internal.h"
+#include "pcp_lower.h"
 #include "pcp_neq.h"
 
 using namespace pcp;
 
-struct pcp_ctx {
+static_assert(sizeof(U32x2) == sizeof(uint2) && alignof(U32x2) == alignof(uint2), "the payload tables are built as U32x2 and read as uint2");
+
+// The context: the model as pushed (HostModel) and what its lowering found (LoweredInfo, assigned by finalize_model) — both pcp_lower.h —,
+// the device copies of the lowered tables, and the state of the calls.
+struct pcp_ctx : HostModel, LoweredInfo {
   int device = 0;
   int num_cu = 256;
   size_t lds_max = 160 * 1024;
   std::string err;
+  bool dirty = true;   // the model changed since it was last lowered (finalize_model)
 
-  // host model
-  uint32_t n_vars = 0;
-  uint32_t set_words = 0;   // > 0: IntervalSet<i32> domains as bitsets (pcp_model_reset)
-  std::vector<pcp_prop> props;          // as pushed
-  std::vector<uint32_t> unit_of_prop;   // unit index of each prop
-  std::vector<int32_t> formula_of_prop; // formula number of each prop (a leaf of that tree), or -1
-  std::vector<std::vector<pcp_fnode>> formulas;  // pcp_model_push_formula: the trees (leaf.first = index among the formula's own leaves)
-  bool has_formulas = false;            // a formula unit or a Boolean / BooleanNeg leaf: the store runs pcp_formula.hip
-  pcp_fnode* d_fnodes = nullptr; size_t cap_fnodes = 0;
-  uint32_t* d_unit_root = nullptr; size_t cap_unit_root = 0;
-  uint32_t n_units = 0;
-  std::vector<std::vector<uint32_t>> sums;  // term::Sum views: member variables of each term (pcp_model_push_sum)
-  uint32_t* d_sum_off = nullptr; uint32_t* d_sum_mem = nullptr; size_t cap_sum_off = 0, cap_sum_mem = 0;
-  int32_t* d_mul_off = nullptr; size_t cap_mul_off = 0;  // XEqYMulZ offsets (dx, dy, dz) per MUL3 record
-  uint32_t n_sum_slots = 0;             // Sum terms with more than one member (those have a pseudo-slot)
-  bool has_groups = false;
-  bool dirty = true;
-
-  // device model
+  // device model: the tables of pcp_lower.h's Lowered, uploaded by finalize_model; an optional one is valid when LoweredInfo says so
   Rec* d_recs = nullptr;
-  Rec8* d_recs8 = nullptr; size_t cap_recs8 = 0; bool compact = false;
+  Rec8* d_recs8 = nullptr; size_t cap_recs8 = 0;
   WordDesc* d_wdesc = nullptr; size_t cap_wdesc = 0;
   GroupDesc* d_gdesc = nullptr; size_t cap_gdesc = 0;
-  uint32_t word_level = 0;           // 0 = no word descriptors worth using, 1 = XNeqY words only, 2 = XLessY words too
   uint32_t* d_adj_off = nullptr;
   uint32_t* d_adj = nullptr;
-  uint2* d_adjp = nullptr; size_t cap_adjp = 0; bool have_adjp = false;
+  uint2* d_adjp = nullptr; size_t cap_adjp = 0;
   int32_t* d_const = nullptr;
+  uint32_t* d_sum_off = nullptr; uint32_t* d_sum_mem = nullptr; size_t cap_sum_off = 0, cap_sum_mem = 0;
+  int32_t* d_mul_off = nullptr; size_t cap_mul_off = 0;  // XEqYMulZ offsets (dx, dy, dz) per MUL3 record
+  pcp_fnode* d_fnodes = nullptr; size_t cap_fnodes = 0;
+  uint32_t* d_unit_root = nullptr; size_t cap_unit_root = 0;
   // pcp_big.hip: the records sorted by kind and the adjacency payloads, both with the operands' cell coordinates (BigRec / BigAdj, pcp_neq.h)
   uint2* d_brec = nullptr; size_t cap_brec = 0; uint2* d_badj = nullptr; size_t cap_badj = 0;
   bool recs_by_kind_valid = false;  // (built on first use; `big_ok`: the model fits the format — offsets within +-4095, fewer than 98304 variables, no record over two constants)
   bool big_ok = false;
-  uint32_t* d_adjp4 = nullptr; size_t cap_adjp4 = 0; bool have_adjp4 = false;  // 4-byte adjacency payloads (pcp_neq.hip)
-  uint32_t* d_seed_always = nullptr; size_t cap_seed_always = 0; bool have_seed_always = false;  // variables with a Constant neighbour (pcp_neq.hip)
-  bool neq_model = false;            // every record is an XNeqY with at least one variable operand, payload adjacency, slots < 65536
-  // all-different units (pcp_small.hip): a Conjunction / Distinct unit whose members are x != y (no offsets, no constants) over EVERY pair of a
-  // variable set of at most 64 variables — what Distinct::new builds (propagators/distinct.rs:63-83).  ad_tab = [n, then per unit: unit id,
-  // count, first index into ad_vars]; ad_unit_mask bit u = unit u is one.
-  uint32_t* d_ad_tab = nullptr; uint32_t* d_ad_vars = nullptr; uint32_t* d_ad_mask = nullptr; size_t cap_ad_tab = 0, cap_ad_vars = 0, cap_ad_mask = 0;
-  uint32_t n_alldiff = 0;
+  uint32_t* d_adjp4 = nullptr; size_t cap_adjp4 = 0;  // 4-byte adjacency payloads (pcp_neq.hip)
+  uint32_t* d_seed_always = nullptr; size_t cap_seed_always = 0;  // variables with a Constant neighbour (pcp_neq.hip)
+  uint32_t* d_ad_tab = nullptr; uint32_t* d_ad_vars = nullptr; uint32_t* d_ad_mask = nullptr; size_t cap_ad_tab = 0, cap_ad_vars = 0, cap_ad_mask = 0;  // all-different units (pcp_small.hip)
   uint32_t* d_rec_unit = nullptr;    // grouped models only: unit of each record
   uint32_t* d_unit_first = nullptr;  // grouped models only: first record of each unit (+ sentinel)
   size_t cap_rec_unit = 0, cap_unit_first = 0;
-  uint32_t n_slots = 0;
-  bool has_ternary = false;
-  uint32_t uniform_kind = 0xFFFFFFFFu;
-  uint32_t max_deg = 0;
-  bool consts_fit16 = true;      // every interned constant within +-kPackedMax (packed tiles)
   size_t cap_recs = 0, cap_adj = 0, cap_adj_off = 0, cap_const = 0;
 
   // scratch
@@ -161,387 +141,54 @@ int32_t ensure(pcp_ctx* c, T*& p, size_t& cap, size_t n) {
   return PCP_OK;
 }
 
-int arity(uint8_t kind) { return kind >= PCP_BOOL ? 1 : (kind <= PCP_LT ? 2 : 3); }
-bool is_sum_operand(uint32_t var) { return var >= PCP_SUM && var < PCP_NOVAR; }
-
-// Reference-panic checks on one prop (SURVEY.md §8b "Error conventions").
-int32_t validate_prop(pcp_ctx* c, const pcp_prop& p) {
-  if (p.kind > PCP_NBOOL) return fail(c, PCP_ERR_ARG, "unknown propagator kind");
-  if (p.kind >= PCP_BOOL && c->set_words) return fail(c, PCP_ERR_UNSUPPORTED, "the reified layer (Boolean / formulas) is interval mode only");
-  if (p.group_kind > 2 || p.reserved != 0) return fail(c, PCP_ERR_ARG, "bad group_kind/reserved");
-  const int n = arity(p.kind);
-  std::vector<uint32_t> seen;  // every variable the propagator subscribes to, Sum members included
-  for (int i = 0; i < n; ++i) {
-    if (p.var[i] == PCP_NOVAR) return fail(c, PCP_ERR_ARG, "missing operand");
-    if (p.off[i] > PCP_BOUND_MAX || p.off[i] < -PCP_BOUND_MAX) return fail(c, PCP_ERR_CONTRACT, "offset outside +-PCP_BOUND_MAX");
-    if (p.var[i] == PCP_CONST) continue;
-    if (is_sum_operand(p.var[i])) {
-      const uint32_t t = p.var[i] & ~PCP_SUM;
-      if (t >= c->sums.size()) return fail(c, PCP_ERR_ARG, "unknown Sum term (pcp_model_push_sum)");
-      if (c->set_words) return fail(c, PCP_ERR_UNSUPPORTED, "Sum views over IntervalSet domains are not supported (interval mode only)");
-      if (p.kind == PCP_MUL3) return fail(c, PCP_ERR_UNSUPPORTED, "XEqYMulZ over a Sum view is not supported");
-      for (uint32_t m : c->sums[t]) seen.push_back(m);
-      continue;
-    }
-    if (p.var[i] >= c->n_vars) return fail(c, PCP_ERR_CONTRACT, "variable index out of range (variable/store.rs:176-179)");
-    seen.push_back(p.var[i]);
-  }
-  std::sort(seen.begin(), seen.end());
-  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
-    return fail(c, PCP_ERR_CONTRACT, "propagator already subscribed to this variable (reactors/indexed_deps.rs:69-77)");
-  if (p.kind == PCP_MUL3 && c->set_words)
-    return fail(c, PCP_ERR_UNSUPPORTED, "XEqYMulZ over IntervalSet domains is not supported (interval mode only)");
+// ensure + copy of one lowered table; an empty table leaves the buffer as it is (and allocates none)
+template <class T, class H>
+int32_t upload(pcp_ctx* c, T*& p, size_t& cap, const std::vector<H>& v) {
+  static_assert(sizeof(T) == sizeof(H), "host and device element must have one layout");
+  if (v.empty()) return PCP_OK;
+  if (int32_t rc = ensure(c, p, cap, v.size())) return rc;
+  HIP_TRY(c, hipMemcpy(p, v.data(), v.size() * sizeof(H), hipMemcpyHostToDevice));
   return PCP_OK;
 }
+#define PCP_TRY(call)              \
+  do {                             \
+    const int32_t rc__ = (call);   \
+    if (rc__) return rc__;         \
+  } while (0)
 
-// Lower the host props to device records + CSR (done lazily, once per model change).
+// Lower the host props to the tables the kernels read (pcp_lower.hip) and upload them (done lazily, once per model change).
+// No host copy of the tables is kept.
 int32_t finalize_model(pcp_ctx* c) {
   if (!c->dirty) return PCP_OK;
-  const size_t P = c->props.size();
-  std::map<int32_t, uint32_t> const_slot;
-  // slots: [0, n_vars) variables, [n_vars, n_vars + n_sum) Sum views of several members, then the interned constants.
-  // `consts` covers every slot >= n_vars (the Sum slots hold 0: their domain is computed from the members on demand).
-  std::vector<uint32_t> sum_slot(c->sums.size(), 0), sum_off(1, 0), sum_mem;
-  uint32_t n_sum = 0;
-  for (size_t t = 0; t < c->sums.size(); ++t) {
-    if (c->sums[t].size() == 1) { sum_slot[t] = c->sums[t][0]; continue; }  // a Sum of one variable forwards to it (sum.rs:63-64)
-    sum_slot[t] = c->n_vars + n_sum++;
-    sum_mem.insert(sum_mem.end(), c->sums[t].begin(), c->sums[t].end());
-    sum_off.push_back((uint32_t)sum_mem.size());
-  }
-  c->n_sum_slots = n_sum;
-  std::vector<int32_t> consts(n_sum, 0);
-  auto slot_of = [&](uint32_t var, int32_t value) -> uint32_t {
-    if (is_sum_operand(var)) return sum_slot[var & ~PCP_SUM];
-    if (var != PCP_CONST) return var;
-    auto it = const_slot.find(value);
-    if (it != const_slot.end()) return it->second;
-    uint32_t s = c->n_vars + (uint32_t)consts.size();
-    const_slot.emplace(value, s);
-    consts.push_back(value);
-    return s;
-  };
-  // every variable an operand makes the propagator depend on (ViewDependencies: identity.rs:66-69, sum.rs:85-91)
-  auto for_each_dep = [&](uint32_t var, auto&& f) {
-    if (var == PCP_CONST) return;
-    if (is_sum_operand(var)) { for (uint32_t m : c->sums[var & ~PCP_SUM]) f(m); return; }
-    f(var);
-  };
-  std::vector<Rec> recs(P);
-  std::vector<int32_t> mul_off;
-  std::vector<uint32_t> deg(c->n_vars + 1, 0);
-  bool tern = false;
-  for (size_t r = 0; r < P; ++r) {
-    const pcp_prop& p = c->props[r];
-    const int n = arity(p.kind);
-    uint32_t s[3] = {0, 0, 0};
-    int64_t off[3] = {0, 0, 0};
-    for (int i = 0; i < n; ++i) {
-      // a Constant operand carries its value in off[i]; as a pseudo-variable its offset is 0
-      s[i] = slot_of(p.var[i], p.off[i]);
-      off[i] = (p.var[i] == PCP_CONST) ? 0 : p.off[i];
-    }
-    int64_t d;
-    if (n == 1) d = off[0];                       // Boolean / BooleanNeg over the view x + d
-    else if (n == 2) d = off[1] - off[0];         // X = x, Y = y + d
-    else if (p.kind == PCP_MUL3) {                // (x + dx) = (y + dy) * (z + dz): the offsets go to a side table, d = its index
-      d = (int64_t)(mul_off.size() / 3);
-      for (int i = 0; i < 3; ++i) mul_off.push_back((int32_t)off[i]);
-    }
-    else d = off[1] + off[2] - off[0];            // x  vs  y + z + d
-    if (d > PCP_BOUND_MAX || d < -PCP_BOUND_MAX) return fail(c, PCP_ERR_CONTRACT, "folded offset outside +-PCP_BOUND_MAX");
-    recs[r].xk = s[0] | ((uint32_t)p.kind << 28);
-    recs[r].y = s[1];
-    recs[r].z = (n == 3) ? s[2] : 0;
-    recs[r].d = (int32_t)d;
-    tern |= (n != 2);  // (Boolean leaves too: such stores take the formula kernel, never the binary fast paths)
-    for (int i = 0; i < n; ++i) for_each_dep(p.var[i], [&](uint32_t v) { ++deg[v]; });
-  }
-  tern |= n_sum != 0;  // Sum views: generic path only (no compact stream, no adjacency payloads, no word descriptors)
-  const uint32_t n_slots = c->n_vars + (uint32_t)consts.size();
-  if (n_slots >= kMaxSlots) return fail(c, PCP_ERR_UNSUPPORTED, "too many variables");
-  std::vector<uint32_t> adj_off(c->n_vars + 1, 0);
-  for (uint32_t v = 0; v < c->n_vars; ++v) adj_off[v + 1] = adj_off[v] + deg[v];
-  c->max_deg = 0;
-  for (uint32_t v = 0; v < c->n_vars; ++v) c->max_deg = std::max(c->max_deg, deg[v]);
-  std::vector<uint32_t> adj(adj_off[c->n_vars]);
-  {
-    std::vector<uint32_t> fill(adj_off.begin(), adj_off.end() - 1);
-    for (size_t r = 0; r < P; ++r) {
-      const pcp_prop& p = c->props[r];
-      for (int i = 0; i < arity(p.kind); ++i) for_each_dep(p.var[i], [&](uint32_t v) { adj[fill[v]++] = (uint32_t)r; });
-    }
-  }
+  Lowered lo;
+  if (int32_t rc = lower_model(*c, lo, c->err)) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
-  int32_t rc;
-  const size_t Ppad = P ? ((P + 255) / 256) * 256 + kStreamPadRecs : 0;  // see kStreamPadRecs
-  if (P) { const Rec last = recs[P - 1]; recs.resize(Ppad, last); }
-  if ((rc = ensure(c, c->d_recs, c->cap_recs, Ppad))) return rc;
-  if ((rc = ensure(c, c->d_adj_off, c->cap_adj_off, adj_off.size()))) return rc;
-  if ((rc = ensure(c, c->d_adj, c->cap_adj, adj.size()))) return rc;
-  if ((rc = ensure(c, c->d_const, c->cap_const, consts.size()))) return rc;
-  if (P) HIP_TRY(c, hipMemcpy(c->d_recs, recs.data(), Ppad * sizeof(Rec), hipMemcpyHostToDevice));
-  c->uniform_kind = 0xFFFFFFFFu;
-  if (P && !n_sum) {
-    const uint32_t k0 = recs[0].xk >> 28;
-    bool same = (k0 == PCP_NEQ || k0 == PCP_LT);
-    for (size_t r = 1; r < P && same; ++r) same = (recs[r].xk >> 28) == k0;
-    if (same) c->uniform_kind = k0;
-  }
-  HIP_TRY(c, hipMemcpy(c->d_adj_off, adj_off.data(), adj_off.size() * 4, hipMemcpyHostToDevice));
-  if (!adj.empty()) HIP_TRY(c, hipMemcpy(c->d_adj, adj.data(), adj.size() * 4, hipMemcpyHostToDevice));
-  c->have_adjp = false;
-  if (!tern && !adj.empty()) {  // adjacency payloads (ModelDev::adjp)
-    std::vector<uint2> adjp(adj.size());
-    std::vector<uint32_t> fill(adj_off.begin(), adj_off.end() - 1);
-    for (size_t r = 0; r < P; ++r) {
-      const uint32_t x = recs[r].xk & kSlotMask, y = recs[r].y, kind = recs[r].xk >> 28;
-      if (x < c->n_vars) adjp[fill[x]++] = make_uint2(y | (kind << 28), (uint32_t)recs[r].d);
-      if (y < c->n_vars) adjp[fill[y]++] = make_uint2(x | (kind << 28) | (1u << 31), (uint32_t)recs[r].d);
-    }
-    if ((rc = ensure(c, c->d_adjp, c->cap_adjp, adjp.size()))) return rc;
-    HIP_TRY(c, hipMemcpy(c->d_adjp, adjp.data(), adjp.size() * sizeof(uint2), hipMemcpyHostToDevice));
-    c->have_adjp = true;
-  }
-  if (!consts.empty()) HIP_TRY(c, hipMemcpy(c->d_const, consts.data(), consts.size() * 4, hipMemcpyHostToDevice));
-  // assignment-driven path (pcp_neq.hip): all-XNeqY models.  A record over two constants has no variable whose list would
-  // run it: such (degenerate) models keep the generic kernels.  Variables with a Constant neighbour are walked in round 0
-  // whatever their domain — the constant is a singleton without a list of its own.
-  c->neq_model = c->uniform_kind == PCP_NEQ && c->have_adjp && n_slots < 65536u;
-  c->have_seed_always = false;
-  if (c->neq_model) {
-    std::vector<uint32_t> seed((n_slots + 31) / 32, 0u);
-    bool any = false;
-    for (size_t r = 0; r < P && c->neq_model; ++r) {
-      const uint32_t x = recs[r].xk & kSlotMask, y = recs[r].y;
-      if (x >= c->n_vars && y >= c->n_vars) c->neq_model = false;
-      else if (x >= c->n_vars) { seed[y >> 5] |= 1u << (y & 31); any = true; }
-      else if (y >= c->n_vars) { seed[x >> 5] |= 1u << (x & 31); any = true; }
-    }
-    c->have_adjp4 = false;
-    if (c->neq_model && n_slots <= 32768u) {
-      bool fits = true;
-      for (size_t r = 0; r < P && fits; ++r) fits = recs[r].d >= -32767 && recs[r].d <= 32767;
-      if (fits) {
-        std::vector<uint32_t> p4(adj.size());
-        std::vector<uint32_t> fill(adj_off.begin(), adj_off.end() - 1);
-        for (size_t r = 0; r < P; ++r) {
-          const uint32_t x = recs[r].xk & kSlotMask, y = recs[r].y;
-          const int32_t d = recs[r].d;
-          if (x < c->n_vars) p4[fill[x]++] = y | ((uint32_t)(uint16_t)(int16_t)(-d) << 16);
-          if (y < c->n_vars) p4[fill[y]++] = x | (1u << 15) | ((uint32_t)(uint16_t)(int16_t)d << 16);
-        }
-        if ((rc = ensure(c, c->d_adjp4, c->cap_adjp4, p4.size()))) return rc;
-        HIP_TRY(c, hipMemcpy(c->d_adjp4, p4.data(), p4.size() * 4, hipMemcpyHostToDevice));
-        c->have_adjp4 = true;
-      }
-    }
-    if (c->neq_model && any) {
-      if ((rc = ensure(c, c->d_seed_always, c->cap_seed_always, seed.size()))) return rc;
-      HIP_TRY(c, hipMemcpy(c->d_seed_always, seed.data(), seed.size() * 4, hipMemcpyHostToDevice));
-      c->have_seed_always = true;
-    }
-  }
-  if (!mul_off.empty()) {
-    if ((rc = ensure(c, c->d_mul_off, c->cap_mul_off, mul_off.size()))) return rc;
-    HIP_TRY(c, hipMemcpy(c->d_mul_off, mul_off.data(), mul_off.size() * 4, hipMemcpyHostToDevice));
-  }
-  if (n_sum) {
-    if ((rc = ensure(c, c->d_sum_off, c->cap_sum_off, sum_off.size()))) return rc;
-    if ((rc = ensure(c, c->d_sum_mem, c->cap_sum_mem, sum_mem.size()))) return rc;
-    HIP_TRY(c, hipMemcpy(c->d_sum_off, sum_off.data(), sum_off.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_sum_mem, sum_mem.data(), sum_mem.size() * 4, hipMemcpyHostToDevice));
-  }
-  c->compact = !tern && n_slots <= kCompactSlots && P > 0;
-  c->consts_fit16 = true;
-  for (int32_t v : consts) c->consts_fit16 &= (v >= -kPackedMax && v <= kPackedMax);
-  if (c->compact) {
-    std::vector<Rec8> r8(Ppad);
-    for (size_t r = 0; r < Ppad; ++r) {
-      r8[r].xyk = (recs[r].xk & kSlotMask) | (recs[r].y << 15) | ((recs[r].xk >> 28) << 30);
-      r8[r].d = recs[r].d;
-    }
-    if ((rc = ensure(c, c->d_recs8, c->cap_recs8, Ppad))) return rc;
-    HIP_TRY(c, hipMemcpy(c->d_recs8, r8.data(), Ppad * sizeof(Rec8), hipMemcpyHostToDevice));
-  }
-  // word descriptors for the level -1 test of packed tiles (WordDesc, pcp_internal.h)
-  c->word_level = 0;
-  if (c->compact) {
-    const size_t W = (P + 63) / 64;
-    std::vector<WordDesc> wd(W + kStreamPadRecs / 64);
-    size_t good = 0;
-    bool any_lt = false;
-    auto lg = [](uint32_t len) { uint32_t k = 0; while ((2u << k) <= len) ++k; return k; };
-    // one part: records [r0, r1) of one binary kind whose x and y slots each span < kRangeMax and whose offsets fit int16
-    auto make_part = [&](size_t r0, size_t r1, WordPart& out) {
-      const uint32_t kind = recs[r0].xk >> 28;
-      if (kind != PCP_NEQ && kind != PCP_LT) return false;
-      uint32_t xlo = ~0u, xhi = 0, ylo = ~0u, yhi = 0;
-      int32_t dmin = INT32_MAX, dmax = INT32_MIN;
-      for (size_t r = r0; r < r1; ++r) {
-        if ((recs[r].xk >> 28) != kind) return false;
-        const uint32_t x = recs[r].xk & kSlotMask, y = recs[r].y;
-        xlo = std::min(xlo, x); xhi = std::max(xhi, x); ylo = std::min(ylo, y); yhi = std::max(yhi, y);
-        dmin = std::min(dmin, recs[r].d); dmax = std::max(dmax, recs[r].d);
-      }
-      if (xhi - xlo >= kRangeMax || yhi - ylo >= kRangeMax || dmin < -30000 || dmax > 30000) return false;
-      const uint32_t kx = lg(xhi - xlo + 1), ky = lg(yhi - ylo + 1);
-      out.x = xlo | ((xhi - (1u << kx) + 1) << 16);
-      out.y = ylo | ((yhi - (1u << ky) + 1) << 16);
-      out.k = kx | (ky << 4) | ((kind == PCP_NEQ ? 1u : 2u) << 8);
-      out.d = ((uint32_t)dmin & 0xffffu) | ((uint32_t)dmax << 16);
-      any_lt |= kind == PCP_LT;
-      return true;
-    };
-    for (size_t w = 0; w < W; ++w) {
-      const size_t r0 = w * 64, r1 = std::min(P, r0 + 64);
-      WordDesc q;
-      memset(&q, 0, sizeof(q));
-      if (make_part(r0, r1, q.a)) {
-        ++good;
-      } else {
-        size_t rs = r0 + 1;  // first change of x
-        while (rs < r1 && (recs[rs].xk & kSlotMask) == (recs[r0].xk & kSlotMask)) ++rs;
-        WordPart pa, pb;
-        if (rs < r1 && make_part(r0, rs, pa) && make_part(rs, r1, pb) && (pa.k >> 8) == (pb.k >> 8)) {
-          q.a = pa; q.b = pb; q.a.k |= 1u << 12;
-          ++good;
-        } else {
-          memset(&q, 0, sizeof(q));
-        }
-      }
-      wd[w] = q;
-    }
-    if (W && good * 2 >= W && W <= 512u * 1024u) {  // worth a sweep organised by word groups (16-bit lane counters: <= 1023 groups per wavefront)
-      if ((rc = ensure(c, c->d_wdesc, c->cap_wdesc, wd.size()))) return rc;
-      HIP_TRY(c, hipMemcpy(c->d_wdesc, wd.data(), wd.size() * sizeof(WordDesc), hipMemcpyHostToDevice));
-      c->word_level = any_lt ? 2 : 1;
-      // group descriptors: the same idea one level up (64 words at a time; the y operands as a suffix [ylo, n_slots))
-      const size_t G = (W + 63) / 64;
-      std::vector<GroupDesc> gd(G);
-      for (size_t g = 0; g < G; ++g) {
-        GroupDesc q;
-        memset(&q, 0, sizeof(q));
-        const size_t r0 = g * 4096, r1 = std::min(P, r0 + 4096);
-        const uint32_t kind = recs[r0].xk >> 28;
-        bool ok = kind == PCP_NEQ || kind == PCP_LT;
-        uint32_t xlo = ~0u, xhi = 0, ylo = ~0u;
-        int32_t dmin = INT32_MAX, dmax = INT32_MIN;
-        for (size_t r = r0; r < r1 && ok; ++r) {
-          ok = (recs[r].xk >> 28) == kind;
-          const uint32_t x = recs[r].xk & kSlotMask;
-          xlo = std::min(xlo, x); xhi = std::max(xhi, x); ylo = std::min(ylo, recs[r].y);
-          dmin = std::min(dmin, recs[r].d); dmax = std::max(dmax, recs[r].d);
-        }
-        if (ok && xhi - xlo < kRangeMax && dmin >= -30000 && dmax <= 30000) {
-          const uint32_t kx = lg(xhi - xlo + 1);
-          q.x = xlo | ((xhi - (1u << kx) + 1) << 16);
-          q.k = kx | ((kind == PCP_NEQ ? 1u : 2u) << 8);
-          q.ylo = ylo;
-          q.d = ((uint32_t)dmin & 0xffffu) | ((uint32_t)dmax << 16);
-        }
-        gd[g] = q;
-      }
-      if ((rc = ensure(c, c->d_gdesc, c->cap_gdesc, gd.size()))) return rc;
-      HIP_TRY(c, hipMemcpy(c->d_gdesc, gd.data(), gd.size() * sizeof(GroupDesc), hipMemcpyHostToDevice));
-    }
-  }
-  if (c->has_groups) {
-    std::vector<uint32_t> first(c->n_units + 1, (uint32_t)P);
-    for (size_t r = P; r-- > 0;) first[c->unit_of_prop[r]] = (uint32_t)r;
-    if ((rc = ensure(c, c->d_rec_unit, c->cap_rec_unit, P))) return rc;
-    if ((rc = ensure(c, c->d_unit_first, c->cap_unit_first, first.size()))) return rc;
-    HIP_TRY(c, hipMemcpy(c->d_rec_unit, c->unit_of_prop.data(), P * 4, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_unit_first, first.data(), first.size() * 4, hipMemcpyHostToDevice));
-  }
-  c->n_alldiff = 0;
-  if (c->has_groups && !c->has_formulas) {
-    // all-different units: every pair of a set of m <= 64 variables exactly once, as x != y without offsets
-    std::vector<uint32_t> tab{0u}, vars, mask((c->n_units + 31) / 32, 0u);
-    size_t r = 0;
-    while (r < P) {
-      const uint32_t u = c->unit_of_prop[r];
-      size_t e = r;
-      while (e < P && c->unit_of_prop[e] == u) ++e;
-      if (e - r >= 3 && c->props[r].group_kind != 0) {
-        std::vector<uint32_t> vs;
-        std::vector<std::pair<uint32_t, uint32_t>> pairs;
-        bool ok = true;
-        for (size_t k = r; k < e && ok; ++k) {
-          const uint32_t x = recs[k].xk & kSlotMask, y = recs[k].y;
-          ok = (recs[k].xk >> 28) == PCP_NEQ && recs[k].d == 0 && x < c->n_vars && y < c->n_vars && x != y;
-          if (ok) { vs.push_back(x); vs.push_back(y); pairs.emplace_back(std::min(x, y), std::max(x, y)); }
-        }
-        if (ok) {
-          std::sort(vs.begin(), vs.end()); vs.erase(std::unique(vs.begin(), vs.end()), vs.end());
-          std::sort(pairs.begin(), pairs.end());
-          const size_t m = vs.size();
-          // (pcp_small.hip keeps the tables of up to 8 such units over up to 256 variables in LDS: kSmallAdUnits, kSmallAdVars)
-          ok = m <= 64 && tab[0] < 8u && vars.size() + m <= 256 && pairs.size() == m * (m - 1) / 2 && std::adjacent_find(pairs.begin(), pairs.end()) == pairs.end();
-          if (ok) {
-            tab.push_back(u); tab.push_back((uint32_t)m); tab.push_back((uint32_t)vars.size());
-            vars.insert(vars.end(), vs.begin(), vs.end());
-            mask[u >> 5] |= 1u << (u & 31u);
-            ++tab[0];
-          }
-        }
-      }
-      r = e;
-    }
-    if (tab[0]) {
-      if ((rc = ensure(c, c->d_ad_tab, c->cap_ad_tab, tab.size()))) return rc;
-      if ((rc = ensure(c, c->d_ad_vars, c->cap_ad_vars, vars.size()))) return rc;
-      if ((rc = ensure(c, c->d_ad_mask, c->cap_ad_mask, mask.size()))) return rc;
-      HIP_TRY(c, hipMemcpy(c->d_ad_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-      HIP_TRY(c, hipMemcpy(c->d_ad_vars, vars.data(), vars.size() * 4, hipMemcpyHostToDevice));
-      HIP_TRY(c, hipMemcpy(c->d_ad_mask, mask.data(), mask.size() * 4, hipMemcpyHostToDevice));
-      c->n_alldiff = tab[0];
-    }
-  }
-  if (c->has_formulas) {
-    // every unit as a tree for pcp_formula.hip: a standalone propagator = one leaf, a Conjunction / Distinct group = an AND over
-    // its members, a formula = its own tree with the leaves renumbered to record indices
-    std::vector<pcp_fnode> fn;
-    std::vector<uint32_t> root(c->n_units + 1, 0);
-    size_t r = 0;
-    while (r < P) {
-      const uint32_t u = c->unit_of_prop[r];
-      size_t e = r;
-      while (e < P && c->unit_of_prop[e] == u) ++e;
-      root[u] = (uint32_t)fn.size();
-      const int32_t f = c->formula_of_prop[r];
-      if (f >= 0) {
-        const auto& tree = c->formulas[(size_t)f];
-        // (the kernel keeps a tree's node statuses in 64-bit masks; only a FLAT Conjunction of leaves may be wider — it is a loop)
-        if (tree.size() > 64) {
-          bool flat = tree[0].type == PCP_F_AND && (size_t)tree[0].n_children + 1 == tree.size();
-          for (size_t i = 1; i < tree.size() && flat; ++i) flat = tree[i].type == PCP_F_LEAF;
-          if (!flat) return fail(c, PCP_ERR_UNSUPPORTED, "a formula of more than 64 nodes (other than a flat Conjunction of propagators)");
-        }
-        const uint32_t base = (uint32_t)fn.size();
-        for (const pcp_fnode& nd : tree) {
-          pcp_fnode q = nd;
-          q.first = nd.type == PCP_F_LEAF ? (uint32_t)r + nd.first : base + nd.first;
-          fn.push_back(q);
-        }
-      } else if (e - r == 1) {
-        fn.push_back(pcp_fnode{PCP_F_LEAF, 0, 0, (uint32_t)r});
-      } else {
-        if (e - r > 65535) return fail(c, PCP_ERR_UNSUPPORTED, "a Conjunction of more than 65535 members next to formula propagators");
-        const uint32_t base = (uint32_t)fn.size();
-        fn.push_back(pcp_fnode{PCP_F_AND, 0, (uint16_t)(e - r), base + 1});
-        for (size_t k = r; k < e; ++k) fn.push_back(pcp_fnode{PCP_F_LEAF, 0, 0, (uint32_t)k});
-      }
-      r = e;
-    }
-    root[c->n_units] = (uint32_t)fn.size();  // (sentinel: a unit's nodes are root[u] .. root[u + 1])
-    if ((rc = ensure(c, c->d_fnodes, c->cap_fnodes, fn.size()))) return rc;
-    if ((rc = ensure(c, c->d_unit_root, c->cap_unit_root, root.size()))) return rc;
-    if (!fn.empty()) HIP_TRY(c, hipMemcpy(c->d_fnodes, fn.data(), fn.size() * sizeof(pcp_fnode), hipMemcpyHostToDevice));
-    if (!root.empty()) HIP_TRY(c, hipMemcpy(c->d_unit_root, root.data(), root.size() * 4, hipMemcpyHostToDevice));
-  }
-  c->n_slots = n_slots;
-  c->has_ternary = tern;
+  // the four tables every launch names are never null after the first finalize
+  PCP_TRY(ensure(c, c->d_recs, c->cap_recs, lo.recs.size()));
+  PCP_TRY(ensure(c, c->d_adj_off, c->cap_adj_off, lo.adj_off.size()));
+  PCP_TRY(ensure(c, c->d_adj, c->cap_adj, lo.adj.size()));
+  PCP_TRY(ensure(c, c->d_const, c->cap_const, lo.consts.size()));
+  PCP_TRY(upload(c, c->d_recs, c->cap_recs, lo.recs));
+  PCP_TRY(upload(c, c->d_adj_off, c->cap_adj_off, lo.adj_off));
+  PCP_TRY(upload(c, c->d_adj, c->cap_adj, lo.adj));
+  PCP_TRY(upload(c, c->d_const, c->cap_const, lo.consts));
+  PCP_TRY(upload(c, c->d_adjp, c->cap_adjp, lo.adjp));
+  PCP_TRY(upload(c, c->d_adjp4, c->cap_adjp4, lo.adjp4));
+  PCP_TRY(upload(c, c->d_seed_always, c->cap_seed_always, lo.seed_always));
+  PCP_TRY(upload(c, c->d_mul_off, c->cap_mul_off, lo.mul_off));
+  PCP_TRY(upload(c, c->d_sum_off, c->cap_sum_off, lo.sum_off));
+  PCP_TRY(upload(c, c->d_sum_mem, c->cap_sum_mem, lo.sum_mem));
+  PCP_TRY(upload(c, c->d_recs8, c->cap_recs8, lo.recs8));
+  PCP_TRY(upload(c, c->d_wdesc, c->cap_wdesc, lo.wdesc));
+  PCP_TRY(upload(c, c->d_gdesc, c->cap_gdesc, lo.gdesc));
+  if (c->has_groups) PCP_TRY(upload(c, c->d_rec_unit, c->cap_rec_unit, c->unit_of_prop));
+  PCP_TRY(upload(c, c->d_unit_first, c->cap_unit_first, lo.unit_first));
+  PCP_TRY(upload(c, c->d_ad_tab, c->cap_ad_tab, lo.ad_tab));
+  PCP_TRY(upload(c, c->d_ad_vars, c->cap_ad_vars, lo.ad_vars));
+  PCP_TRY(upload(c, c->d_ad_mask, c->cap_ad_mask, lo.ad_mask));
+  PCP_TRY(upload(c, c->d_fnodes, c->cap_fnodes, lo.fnodes));
+  PCP_TRY(upload(c, c->d_unit_root, c->cap_unit_root, lo.unit_root));
+  static_cast<LoweredInfo&>(*c) = lo;
   c->recs_by_kind_valid = false;
   c->dirty = false;
   return PCP_OK;
@@ -763,7 +410,7 @@ int32_t pcp_model_reset(pcp_ctx* c, uint32_t n_vars, uint32_t set_words) {
 int32_t pcp_model_push_props(pcp_ctx* c, uint32_t n, const pcp_prop* props) {
   if (!c || (n && !props)) return PCP_ERR_ARG;
   for (uint32_t i = 0; i < n; ++i) {
-    int32_t rc = validate_prop(c, props[i]);
+    int32_t rc = validate_prop(*c, props[i], c->err);
     if (rc) return rc;
   }
   for (uint32_t i = 0; i < n; ++i) {
@@ -788,29 +435,7 @@ int32_t pcp_model_push_props(pcp_ctx* c, uint32_t n, const pcp_prop* props) {
 
 int32_t pcp_model_push_formula(pcp_ctx* c, uint32_t n_nodes, const pcp_fnode* nodes, uint32_t n_leaves, const pcp_prop* leaves) {
   if (!c || !nodes || !leaves || n_nodes == 0 || n_leaves == 0) return PCP_ERR_ARG;
-  if (c->set_words) return fail(c, PCP_ERR_UNSUPPORTED, "formula propagators are interval mode only");
-  // the tree: children behind their parent and consecutive, every node reached exactly once, every leaf used exactly once, depth <= 8
-  std::vector<uint32_t> depth(n_nodes, 0), uses(n_nodes, 0), leaf_uses(n_leaves, 0);
-  depth[0] = 1; uses[0] = 1;
-  for (uint32_t i = 0; i < n_nodes; ++i) {
-    const pcp_fnode& nd = nodes[i];
-    if (nd.reserved != 0 || nd.type > PCP_F_OR) return fail(c, PCP_ERR_ARG, "bad formula node");
-    if (uses[i] != 1) return fail(c, PCP_ERR_ARG, "formula node not reached exactly once from the root");
-    if (depth[i] > 8) return fail(c, PCP_ERR_UNSUPPORTED, "formula deeper than 8 levels");
-    if (nd.type == PCP_F_LEAF) {
-      if (nd.first >= n_leaves) return fail(c, PCP_ERR_ARG, "formula leaf out of range");
-      if (++leaf_uses[nd.first] != 1) return fail(c, PCP_ERR_ARG, "formula leaf used twice");
-      continue;
-    }
-    if (nd.n_children == 0) return fail(c, PCP_ERR_CONTRACT, "a Conjunction / Disjunction needs at least one child");
-    if (nd.first <= i || (uint64_t)nd.first + nd.n_children > n_nodes) return fail(c, PCP_ERR_ARG, "formula children out of range");
-    for (uint32_t k = 0; k < nd.n_children; ++k) { ++uses[nd.first + k]; depth[nd.first + k] = depth[i] + 1; }
-  }
-  for (uint32_t i = 0; i < n_leaves; ++i) {
-    if (leaf_uses[i] != 1) return fail(c, PCP_ERR_ARG, "formula leaf not used");
-    int32_t rc = validate_prop(c, leaves[i]);
-    if (rc) return rc;
-  }
+  if (int32_t rc = validate_formula(*c, n_nodes, nodes, n_leaves, leaves, c->err)) return rc;
   c->formulas.emplace_back(nodes, nodes + n_nodes);
   ++c->n_units;
   for (uint32_t i = 0; i < n_leaves; ++i) {
@@ -1080,8 +705,7 @@ int32_t pcp_propagate_device(pcp_ctx* c, uint32_t n_nodes, const pcp_device_batc
       (int64_t)c->hull_hi - c->hull_lo <= 1023 && (c->opt_global_dom == 2 || !lds_bytes_for(S, 1, 256, block)) && lds_bytes_big(c->n_vars, S) &&
       lds_bytes_big(c->n_vars, S) <= c->lds_max && (c->opt_global_dom == 2 || n_nodes * 2 > (uint32_t)c->num_cu || words < 64)) {
     if (!c->recs_by_kind_valid) {  // built on first use: only stores that take this path need it
-      const size_t Ppad = (size_t)P ? ((size_t)P + 255) / 256 * 256 + kStreamPadRecs : 0;
-      std::vector<Rec> all(Ppad);
+      std::vector<Rec> all((size_t)P ? ((size_t)P + 255) / 256 * 256 + kStreamPadRecs : 0);
       HIP_TRY(c, hipMemcpy(all.data(), c->d_recs, all.size() * sizeof(Rec), hipMemcpyDeviceToHost));
       std::vector<uint32_t> adj_off(c->n_vars + 1), adj;
       HIP_TRY(c, hipMemcpy(adj_off.data(), c->d_adj_off, adj_off.size() * 4, hipMemcpyDeviceToHost));
@@ -1089,100 +713,12 @@ int32_t pcp_propagate_device(pcp_ctx* c, uint32_t n_nodes, const pcp_device_batc
       if (!adj.empty()) HIP_TRY(c, hipMemcpy(adj.data(), c->d_adj, adj.size() * 4, hipMemcpyDeviceToHost));
       std::vector<int32_t> consts(S - c->n_vars);
       if (!consts.empty()) HIP_TRY(c, hipMemcpy(consts.data(), c->d_const, consts.size() * 4, hipMemcpyDeviceToHost));
-      c->big_ok = c->n_vars < 98304u;
-      // a record with a Constant operand becomes a unary record  var (op) K:  x (kind) c + d  /  c (kind) y + d  <=>  y (>, =, !=) c - d
-      struct BR { uint2 r; uint32_t key; };
-      std::vector<BR> br(P);
-      auto coord = [](uint32_t slot) { return (slot / 3u) | ((slot % 3u) << 15); };
-      const uint32_t nv = c->n_vars;
-      for (size_t r = 0; r < P && c->big_ok; ++r) {
-        const uint32_t x = all[r].xk & kSlotMask, y = all[r].y, kind = all[r].xk >> 28;
-        const int64_t d = all[r].d;
-        if (kind > PCP_LT || (x >= nv && y >= nv)) { c->big_ok = false; break; }
-        // (the folded constant K is computed in 64 bits and must stay far inside int32: the kernel forms K - lo, K - 1 and K + 1; a model
-        // whose constant and offset add up to more than 2^30 in magnitude goes to the generic kernels instead of being wrapped)
-        constexpr int64_t kFoldMax = (int64_t)1 << 30;
-        if (y >= nv) {         // x (kind) K,  K = c + d
-          const uint32_t op = kind == PCP_LT ? 0u : kind == PCP_EQ ? 2u : 3u;
-          const int64_t K = (int64_t)consts[y - nv] + d;
-          if (K < -kFoldMax || K > kFoldMax) { c->big_ok = false; break; }
-          br[r] = BR{make_uint2(coord(x) | (op << 17) | (3u << 30), (uint32_t)(int32_t)K), 3u};
-        } else if (x >= nv) {  // c (kind) y + d:  LT  y > c - d  |  EQ  y = c - d  |  NEQ  y != c - d
-          const uint32_t op = kind == PCP_LT ? 1u : kind == PCP_EQ ? 2u : 3u;
-          const int64_t K = (int64_t)consts[x - nv] - d;
-          if (K < -kFoldMax || K > kFoldMax) { c->big_ok = false; break; }
-          br[r] = BR{make_uint2(coord(y) | (op << 17) | (3u << 30), (uint32_t)(int32_t)K), 3u};
-        } else {
-          if (d < -4095 || d > 4095) { c->big_ok = false; break; }
-          br[r] = BR{make_uint2(coord(x) | (((uint32_t)(int32_t)d & 0x1fffu) << 17) | (kind << 30), coord(y)), kind};
-        }
-      }
+      std::vector<U32x2> brec, badj;
+      c->big_ok = lower_big(all, adj_off, adj, consts, c->n_vars, P, c->opt_big_bank != 0, brec, badj);
       if (c->big_ok) {
-        // the adjacency payloads first (they follow ModelDev::adj, which names records of the UNSORTED table)
-        std::vector<uint2> badj(adj.size());
-        for (uint32_t v = 0; v < nv; ++v)
-          for (uint32_t k = adj_off[v]; k < adj_off[v + 1]; ++k) {
-            const Rec& rec = all[adj[k]];
-            const BR& b = br[adj[k]];
-            const uint32_t x = rec.xk & kSlotMask, y = rec.y, kind = rec.xk >> 28;
-            if (b.key == 3u) { badj[k] = make_uint2(0x7fffu | (((b.r.x >> 17) & 3u) << 18) | (1u << 20), b.r.y); continue; }
-            const bool is_y = x != v;
-            badj[k] = make_uint2(coord(is_y ? x : y) | ((is_y ? 1u : 0u) << 17) | (kind << 18), (uint32_t)rec.d);
-          }
-        std::stable_sort(br.begin(), br.end(), [](const BR& p, const BR& q) { return p.key < q.key; });
-        // Bank-aware order within a kind (round 6; the order of the table is free — every fair schedule reaches the same fixpoint, DESIGN.md §2 —
-        // and the model is immutable).  A cell word is 8 bytes = one PAIR of LDS banks, and a wavefront's ds_read_b64 / 64-bit compare-and-swap is
-        // served one 32-lane half at a time: it is conflict-free iff the half's 32 word indices differ mod 32.  With the model's own (random) order a
-        // half hit ~12 distinct bank pairs out of 32 twice or more: SQ_LDS_BANK_CONFLICT was 0.44 of SQ_LDS_IDX_ACTIVE (profiles/r05_c3_*).  Greedy:
-        // the records of a kind are dealt from 32 buckets (x word mod 32), one per lane of a half, preferring among a bucket's next few records one
-        // whose y word falls on a bank pair the half has not used yet.  Neighbouring lanes then never compare-and-swap the same word either.
-        if (c->opt_big_bank) {
-          size_t s0 = 0;
-          while (s0 < P) {
-            size_t e0 = s0;
-            while (e0 < P && br[e0].key == br[s0].key) ++e0;
-            std::vector<uint32_t> bucket[32];
-            for (size_t r = s0; r < e0; ++r) bucket[br[r].r.x & 31u].push_back((uint32_t)r);
-            size_t head[32] = {0};
-            std::vector<BR> out;
-            out.reserve(e0 - s0);
-            const bool unary = br[s0].key == 3u;
-            size_t pos = s0;           // table position of the next record: halves are positions [32 h, 32 h + 32)
-            uint32_t usedx = 0, usedy = 0;
-            uint32_t rot = 0;
-            while (out.size() < e0 - s0) {
-              if ((pos & 31u) == 0) { usedx = 0; usedy = 0; }
-              // the fullest bucket whose bank pair this half has not used (ties: rotate), else the fullest bucket at all
-              int best = -1; size_t best_n = 0;
-              for (uint32_t i = 0; i < 32; ++i) {
-                const uint32_t b = (i + rot) & 31u;
-                const size_t n = bucket[b].size() - head[b];
-                if (n > best_n && !((usedx >> b) & 1u)) { best_n = n; best = (int)b; }
-              }
-              if (best < 0)
-                for (uint32_t b = 0; b < 32; ++b) { const size_t n = bucket[b].size() - head[b]; if (n > best_n) { best_n = n; best = (int)b; } }
-              std::vector<uint32_t>& bk = bucket[best];
-              size_t pick = head[best];
-              if (!unary)
-                for (size_t k2 = head[best]; k2 < std::min(bk.size(), head[best] + 16); ++k2)
-                  if (!((usedy >> (br[bk[k2]].r.y & 31u)) & 1u)) { pick = k2; break; }
-              std::swap(bk[pick], bk[head[best]]);
-              const BR& chosen = br[bk[head[best]++]];
-              usedx |= 1u << (chosen.r.x & 31u);
-              if (!unary) usedy |= 1u << (chosen.r.y & 31u);
-              out.push_back(chosen);
-              ++pos; ++rot;
-            }
-            std::copy(out.begin(), out.end(), br.begin() + s0);
-            s0 = e0;
-          }
-        }
-        std::vector<uint2> brec(Ppad);
-        for (size_t r = 0; r < Ppad; ++r) brec[r] = br[std::min<size_t>(r, P - 1)].r;
-        if ((rc = ensure(c, c->d_brec, c->cap_brec, brec.size()))) return rc;
-        if ((rc = ensure(c, c->d_badj, c->cap_badj, std::max<size_t>(badj.size(), 1)))) return rc;
-        HIP_TRY(c, hipMemcpy(c->d_brec, brec.data(), brec.size() * sizeof(uint2), hipMemcpyHostToDevice));
-        if (!badj.empty()) HIP_TRY(c, hipMemcpy(c->d_badj, badj.data(), badj.size() * sizeof(uint2), hipMemcpyHostToDevice));
+        if ((rc = ensure(c, c->d_badj, c->cap_badj, std::max<size_t>(badj.size(), 1)))) return rc;  // (never null, even without adjacency)
+        if ((rc = upload(c, c->d_brec, c->cap_brec, brec))) return rc;
+        if ((rc = upload(c, c->d_badj, c->cap_badj, badj))) return rc;
       }
       c->recs_by_kind_valid = true;
     }

@@ -937,3 +937,54 @@ def test_truncate_mirrors_restore(ctx):
     ctx.push_props(props[5:])
     again = ctx.propagate(lb[None], ub[None])
     assert np.array_equal(again[0], full[0]) and again[3][0] == M.TRUE
+
+
+def test_relower_one_context():
+    """Four models lowered one after the other on ONE context — all-XNeqY (payload adjacency, 4-byte payloads, word descriptors), ternary
+    with interned constants, a grouped Distinct (unit tables, the all-different table), all-XNeqY again: whatever an earlier model left
+    behind in the context must not reach a later one.  Every step against the oracle, and on the plan a fresh context chooses."""
+    n = 8
+    queens = M.nqueens_props(n)
+    QL, QU = np.tile(np.ones(n, np.int32), (64, 1)), np.tile(np.full(n, n, np.int32), (64, 1))
+    for k in range(64):  # the 64 placements of the first two queens
+        QL[k, 0] = QU[k, 0] = 1 + k // 8
+        QL[k, 1] = QU[k, 1] = 1 + k % 8
+    # x0 < x1 + 2,  x1 != 5,  x0 + 1 = x1 + x2 - 3,  x2 != 5
+    tern = np.zeros(4, dtype=M.PROP_DTYPE)
+    tern["var"][:] = M.PCP_NOVAR
+    tern["group"] = np.arange(4)
+    for r, (kind, var, off) in enumerate([(M.LT, (0, 1), (0, 2)), (M.NEQ, (1, M.PCP_CONST), (0, 5)), (M.EQ3, (0, 1, 2), (1, -3, 0)), (M.NEQ, (2, M.PCP_CONST), (0, 5))]):
+        tern[r]["kind"] = kind
+        tern[r]["var"][: len(var)] = var
+        tern[r]["off"][: len(off)] = off
+    TL = np.array([[0, 0, 0], [4, 5, 0], [0, 5, 5], [9, 0, 0]], np.int32)
+    TU = np.array([[9, 9, 9], [9, 6, 9], [9, 5, 9], [9, 3, 2]], np.int32)
+    vs, cs = M.VStore(), M.CStore()
+    cs.alloc(M.Distinct([vs.alloc((1, 4)) for _ in range(4)]))
+    dist = cs.lower(4)
+    DL = np.array([[1, 1, 1, 1], [2, 1, 1, 1], [1, 2, 3, 4], [1, 1, 2, 3], [4, 1, 1, 1]], np.int32)
+    DU = np.array([[4, 4, 4, 4], [2, 4, 4, 4], [1, 2, 3, 4], [1, 1, 4, 4], [4, 4, 4, 1]], np.int32)
+    DA = np.array([[1], [1], [1], [1], [0]], np.uint64)  # the unit active, but for the last node
+    steps = [("queens", n, queens, QL, QU, None), ("ternary", 3, tern, TL, TU, None), ("distinct", 4, dist, DL, DU, DA), ("queens again", n, queens, QL, QU, None)]
+
+    def run(c, n_vars, props, L, U, act):
+        c.set_model(n_vars, props)
+        got = c.propagate_implicit(L, U) if act is None else c.propagate(L, U, act)
+        return got, c.last_plan()
+
+    one = E.Context(0)
+    try:
+        for what, n_vars, props, L, U, act in steps:
+            ref = orc.OracleModel(n_vars, props).consistency(L, U, act)
+            got, plan = run(one, n_vars, props, L, U, act)
+            assert_parity(ref[:4], got[:4], what)
+            fresh = E.Context(0)
+            try:
+                got_f, plan_f = run(fresh, n_vars, props, L, U, act)
+            finally:
+                fresh.close()
+            assert_parity(ref[:4], got_f[:4], what + " [fresh context]")
+            assert plan["path"] == plan_f["path"] and plan == plan_f, (what, plan, plan_f)
+            assert plan["path"] == (1 if props is queens else 4), (what, plan)
+    finally:
+        one.close()
