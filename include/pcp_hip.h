@@ -264,6 +264,30 @@ int32_t pcp_propagate_device(pcp_ctx* ctx, uint32_t n_nodes, const pcp_device_ba
  * operation on `bits`.) */
 int32_t pcp_propagate_device_units(pcp_ctx* ctx, uint32_t n_nodes, const pcp_device_batch* batch, const uint32_t* node_unit_off,
                                    const pcp_prop* node_units, void* hip_stream);
+/* Node EXCLUSIONS — the narrow companion of pcp_propagate_device_units, on the assignment-driven all-XNeqY kernel (plan.path 1): stores of
+ * any size that fit LDS (N-queens-1000), packed cells, hints, the worklist rounds.  Of the unary propagators a branch appends only Enumerate's
+ * right branch  x != v  over an Identity variable (search/branching/enumerate.rs:54-59) cannot be folded into bounds by the caller: on
+ * Interval<i32> it removes a value only at a bound (x_neq_y.rs:82-93), so with v inside the domain it removes nothing and stays in that ONE
+ * node's cstore until v reaches a bound.  An exclusion list is data that travels with a node, 8 bytes per entry — what a brancher writes:
+ *   excl_off : device uint32 [n_nodes + 1], CSR offsets into excl (NULL = no node has any: exactly pcp_propagate_device)
+ *   excl     : device pcp_excl [excl_off[n_nodes]]
+ * Node i is propagated as if  XNeqY(Identity(var), Constant(value))  had been allocated behind the model's propagators once for each entry of
+ * excl[excl_off[i] .. excl_off[i + 1])  — what Branch::distribute does (search/branching/branch.rs:36-55).  The exclusions are scheduled with
+ * the model's propagators (every one once, then again while anything narrows) and count in the status: a node is PCP_TRUE only if every
+ * exclusion is entailed too (its value lies outside [lb, ub]); x assigned to an excluded value gives PCP_FALSE.  Any number of exclusions per
+ * node, duplicates and any order are allowed.  Their liveness is not reported: the caller drops an exclusion once its value has left the
+ * domain.  An entry with var >= n_vars refuses that node only (PCP_STATUS_HULL, outputs untouched, sticky flag).
+ * pcp_stats: every test of an exclusion is one step; a node's initial schedule (n_recs steps) grows by its number of exclusions.
+ * Accepted: interval mode, an all-XNeqY model whose store fits LDS, implicit nodes (active_in == NULL; active_out on request), int32 rows,
+ * dirty_var hints.  Anything else returns PCP_ERR_UNSUPPORTED with a message: set mode (it needs none of this), formula propagators, any other
+ * model, a store that does not fit LDS, cell_format != 0, options force_path 2 / global_dom, the device DFS stack.
+ * Enqueued on hip_stream, not synchronised, no host read-back. */
+typedef struct {
+  uint32_t var;   /* an Identity view, < n_vars */
+  int32_t value;  /* x(var) != value */
+} pcp_excl;
+int32_t pcp_propagate_device_excl(pcp_ctx* ctx, uint32_t n_nodes, const pcp_device_batch* batch, const uint32_t* excl_off, const pcp_excl* excl,
+                                  void* hip_stream);
 /* Branch and bound — the reference's minimize / maximize (search/branch_and_bound.rs:64-84).  Once a solution is known, every node entered
  * gets one extra unary propagator before its propagation: Minimize  XLessY(var, Constant(best))  (var < best), Maximize  x_greater_y(var,
  * Constant(best))  (var > best).  It narrows its variable once and is then entailed, so it is folded into the node's domain, like

@@ -45,6 +45,14 @@ pub struct pcp_prop {
     pub off: [i32; 3],
 }
 
+/// One value exclusion of a node: x(var) != value (pcp_propagate_device_excl).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct pcp_excl {
+    pub var: u32,
+    pub value: i32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct pcp_stats {
@@ -175,6 +183,7 @@ extern "C" {
     /// `node_unit_off` device u32 [n_nodes + 1], `node_units` device pcp_prop records (one variable against one Constant).
     pub fn pcp_propagate_device_units(ctx: *mut pcp_ctx, n_nodes: u32, batch: *const pcp_device_batch, node_unit_off: *const u32,
                                       node_units: *const pcp_prop, hip_stream: *mut c_void) -> i32;
+    pub fn pcp_propagate_device_excl(ctx: *mut pcp_ctx, n_nodes: u32, batch: *const pcp_device_batch, excl_off: *const u32, excl: *const pcp_excl, hip_stream: *mut c_void) -> i32; // Enumerate's x != v on the all-XNeqY kernel
     pub fn pcp_branch_device(ctx: *mut pcp_ctx, n_nodes: u32, lb: *const i32, ub: *const i32, active: *const u64, status: *const u8,
                              child_lb: *mut i32, child_ub: *mut i32, child_active: *mut u64, counts: *mut u32,
                              hip_stream: *mut c_void) -> i32; // Brancher<FirstSmallestVar, MiddleVal, BinarySplit>::enter

@@ -242,7 +242,9 @@ int32_t propagate_set_device(pcp_ctx* c, uint32_t n_nodes, const pcp_device_batc
 
 // All-XNeqY models, implicit-active nodes: the assignment-driven kernel (pcp_neq.hip).  Returns 1 when the variable store does
 // not fit LDS even with one node per workgroup (the caller falls through to the generic kernels).
-int32_t propagate_neq_device(pcp_ctx* c, uint32_t n_nodes, const pcp_device_batch* bt, hipStream_t stream) {
+// excl_off / excl: pcp_propagate_device_excl's per-node exclusions (device pointers), or null.
+int32_t propagate_neq_device(pcp_ctx* c, uint32_t n_nodes, const pcp_device_batch* bt, hipStream_t stream, const uint32_t* excl_off = nullptr,
+                             const pcp_excl* excl = nullptr) {
   const uint32_t S = c->n_slots, V = c->n_vars, P = (uint32_t)c->props.size();
   const bool hull_fits16 = c->hull_set && c->hull_lo >= -kPackedMax && c->hull_hi <= kPackedMax;
   const bool packed = hull_fits16 && c->consts_fit16 && c->opt_packed;
@@ -287,6 +289,8 @@ int32_t propagate_neq_device(pcp_ctx* c, uint32_t n_nodes, const pcp_device_batc
   // (the tiles behind the static ones are dealt to EIGHT residues of blockIdx.x: a grid of fewer than eight workgroups — a device or an option
   // that leaves fewer than eight resident — would never draw some of them: fixed stride there)
   a.tile_ctr = (c->opt_neq_persist && c->opt_neq_dynamic && !c->dfs_sp && plan.grid >= 8u && (uint64_t)a.tile_static * plan.grid < (n_nodes + B - 1) / B) ? c->d_tile_ctr : nullptr;
+  a.excl_off = excl_off; a.excl = excl;
+  if (excl_off) a.tile_ctr = nullptr;  // (the EXCL kernels take their tiles by the fixed stride)
   if (a.tile_ctr) {
     // The tickets belong to the context and must be zero when a launch starts.  A launch that ended cleanly left them zero; after a HIP error on
     // this context they are zeroed here; and a launch on a different stream than the last ticketed one first waits for that one to end.
@@ -1116,6 +1120,32 @@ int32_t pcp_propagate_device_units(pcp_ctx* c, uint32_t n_nodes, const pcp_devic
   const int32_t rc = pcp_propagate_device(c, n_nodes, bt, hip_stream);
   c->cur_nu_off = nullptr; c->cur_nu = nullptr;
   return rc;
+}
+
+// ≡ Consistency::consistency for nodes that carry value exclusions of their own — Enumerate's right branches x != v (enumerate.rs:54-59) — on
+// the assignment-driven all-XNeqY kernel (pcp_neq.hip, the EXCL instantiations): the narrow companion of pcp_propagate_device_units.
+int32_t pcp_propagate_device_excl(pcp_ctx* c, uint32_t n_nodes, const pcp_device_batch* bt, const uint32_t* excl_off, const pcp_excl* excl, void* hip_stream) {
+  if (!c || !bt) return PCP_ERR_ARG;
+  if (!excl_off) return pcp_propagate_device(c, n_nodes, bt, hip_stream);
+  if (!excl) return fail(c, PCP_ERR_ARG, "excl must not be null when excl_off is given");
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const int32_t rc = finalize_model(c);
+  if (rc) return rc;
+  c->ev_valid = false;
+  if (n_nodes == 0) return PCP_OK;
+  if (!bt->status) return fail(c, PCP_ERR_ARG, "status must not be null");
+  if (bt->cell_format > PCP_CELLS_PACKED16 || bt->reserved) return fail(c, PCP_ERR_ARG, "unknown cell_format (or reserved != 0)");
+  if (c->set_words) return fail(c, PCP_ERR_UNSUPPORTED, "node exclusions: interval mode only (set mode needs none: x != v is an exact set operation on `bits`)");
+  if (c->has_formulas) return fail(c, PCP_ERR_UNSUPPORTED, "node exclusions: stores without formula propagators");
+  if (!c->neq_model || !c->opt_neq_path) return fail(c, PCP_ERR_UNSUPPORTED, "node exclusions: all-XNeqY models on the assignment-driven kernel only (pcp_propagate_device_units serves small stores of any model)");
+  if (bt->cell_format) return fail(c, PCP_ERR_UNSUPPORTED, "node exclusions: int32 rows only (cell_format PCP_CELLS_PACKED16 is refused)");
+  if (bt->active_in || !c->opt_implicit) return fail(c, PCP_ERR_UNSUPPORTED, "node exclusions: implicit nodes only (active_in must be null)");
+  if (c->opt_force_path == 2 || c->opt_global_dom) return fail(c, PCP_ERR_UNSUPPORTED, "node exclusions: force_path 2 / global_dom keep the generic kernels, which do not read them");
+  if (c->dfs_sp) return fail(c, PCP_ERR_UNSUPPORTED, "node exclusions: not on the device DFS stack");
+  if (!bt->lb_in || !bt->ub_in || !bt->lb_out || !bt->ub_out) return fail(c, PCP_ERR_ARG, "domain pointers must not be null");
+  const int32_t rcn = propagate_neq_device(c, n_nodes, bt, stream, excl_off, excl);
+  return rcn == 1 ? fail(c, PCP_ERR_UNSUPPORTED, "node exclusions: the variable store does not fit LDS") : rcn;
 }
 
 // Branch and bound (pcp_bnb.hip): fold the incumbent into the objective's domain, the fixpoint of pcp_propagate_device on the folded rows,

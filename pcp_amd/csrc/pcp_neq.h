@@ -43,6 +43,8 @@ struct NeqArgs {
   int32_t* ub_out;
   uint8_t* status;
   pcp_stats* stats;
+  const uint32_t* excl_off;     // pcp_propagate_device_excl: [n_nodes + 1] CSR offsets into excl, or null (then the EXCL kernels are not launched)
+  const pcp_excl* excl;         //   the nodes' own value exclusions x(var) != value (Enumerate's right branches), 8 bytes each
 };
 size_t lds_bytes_neq(uint32_t n_slots, uint32_t n_vars, uint32_t nodes_per_block, bool packed, uint32_t wgs = 2);
 hipError_t launch_neqfix(const NeqArgs& a, const LaunchPlan& p, hipStream_t stream);

@@ -527,6 +527,68 @@ __device__ __forceinline__ uint32_t neq_write_back(const Tile& tl, const int32_t
   return wb_need;
 }
 
+// ---- EXCL: the nodes' own value exclusions (pcp_propagate_device_excl).  Entry (var, value) of node i is the reference's
+// XNeqY(Identity(var), Constant(value)) in that ONE node's cstore — Enumerate's right branch (search/branching/enumerate.rs:54-59, allocated by
+// Branch::distribute, branch.rs:36-55).  On Interval<i32> it removes its value only at a bound (x_neq_y.rs:82-93), so with the value inside the
+// domain it does nothing and stays subscribed until the value reaches a bound: it has to travel with its node.
+// The sweep: one wavefront per node of the tile, lanes striding over the node's entries (8 bytes each, read from global memory: they are
+// L2-resident and the LDS carve stays what it is).  Per entry what pcp_small.hip does for a node unit of kind PCP_NEQ, through the tile's
+// TileDom*: value == lb raises lb, value == ub lowers ub (an assigned variable at its excluded value ends empty: the node fails) — so the
+// changed marks, N_DIRTY and the counters behave as for any narrowing.  The sweep repeats WAVE-LOCALLY while a lane narrowed: exclusions
+// l+1, l+2, l in that order move lb to l+3 in three passes of one wavefront, not in three rounds of the workgroup.  Every (entry, pass) is one
+// step (ctr.ev); the first pass of the first sweep stands for the initial schedule (ev0).  An entry with var >= n_vars refuses its node.
+// Packed cells: a value outside +-kPackedMax is in no domain.  int2 cells: staging refuses a node with a bound beyond +-kBoundMax (2^29 - 1), so
+// a value that equals a bound is within that range and lb + 1 / ub - 1 cannot overflow.
+template <bool PACKED, class Tile>
+__device__ __forceinline__ void neq_excl_sweep(const Tile& tl, const NeqArgs& a, Ctr& ctr, uint32_t& ev0, const bool first) {
+  const uint32_t inert = tl.misc[N_FAIL] | tl.misc[N_OOB];
+  for (uint32_t b = tl.wv; b < tl.nb; b += tl.nwv) {
+    if ((inert >> b) & 1u) continue;  // (wave-uniform)
+    const uint32_t nid = tl.misc[N_NID + b];
+    const uint32_t e0 = (uint32_t)__builtin_amdgcn_readfirstlane(a.excl_off[nid]), e1 = (uint32_t)__builtin_amdgcn_readfirstlane(a.excl_off[nid + 1]);
+    const auto dm = tl.dom_of(b, &ctr);
+    for (uint32_t pass = 0;; ++pass) {
+      bool moved = false, malformed = false;
+      for (uint32_t i = e0 + tl.lane; i < e1; i += 64u) {
+        const pcp_excl x = a.excl[i];
+        if (x.var >= tl.V) { malformed = true; continue; }
+        ++ctr.ev;
+        if (first && pass == 0) ++ev0;
+        if (PACKED && (x.value < -kPackedMax || x.value > kPackedMax)) continue;
+        const int2 d = dm.load(x.var);
+        if (d.x > d.y) continue;  // (emptied by another entry: the node has failed)
+        if (x.value == d.x) { dm.raise_lb(x.var, d.x + 1); moved = true; }
+        else if (x.value == d.y) { dm.lower_ub(x.var, d.y - 1); moved = true; }
+      }
+      if (__ballot(malformed)) {  // refused, this node only (PCP_STATUS_HULL, sticky flag): its outputs are left alone
+        if (tl.lane == 0) { atomicOr(&tl.misc[N_OOB], 1u << b); atomicMax(a.violation, 1u); }
+        break;
+      }
+      if (!__ballot(moved)) break;
+      if ((__hip_atomic_load(&tl.misc[N_FAIL], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> b) & 1u) break;
+    }
+  }
+}
+// ... and their part of the status (store.rs:250-256): x != value is entailed iff value lies outside [lb, ub] (x_neq_y.rs:71-73); at a
+// fixpoint that did not fail a value inside is strictly inside.  One wavefront per node that is neither failed nor refused.
+template <bool PACKED, class Tile>
+__device__ __forceinline__ void neq_excl_status(const Tile& tl, const NeqArgs& a) {
+  const uint32_t inert = tl.misc[N_FAIL] | tl.misc[N_OOB];
+  for (uint32_t b = tl.wv; b < tl.nb; b += tl.nwv) {
+    if ((inert >> b) & 1u) continue;
+    const uint32_t nid = tl.misc[N_NID + b];
+    const uint32_t e0 = (uint32_t)__builtin_amdgcn_readfirstlane(a.excl_off[nid]), e1 = (uint32_t)__builtin_amdgcn_readfirstlane(a.excl_off[nid + 1]);
+    bool open = false;
+    for (uint32_t i = e0 + tl.lane; i < e1; i += 64u) {
+      const pcp_excl x = a.excl[i];
+      if (x.var >= tl.V) continue;
+      const int2 d = cell_bounds<PACKED>(tl.dom[tl.rowof(x.var) + b]);
+      open |= x.value >= d.x && x.value <= d.y;
+    }
+    if (__ballot(open) && tl.lane == 0) atomicOr(&tl.misc[N_UNK], 1u << b);
+  }
+}
+
 // ---- the jumps of a round: each window's bound moves to the first value no assigned neighbour forbids (the windows were filled by the
 // list walk of one- and two-node masks: see the kernel's header).  Every skipped value is one the filter would remove at the bound.
 // QUIET jumps (round 5).  The walk that filled a window saw EVERY entry of the variable's list, so a bound that jumped to a value inside the
@@ -1553,7 +1615,10 @@ __device__ __forceinline__ void neq_stage_tile(const Tile& tl, const NeqArgs& a,
 // CELLS: the bounds rows in HBM are rows of packed cells (pcp_device_batch.cell_format PCP_CELLS_PACKED16; PACKED batch launches only).
 // TICKETS: the launch has more tiles than `tile_static` per workgroup and deals the rest by tickets (NeqArgs::tile_ctr != null).  A template flag,
 // not a run-time test: the ticket's registers cost the 16 384-node headline launch — which never draws — 16 B of scratch per lane in round 5.
-template <bool PACKED, bool PAY4, bool DFS, int BT, bool CELLS = false, bool TICKETS = false>
+// EXCL: the nodes carry value exclusions of their own (NeqArgs::excl_off / excl, pcp_propagate_device_excl): neq_excl_sweep at the top of every
+// round, neq_excl_status behind the status scan.  Everything it adds sits under `if constexpr (EXCL)`; instantiated for batch launches with a
+// run-time tile size, int32 rows and a fixed tile stride only (DFS = false, BT = 0, CELLS = false, TICKETS = false).
+template <bool PACKED, bool PAY4, bool DFS, int BT, bool CELLS = false, bool TICKETS = false, bool EXCL = false>
 __global__ void __launch_bounds__(DFS ? 512 : 1024) __attribute__((amdgpu_waves_per_eu(4))) neqfix_kernel(const NeqArgs a_in) {  // (four wavefronts per SIMD: the forest runs 16 per CU)
   NeqArgs a = a_in;
   a.stats += blockIdx.x & (kStatSlots - 1);
@@ -1828,8 +1893,20 @@ __global__ void __launch_bounds__(DFS ? 512 : 1024) __attribute__((amdgpu_waves_
   for (uint32_t round = fstate;; ++round) {
     if (round >= kMaxRounds) { if (tid == 0) { atomicOr(&misc[N_OOB], nb >= 32 ? 0xFFFFFFFFu : ((1u << nb) - 1u)); atomicMax(a.violation, 1u); } bar(); break; }  // (refused, not hung)
     const uint32_t m_count = (round & 1u) ? N_COUNT1 : N_COUNT0, m_rmask = (round & 1u) ? N_RMASK1 : N_RMASK0, m_win = (round & 1u) ? N_WIN1 : N_WIN0;
-    const uint32_t inert = misc[N_FAIL] | misc[N_OOB];
+    uint32_t inert = misc[N_FAIL] | misc[N_OOB];
     const uint32_t narrow_before = ctr.narrow;
+    // (x) EXCL: the nodes' own exclusions, all of them, every round (neq_excl_sweep) — the first time behind the staging barrier and before
+    // round 0's list is built, so that its narrowings are marks like any other.  `narrow_before` was taken above: a sweep that narrowed
+    // keeps the loop alive (and its marks give the round a list).  INVARIANT: a tile's rounds end only after a sweep over the FINAL cells
+    // has narrowed nothing.  Every exit below is reached with the cells as this sweep left them or found them — `total == 0`: no mark, so
+    // neither the sweep nor the round before changed a cell that still matters; "narrowed nothing, no window": nothing moved since the sweep
+    // — except the jumps (neq_apply_jumps may land a bound on an excluded value, without a mark when the jump was quiet): they are followed
+    // by another round, i.e. by another sweep.  The kMaxRounds refusal above stands.
+    if constexpr (EXCL) {
+      neq_excl_sweep<PACKED>(NeqTile<PACKED>{dom, chg, misc, adjo, list, win, V, Wv, B, sh, nb, tid, lane, wv, nwv, nth}, a, ctr, ev0, round == 0);
+      bar();
+      inert = misc[N_FAIL] | misc[N_OOB];
+    }
     // (a0) the cheaper of two covers.  A changed variable that is NOT assigned wakes only propagators that can act if their OTHER
     // side is assigned (x_neq_y.rs:82-93), and those sit in the assigned variables' lists too.  After an assignment near the root
     // ~V variables of a node lose a bound and each would re-walk its whole list to find nothing; the lists of the node's few
@@ -1837,6 +1914,8 @@ __global__ void __launch_bounds__(DFS ? 512 : 1024) __attribute__((amdgpu_waves_
     // become {assigned variables} + {changed variables with a Constant neighbour: that record is in their own list only}.  Every
     // propagator incident to a changed variable that can act is still evaluated, so the fixpoint is the same; the choice is made
     // again every round, so the tail of a cascade (few changed variables) goes back to the changed lists and their jump windows.
+    // (EXCL: the exclusions are in no list and need no cover — the sweep (x) runs every one of them every round, whatever the marks say; the
+    // same holds for the hinted form of round 0, which lists the hinted variable alone.)
     // One wavefront per node; nothing leaves the wavefront until the barrier.  (-DPCP_NEQ_NO_RESWEEP: A/B builds without it.)
 #ifndef PCP_NEQ_NO_RESWEEP
 #ifdef PCP_NEQ_RESWEEP_DEAD  // A/B: the code is there, never run
@@ -1899,6 +1978,7 @@ __global__ void __launch_bounds__(DFS ? 512 : 1024) __attribute__((amdgpu_waves_
   // chains one after the other in every wavefront.
   if (fstate != 3u) {
     neq_status_scan<PACKED, DFS>(tl, pay, (a.debug & 2u) != 0);
+    if constexpr (EXCL) neq_excl_status<PACKED>(tl, a);  // (a node with an exclusion whose value is still inside its variable's domain is Unknown)
     if constexpr (!DFS && TICKETS) { if (tid == nth - 64u && draws()) misc_base[kNextTileWord] = neq_karg<uint32_t>(offsetof(NeqArgs, tile_static)) * gridDim.x + 8u * ticket + (blockIdx.x & 7u); }
   }
 
@@ -1943,6 +2023,12 @@ __global__ void __launch_bounds__(DFS ? 512 : 1024) __attribute__((amdgpu_waves_
     const unsigned long long s2 = (unsigned long long)active_nodes * a.m.n_recs + *reinterpret_cast<unsigned long long*>(&misc[N_STEPS]);
     const unsigned long long sev = *reinterpret_cast<unsigned long long*>(&misc[N_EV]), sfu = *reinterpret_cast<unsigned long long*>(&misc[N_FULL]);
     const uint32_t nf = __popc(misc[N_FAIL] & (nb >= 32 ? 0xFFFFFFFFu : ((1u << nb) - 1u)));
+    if constexpr (EXCL) {  // the initial schedule of a node holds its own exclusions too: one step each (the later tests are in N_STEPS / tot_later)
+      unsigned long long xs = 0;
+      for (uint32_t b = 0; b < nb; ++b)
+        if (!((misc[N_OOB] >> b) & 1u)) xs += a.excl_off[misc[N_NID + b] + 1] - a.excl_off[misc[N_NID + b]];
+      if (xs) atomicAdd(&accl[0], xs);
+    }
     if constexpr (DFS) {
       // the counters are added up in registers and handed over once per launch: six same-address atomics per node are nothing for one
       // tree and serialise a forest of hundreds (pcp_dfs_forest_device)
@@ -2038,13 +2124,13 @@ size_t lds_bytes_neq(uint32_t n_slots, uint32_t n_vars, uint32_t nodes_per_block
   return c.total <= 160 * 1024 ? c.total : 0;
 }
 
-template <bool PACKED, bool PAY4, bool DFS, int BT, bool CELLS, bool TICKETS>
+template <bool PACKED, bool PAY4, bool DFS, int BT, bool CELLS, bool TICKETS, bool EXCL = false>
 static hipError_t launch_neq_t(const NeqArgs& a, const LaunchPlan& p, hipStream_t stream) {
   if (p.lds_bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(neqfix_kernel<PACKED, PAY4, DFS, BT, CELLS, TICKETS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(neqfix_kernel<PACKED, PAY4, DFS, BT, CELLS, TICKETS, EXCL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((neqfix_kernel<PACKED, PAY4, DFS, BT, CELLS, TICKETS>), dim3(p.grid), dim3(p.block), p.lds_bytes, stream, a);
+  hipLaunchKernelGGL((neqfix_kernel<PACKED, PAY4, DFS, BT, CELLS, TICKETS, EXCL>), dim3(p.grid), dim3(p.block), p.lds_bytes, stream, a);
   return hipGetLastError();
 }
 template <bool PACKED, bool PAY4, bool DFS, int BT, bool CELLS = false>
@@ -2148,6 +2234,12 @@ hipError_t launch_neqfix(const NeqArgs& a, const LaunchPlan& p, hipStream_t stre
   if (a.dfs.n_steps) {
     if (a.nodes_per_block != 1 || p.grid < 1 || !a.dfs.sp || !a.dfs.stop || !a.dfs.counters) return hipErrorInvalidValue;  // (grid = trees)
     return launch_neq_d<true, 1>(a, p, stream);
+  }
+  if (a.excl_off) {
+    // nodes with exclusions of their own: the four EXCL kernels (run-time tile size, int32 rows, fixed tile stride)
+    if (!a.excl || a.cell_rows || a.tile_ctr || a.sp_ptr) return hipErrorInvalidValue;
+    if (a.adjp4) return a.packed ? launch_neq_t<true, true, false, 0, false, false, true>(a, p, stream) : launch_neq_t<false, true, false, 0, false, false, true>(a, p, stream);
+    return a.packed ? launch_neq_t<true, false, false, 0, false, false, true>(a, p, stream) : launch_neq_t<false, false, false, 0, false, false, true>(a, p, stream);
   }
   return a.nodes_per_block == 16 ? launch_neq_d<false, 16>(a, p, stream) : launch_neq_d<false, 0>(a, p, stream);
 }

@@ -25,7 +25,7 @@ ERRORS = {-1: "PCP_ERR_ARG", -2: "PCP_ERR_CONTRACT", -3: "PCP_ERR_HIP", -4: "PCP
 ABI_SYMBOLS = [
     "pcp_ctx_create", "pcp_ctx_destroy", "pcp_last_error", "pcp_strerror", "pcp_abi_version",
     "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull",
-    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
+    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
 ]
 
 
@@ -132,6 +132,7 @@ def load_library():
     L.pcp_model_set_hull.argtypes = [vp, i32, i32]
     L.pcp_propagate.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
     L.pcp_propagate_device.argtypes = [vp, u32, C.POINTER(DeviceBatch), vp]
+    L.pcp_propagate_device_excl.argtypes = [vp, u32, C.POINTER(DeviceBatch), vp, vp, vp]
     L.pcp_propagate_device_bnb.argtypes = [vp, u32, C.POINTER(DeviceBatch), C.POINTER(Objective), vp]
     L.pcp_branch_device.argtypes = [vp, u32] + [vp] * 9
     L.pcp_branch_device_hint.argtypes = [vp, u32] + [vp] * 10
@@ -150,7 +151,7 @@ def load_library():
     L.pcp_last_plan.argtypes = [vp, C.POINTER(PcpPlan)]
     L.pcp_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
     for f in ("pcp_ctx_create", "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull", "pcp_model_set_hull",
-              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
+              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
         getattr(L, f).restype = i32
     _lib = L
     return L
@@ -326,6 +327,16 @@ class Context:
             return None if t is None else C.c_void_p(t.data_ptr())
         bt = DeviceBatch(p(lb_in), p(ub_in), p(lb_out), p(ub_out), p(active_in), p(active_out), p(status), None, None, None, 0, 0)
         self._check(self._L.pcp_propagate_device_units(self._h, n_nodes, C.byref(bt), p(unit_off), p(units), C.c_void_p(stream_ptr)))
+
+    def propagate_device_excl(self, n_nodes: int, lb_in, ub_in, lb_out, ub_out, active_out, status, excl_off, excl, stream_ptr: int = 0, dirty=None):
+        """pcp_propagate_device_excl: the batch of `propagate_device` (implicit nodes, int32 rows, an all-XNeqY model on the assignment-driven
+        kernel) where node i also carries the value exclusions excl[excl_off[i] : excl_off[i + 1]] — `excl_off` an int32 device tensor [n + 1],
+        `excl` an int32 device tensor [m, 2] of (var, value) pairs (the bytes of pcp_excl): Enumerate's x != v right branches
+        (search/branching/enumerate.rs:54-59) at any store size that fits LDS.  excl_off = None: exactly propagate_device."""
+        def p(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+        bt = DeviceBatch(p(lb_in), p(ub_in), p(lb_out), p(ub_out), None, p(active_out), p(status), None, None, p(dirty), 0, 0)
+        self._check(self._L.pcp_propagate_device_excl(self._h, n_nodes, C.byref(bt), p(excl_off), p(excl), C.c_void_p(stream_ptr)))
 
     def propagate_device_bnb(self, n_nodes: int, lb_in, ub_in, lb_out, ub_out, active_in, active_out, status, objective, stream_ptr: int = 0,
                              bits_in=None, bits_out=None):

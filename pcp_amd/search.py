@@ -203,6 +203,141 @@ def dfs(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = False, node
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Enumerate (search/branching/enumerate.rs:33-60): children ``x = v`` and ``x != v``.  ``x = v`` folds into the child's bounds like a
+# BinarySplit constraint.  ``x != v`` on an Interval removes v only at a bound (x_neq_y.rs:82-93): with v AT a bound it fires once and is then
+# entailed — folded —, with v inside the domain it removes nothing and stays in that node's cstore: the child carries the exclusion
+# (x, v) and the engine propagates it with the model (pcp_propagate_device_excl).  Exclusions are int32 [m, 2] arrays of (var, value) pairs
+# — the bytes of pcp_excl — in CSR form: node i owns excl[excl_off[i] : excl_off[i + 1]].
+# ---------------------------------------------------------------------------------------------------------------------
+def _excl_pairs(excl) -> np.ndarray:
+    if excl is None:
+        return np.zeros((0, 2), np.int32)
+    e = np.asarray(excl)
+    if e.dtype.names:  # a structured (var, value) array
+        e = np.stack([e["var"].astype(np.int64), e["value"].astype(np.int64)], axis=1) if len(e) else np.zeros((0, 2), np.int64)
+    return np.ascontiguousarray(e, np.int32).reshape(-1, 2)
+
+
+def branch_enumerate(lb: np.ndarray, ub: np.ndarray, excl_off=None, excl=None, val: str = "middle", var=None):
+    """Enumerate children of each (Unknown, propagated) row: returns (L, U, off, excl2, dirty) with 2 rows per input row, ``x = v`` first
+    (the reference's order, enumerate.rs:47-60).  The variable is FirstSmallestVar's (``var``: an index or one per row instead — the
+    reference's test_distributor distributes on a given variable); the value MiddleVal's (``val="middle"``) or MinVal's (``"min"``:
+    dom.lower(), min_val.rs:25-27).  Left child: x = v in the bounds.  Right child: the exclusion (x, v) appended behind the inherited ones,
+    or, when v is a bound of x, folded into that bound (the propagator would fire once and be entailed: the same fixpoint).  Both children
+    inherit those of the parent's exclusions whose value still lies inside their variable's domain IN THE CHILD (the others are entailed for
+    good: domains only shrink).  ``dirty``: the variable branched on — each child differs from its parent's fixpoint in it alone.
+    One departure from the letter of the reference: an interior x != v leaves an Interval as it is, so the right child is its parent again and
+    MiddleVal would choose the same v for ever (the reference's Enumerate tests use MinVal, whose value is a bound and always goes).  A value
+    the node has excluded already is therefore not chosen again: the nearest value to it that is still free is taken, the lower one first."""
+    if val not in ("middle", "min"):
+        raise ValueError(f"val must be 'middle' or 'min', not {val!r}")
+    lb = np.ascontiguousarray(lb, np.int32)
+    lb = lb.reshape(1, -1) if lb.ndim == 1 else lb
+    ub = np.ascontiguousarray(ub, np.int32).reshape(lb.shape)
+    n = lb.shape[0]
+    pairs = _excl_pairs(excl)
+    off = np.zeros(n + 1, np.int64) if excl_off is None else np.asarray(excl_off, np.int64)
+    rows = np.arange(n)
+    x = first_smallest_var(lb, ub) if var is None else np.broadcast_to(np.asarray(var, np.int64), (n,))
+    if (x < 0).any() or (lb[rows, x] >= ub[rows, x]).any():
+        raise RuntimeError("Cannot select a variable in a space where all variables are assigned.")
+    v = middle_val(lb[rows, x], ub[rows, x]) if val == "middle" else lb[rows, x].copy()
+    for i in range(n):  # a value this node has excluded already is not tried again (see the docstring)
+        taken = {int(w) for y, w in pairs[off[i]:off[i + 1]] if y == x[i]}
+        if int(v[i]) in taken:
+            lo, hi = int(lb[i, x[i]]), int(ub[i, x[i]])
+            # (outwards from v, stopping at the first free value: at most 2 * len(taken) + 2 candidates are looked at, whatever the width)
+            free = next((c for d in range(1, hi - lo + 1) for c in (int(v[i]) - d, int(v[i]) + d) if lo <= c <= hi and c not in taken), None)
+            if free is None:
+                raise RuntimeError("Cannot select a value: every value of the variable is excluded.")
+            v[i] = free
+    L = np.repeat(lb, 2, axis=0)
+    U = np.repeat(ub, 2, axis=0)
+    L[2 * rows, x] = v; U[2 * rows, x] = v  # x = v
+    at_lb, at_ub = v == lb[rows, x], v == ub[rows, x]
+    L[2 * rows + 1, x] = np.where(at_lb, v + 1, lb[rows, x])  # x != v with v at a bound
+    U[2 * rows + 1, x] = np.where(at_ub & ~at_lb, v - 1, ub[rows, x])
+    out, off2 = [], [0]
+    for i in range(n):
+        mine = pairs[off[i]:off[i + 1]]
+        for c in (2 * i, 2 * i + 1):
+            keep = mine[(mine[:, 1] >= L[c, mine[:, 0]]) & (mine[:, 1] <= U[c, mine[:, 0]])] if len(mine) else mine
+            if c & 1 and not (at_lb[i] or at_ub[i]):
+                keep = np.concatenate([keep, np.array([[x[i], v[i]]], np.int32)])
+            out.append(keep)
+            off2.append(off2[-1] + len(keep))
+    excl2 = np.ascontiguousarray(np.concatenate(out), np.int32).reshape(-1, 2) if out else np.zeros((0, 2), np.int32)
+    return L, U, np.asarray(off2, np.int32), excl2, np.repeat(x, 2).astype(np.int32)
+
+
+def dfs_enumerate(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = False, node_limit: int = 0, batch: int = 1, val: str = "middle",
+                  record: Optional[list] = None, hints: bool = True) -> SearchStats:
+    """The batched host-stepped depth-first search of ``dfs`` under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>: the top
+    ``batch`` open nodes go through ``ctx.propagate_device_excl`` in one launch, each with its own exclusions (and, with ``hints``, the
+    variable it was branched on as its dirty-variable hint).  ``record``: a list that receives, per node in the order propagated,
+    (lb_in, ub_in, exclusions [k, 2], status, lb_out, ub_out)."""
+    import torch
+    st = SearchStats()
+    dev = torch.device("cuda", ctx.device)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    V = ctx.n_vars
+    steps0 = ctx.stats_read(stream)
+    stack = [(np.ascontiguousarray(lb0, np.int32).reshape(V), np.ascontiguousarray(ub0, np.int32).reshape(V), np.zeros((0, 2), np.int32), -1)]
+    while stack:
+        take = stack[-batch:][::-1]  # top of the stack first
+        del stack[-batch:]
+        if node_limit:
+            take = take[: max(0, node_limit - st.num_nodes)]
+            if not take:
+                break
+        L = np.stack([t[0] for t in take])
+        U = np.stack([t[1] for t in take])
+        N = L.shape[0]
+        off = np.zeros(N + 1, np.int32)
+        off[1:] = np.cumsum([len(t[2]) for t in take])
+        flat = np.concatenate([t[2] for t in take]).astype(np.int32).reshape(-1, 2)
+        t_lb, t_ub = torch.from_numpy(L.copy()).to(dev), torch.from_numpy(U.copy()).to(dev)
+        t_st = torch.zeros(N, dtype=torch.uint8, device=dev)
+        t_off = torch.from_numpy(off).to(dev)
+        t_ex = torch.from_numpy(flat if len(flat) else np.zeros((1, 2), np.int32)).to(dev)  # (never a null pointer: an empty list is offsets alone)
+        t_dirty = torch.tensor([t[3] for t in take], dtype=torch.int32, device=dev) if hints else None
+        ctx.propagate_device_excl(N, t_lb, t_ub, t_lb, t_ub, None, t_st, t_off, t_ex, stream, dirty=t_dirty)
+        lb, ub, status = t_lb.cpu().numpy(), t_ub.cpu().numpy(), t_st.cpu().numpy()
+        st.launches += 1
+        if (status > UNKNOWN).any():
+            raise RuntimeError("dfs_enumerate: the engine refused a node (PCP_STATUS_HULL)")
+        if record is not None:
+            for i in range(N):
+                record.append((L[i].copy(), U[i].copy(), take[i][2].copy(), int(status[i]), lb[i].copy(), ub[i].copy()))
+        st.num_nodes += N
+        if node_limit and st.num_nodes >= node_limit:  # StopNode: the node that reaches the limit is a node, never a solution or a failure
+            status = status.copy()
+            status[-1] = UNKNOWN
+        st.num_failed_node += int((status == FALSE).sum())
+        done = False
+        for r in np.nonzero(status == TRUE)[0]:
+            st.num_solution += 1
+            st.solutions.append(lb[r].copy())
+            if not all_solutions:
+                done = True
+        if done or (node_limit and st.num_nodes >= node_limit):
+            break
+        unk = np.nonzero(status == UNKNOWN)[0]
+        if len(unk):
+            poff = np.zeros(len(unk) + 1, np.int64)
+            poff[1:] = np.cumsum([len(take[u][2]) for u in unk])
+            pex = np.concatenate([take[u][2] for u in unk]).reshape(-1, 2)
+            cl, cu, coff, cex, cd = branch_enumerate(lb[unk], ub[unk], poff, pex, val=val)
+            # push so that the first taken node's left child ends on top: iterate parents in reverse, right then left
+            for k in range(len(unk) - 1, -1, -1):
+                for c in (2 * k + 1, 2 * k):
+                    stack.append((cl[c], cu[c], cex[coff[c]:coff[c + 1]].copy(), int(cd[c])))
+    steps1 = ctx.stats_read(stream)
+    st.filter_steps = (steps1["steps"] + steps1["steps3"]) - (steps0["steps"] + steps0["steps3"])
+    return st
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Set mode (IntervalSet<i32> domains as bitsets — the reference's default FDSpace, search/mod.rs:41-43).  The same engine,
 # with the selectors the reference applies to sets: FirstSmallestVar compares CARDINALITIES (first_smallest_var.rs:30-39:
 # `v.size()`), MiddleVal is (lower + upper) / 2 (middle_val.rs:25-27), BinarySplit keeps the values <= v resp. > v.
