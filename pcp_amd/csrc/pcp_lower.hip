@@ -356,7 +356,9 @@ int32_t lower_model(const HostModel& m, Lowered& out, std::string& err) {
       bool fits = true;
       for (size_t r = 0; r < P && fits; ++r) fits = recs[r].d >= -32767 && recs[r].d <= 32767;
       if (fits) {
-        out.adjp4.resize(adj.size());
+        // (one zero entry behind the last list: the lean round 0 requests a listed variable's first entry whatever its degree — neq_fast_load —,
+        // and for a last variable without records that is the entry at adj_off[n_vars])
+        out.adjp4.assign(adj.size() + 1, 0u);
         std::vector<uint32_t> fill(adj_off.begin(), adj_off.end() - 1);
         for (size_t r = 0; r < P; ++r) {
           const uint32_t x = recs[r].xk & kSlotMask, y = recs[r].y;

@@ -9,7 +9,7 @@ namespace pcp {
 // walks the adjacency lists of the variables that are singletons in the staged domains.
 struct NeqArgs {
   ModelDev m;                   // needs adj_off, adjp, const_val, n_vars, n_slots (< 65536), n_recs, max_deg
-  const uint32_t* adjp4;        // [adj_off[n_vars]] 4-byte payloads (other | is_y << 15 | t << 16) when slots < 32768 and |offsets| < 32768, else null
+  const uint32_t* adjp4;        // [adj_off[n_vars] + 1] (a zero entry behind the last list) 4-byte payloads (other | is_y << 15 | t << 16) when slots < 32768 and |offsets| < 32768, else null
   const uint32_t* seed_always;  // [ceil(n_slots/32)] bit v = variable v has a Constant neighbour (walked in round 0 whatever its domain), or null
   uint32_t n_nodes;
   uint32_t nodes_per_block;     // B <= 16 nodes per workgroup, domains in LDS node-major

@@ -432,7 +432,13 @@ const uint32_t inert = tl.misc[N_FAIL] | tl.misc[N_OOB] | ~only;  // (`only`: th
 }
 
 // The usual outcome of the status scan, split in two so that its one memory round trip is in flight while the tile's list walk runs (the lean
-// round 0, neq_fast_walk).  Full tiles on eight wavefronts only: node wv in a wavefront's lanes 0-31, node wv + 8 in its lanes 32-63.
+// round 0, neq_fast_walk).  Full tiles only: node wv in a wavefront's lanes 0-31, node wv + nwv in its lanes 32-63 — ONE pair per wavefront, no
+// loop.  Workgroups of EIGHT OR MORE wavefronts only (neq_block 512 ... 1024; the two sizes the host picks by itself are 512 and 1024): with fewer,
+// the nodes from 2 * nwv on would never be looked at, and a tile whose first 2 * nwv nodes are all open would skip the full scan and report the
+// others True.  The lean round 0 is gated on nth >= 512 for that reason (neqfix_kernel); smaller workgroups take the general rounds and
+// neq_status_scan, which loops.  With nine to sixteen wavefronts the upper halves address "nodes" 16 .. 31: they read LDS words beyond their
+// variable's sixteen cells (the next rows; behind the last row the words that follow the cells in the workgroup's LDS) and may set bits 16 .. 31
+// of misc[N_UNK], which nobody reads — `live`, `only` and the statuses look at bits 0 .. 15 (tests/test_neq_launch_shapes.py runs every size).
 // issue: the node's first unassigned variable u among its first 32, u's cell and the first 32 entries of u's list (one load per lane);
 // finish: is one of those records open — not entailed: the intervals meet (x_neq_y.rs:71-73 via x_eq_y.rs:87-93)?  Then the node is Unknown
 // (store.rs:250-256) and its bit of misc[N_UNK] is set.  Anything else — no unassigned variable among the first 32, no open record among the
@@ -1820,7 +1826,9 @@ __global__ void __launch_bounds__(DFS ? 512 : 1024) __attribute__((amdgpu_waves_
   // ---- round 0 of a frontier tile, lean (neq_fast_walk): a full tile whose nodes have few assigned variables between them -------------------
   uint32_t fstate = 0;  // (workgroup-uniform) 0 / 1: the general rounds from round 0 / 1;  2: the rounds are done, the statuses are not;  3: both are
   if constexpr (!DFS && BT == 16 && PACKED && PAY4) {
-    if (r0_direct && nb == 16u && a.seed_always == nullptr && !(a.debug & (131072u | 1u | 4u)) && a.m.max_deg <= kFastPer * nth) {
+    // (512 threads and more: the early status scan looks at nodes wv and wv + nwv only — all sixteen from eight wavefronts on: neq_status_issue.
+    // blockDim.x is nth, read again here: compared as `nth` it cost the CELLS instantiation a VGPR)
+    if (r0_direct && nb == 16u && a.seed_always == nullptr && !(a.debug & (131072u | 1u | 4u)) && a.m.max_deg <= kFastPer * nth && blockDim.x >= 512u) {
       const uint32_t cnt = (uint32_t)__builtin_amdgcn_readfirstlane(misc[N_COUNT0]);
       if (cnt <= kFastLists && (uint32_t)__builtin_amdgcn_readfirstlane(misc[N_R0OVF]) == 0u) {
         const NeqTile<PACKED> tf{dom, chg, misc, adjo, list, win, V, Wv, B, sh, nb, tid, lane, wv, nwv, nth};

@@ -126,7 +126,8 @@ void binary_payloads() {
   CHECK(is(lo.adjp[2], 0 | Y, 3) && is(lo.adjp[3], 3, 0));            // x1: record 0 as y, record 2 against the constant's slot
   CHECK(is(lo.adjp[4], 0, 0xFFFFFFFFu));                              // x2: record 1 as x
   // other | is_y << 15 | t << 16 with t = -d on the x side, d on the y side
-  CHECK((lo.adjp4 == U32{1u | 0xFFFDu << 16, 2u | 1u << 15 | 0xFFFFu << 16, 0u | 1u << 15 | 3u << 16, 3u, 0u | 1u << 16}));
+  // ... and one zero entry behind the last list
+  CHECK((lo.adjp4 == U32{1u | 0xFFFDu << 16, 2u | 1u << 15 | 0xFFFFu << 16, 0u | 1u << 15 | 3u << 16, 3u, 0u | 1u << 16, 0u}));
   CHECK(lo.seed_always == U32{1u << 1});  // x1 is the constant's only neighbour
   // the kind travels in bits 28..30
   std::vector<pcp_prop> lt = ps;
@@ -147,6 +148,12 @@ void binary_payloads() {
   CHECK(l4.neq_model && !l4.have_adjp4 && l4.adjp4.empty() && l4.have_seed_always && is(l4.adjp[0], 1, 32768));
   wide[0].off[1] = 32767;
   CHECK(lower(model(3, wide)).have_adjp4);
+  // a last variable that is in no record (x3): its empty list starts at adj_off[n_vars], the end of the payloads.  The lean round 0 of pcp_neq.hip
+  // requests a listed variable's first entry whatever its degree (neq_fast_load): the 4-byte table keeps one zero entry there.
+  const Lowered iso = lower(model(4, {prop(PCP_NEQ, 0, 0, 1, 3), prop(PCP_NEQ, 2, 1, 0, 0)}));
+  CHECK((iso.adj_off == U32{0, 2, 3, 4, 4}) && iso.adj.size() == 4 && iso.adjp.size() == 4 && iso.neq_model && iso.have_adjp4 && !iso.have_seed_always);
+  CHECK(iso.adjp4.size() == iso.adj_off[4] + 1 && iso.adjp4.back() == 0u);
+  CHECK((iso.adjp4 == U32{1u | 0xFFFDu << 16, 2u | 1u << 15 | 0xFFFFu << 16, 0u | 1u << 15 | 3u << 16, 0u | 1u << 16, 0u}));
   std::printf("ok binary model payloads\n");
 }
 

@@ -9,10 +9,9 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from pcp_amd import model as M
 import pcp_amd.engine as E
 
-from util import assert_parity, splitmix64
+from util import assert_parity, dense_neq, tiles
 
 pytestmark = pytest.mark.gpu
 
@@ -22,54 +21,6 @@ def ctx():
     c = E.Context(0)
     yield c
     c.close()
-
-
-def dense_neq(seed, V, dom, per_pair=3, p_pair=0.9, max_off=3):
-    """x != y + c over many pairs, several offsets per pair (the shape of N-queens: a bound that loses a value often meets the next forbidden one)."""
-    rng = splitmix64(seed)
-    rows = []
-    for x in range(V):
-        for y in range(x + 1, V):
-            if rng.random() < p_pair:
-                for c in rng.choice(np.arange(-max_off, max_off + 1), size=per_pair, replace=False):
-                    rows.append((x, y, int(c)))
-    props = np.zeros(len(rows), dtype=M.PROP_DTYPE)
-    props["var"][:] = M.PCP_NOVAR
-    props["group"] = np.arange(len(rows))
-    props["kind"] = M.NEQ
-    for r, (x, y, c) in enumerate(rows):
-        props[r]["var"][0], props[r]["var"][1], props[r]["off"][1] = x, y, c
-    return props
-
-
-def tiles(seed, V, dom, n_tiles, max_assigned, p_short=0.25):
-    """16-node tiles; in each, up to `max_assigned` variables are assigned in random subsets of the tile's nodes, values near the others' bounds so
-    that filters act; some other variables are narrowed to short intervals (so that a narrowing can assign them) or to bounds next to forbidden values."""
-    rng = splitmix64(seed)
-    N = 16 * n_tiles
-    L = np.full((N, V), dom[0], np.int32)
-    U = np.full((N, V), dom[1], np.int32)
-    for t in range(n_tiles):
-        k = int(rng.integers(0, max_assigned + 1))
-        vs = rng.choice(V, size=k, replace=False)
-        for v in vs:
-            mask = rng.random(16) < (1.0 if rng.random() < 0.5 else 0.5)
-            val = int(rng.integers(dom[0], dom[1] + 1))
-            for b in np.nonzero(mask)[0]:
-                n = 16 * t + b
-                L[n, v] = U[n, v] = val if rng.random() < 0.8 else int(rng.integers(dom[0], dom[1] + 1))
-        for b in range(16):
-            n = 16 * t + b
-            for v in range(V):
-                if v in vs:
-                    continue
-                u = rng.random()
-                if u < p_short:  # a short interval: two or three values (a narrowing may assign it: the general rounds take over)
-                    a = int(rng.integers(dom[0], dom[1])); L[n, v], U[n, v] = a, min(dom[1], a + int(rng.integers(1, 3)))
-                elif u < p_short + 0.25:  # a wide interval with a bound inside the band of forbidden values
-                    a = int(rng.integers(dom[0], dom[0] + 6)); L[n, v] = a
-                    U[n, v] = int(rng.integers(max(a + 3, dom[1] - 6), dom[1] + 1))
-    return L, U
 
 
 SEEN = {"neq_lean": 0, "neq_lean_passes": 0, "neq_lean_handover": 0, "general": 0}
