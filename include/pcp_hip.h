@@ -357,6 +357,40 @@ int32_t pcp_branch_device_hint(pcp_ctx* ctx, uint32_t n_nodes, const int32_t* lb
 int32_t pcp_branch_device_set(pcp_ctx* ctx, uint32_t n_nodes, const uint64_t* bits, const int32_t* lb, const int32_t* ub, const uint64_t* active,
                               const uint8_t* status, uint64_t* child_bits, uint64_t* child_active, uint32_t* counts, void* hip_stream);
 
+/* The brancher that WRITES exclusion lists — the other half of pcp_propagate_device_excl:
+ * ≡ Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>::enter (search/branching/brancher.rs:52-71, search/branching/enumerate.rs:47-60)
+ * applied to every PCP_UNKNOWN node of a propagated batch whose node i carries the entries excl[excl_off[i] .. excl_off[i + 1]) (excl_off NULL =
+ * no node has any; excl_off[0] need not be 0: a batch may be a slice of a larger CSR):
+ *   variable = first index among the variables of minimal size > 1, sizes in 64 bits   (first_smallest_var.rs:30-39)
+ *   value    = PCP_VAL_MIDDLE: (lb + ub) / 2 truncated toward zero (middle_val.rs:25-27);  PCP_VAL_MIN: lb (min_val.rs:25-27).  A value the
+ *              node has excluded already (an entry on the chosen variable) is not chosen again — on Interval<i32> an interior x != v removes
+ *              nothing, so MiddleVal would choose it for ever —: the nearest value of [lb, ub] without an entry is taken, v - d before v + d.
+ *   children = `x = value` then `x != value` (enumerate.rs:47-60).  x = value is folded into both bounds.  x != value is folded when the value
+ *              is a bound of x (the lower bound: lb = value + 1; else the upper: ub = value - 1); otherwise the bounds stay and the entry
+ *              (x, value) is appended BEHIND the inherited ones.  Each child inherits, in the parent's order, those of the parent's entries
+ *              whose value lies inside [lb, ub] of their variable in that child's row (the others are entailed for good).  An entry with
+ *              var >= n_vars is never used as an index: it is dropped from both children.
+ *   child_lb / child_ub : [2*n_nodes][n_vars] (capacity);  child_dirty : [2*n_nodes] (capacity, nullable): the variable branched on
+ *   child_excl_off      : [2*n_nodes + 1] (capacity): child_excl_off[0 .. n_children] is the CSR of the child ROWS, child_excl_off[0] = 0
+ *   child_excl          : [child_excl_capacity].  n_child_excl <= 2 m + n_unknown, m = the number of entries of the Unknown nodes: a buffer of
+ *                         that size always suffices.
+ *   counts              : device uint32[8] out = { n_children, n_true, n_false, n_unknown, n_other, n_child_excl, error, 0 }, the first five
+ *                         as in pcp_branch_device.  error: 0 none; 1 n_child_excl > child_excl_capacity; 3 an Unknown node without a variable
+ *                         of size > 1 (the reference panics, first_smallest_var.rs:36); 4 every value of the chosen variable is excluded.
+ *                         Several errors in one batch: the largest code.  On an error the first six counts are still valid (a node with
+ *                         error 3 or 4 counts no entries), the children are unspecified and the inputs untouched: the call can be repeated.
+ * Children come in tree order, two per Unknown node, x = value first; option branch_reverse reverses the rows (and with them the CSR) as for
+ * pcp_branch_device.  The child buffers must not overlap the inputs.  Rows need no alignment and n_vars need not be a multiple of 4.
+ * Accepted: interval mode, int32 rows, implicit nodes — the contract of pcp_propagate_device_excl, except that the model may be any.  Set mode:
+ * PCP_ERR_UNSUPPORTED.  val > PCP_VAL_MIN or a null required pointer: PCP_ERR_ARG.  n_nodes == 0: PCP_OK, counts zeroed.
+ * All pointers are device pointers; everything is enqueued on hip_stream, nothing is synchronised, nothing is allocated in steady state. */
+#define PCP_VAL_MIDDLE 0u
+#define PCP_VAL_MIN 1u
+int32_t pcp_branch_device_excl(pcp_ctx* ctx, uint32_t n_nodes, const int32_t* lb, const int32_t* ub, const uint8_t* status,
+                               const uint32_t* excl_off, const pcp_excl* excl, uint32_t val, int32_t* child_lb, int32_t* child_ub,
+                               uint32_t* child_dirty, uint32_t* child_excl_off, pcp_excl* child_excl, uint32_t child_excl_capacity,
+                               uint32_t* counts, void* hip_stream);
+
 /* ---- the reference's search loop, one node per step, without the host in the loop -----------------------------------------------
  * ≡ OneSolution / AllSolution<Propagation<Brancher<FirstSmallestVar, MiddleVal, BinarySplit>>> over a VectorStack
  * (search/mod.rs:45-52, search/engine/one_solution.rs:92-105), optionally under StopNode (search/stop_node.rs:47-62): each step

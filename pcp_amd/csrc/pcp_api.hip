@@ -64,6 +64,8 @@ struct pcp_ctx : HostModel, LoweredInfo {
   uint32_t trusted_epoch = 0;   // epoch of the last packed launch without a retry launch (hull declared)
   uint64_t* d_live = nullptr; size_t cap_live = 0;       // working live mask when the caller passes none
   uint32_t* d_child_base = nullptr; size_t cap_child_base = 0;  // branching scratch
+  uint2* d_enum_pick = nullptr; size_t cap_enum_pick = 0;     // pcp_branch_device_excl: per node (variable, value)
+  uint32_t* d_enum_cnt = nullptr; size_t cap_enum_cnt = 0;    // pcp_branch_device_excl: per child slot, the entries it keeps
   uint32_t* d_team = nullptr; size_t cap_team = 0;       // team-mode scratch (u32 words)
   uint8_t* d_bnb_empty = nullptr; size_t cap_bnb_empty = 0;  // pcp_propagate_device_bnb: per node, 1 = the incumbent's fold emptied it
   // host-buffer path staging
@@ -383,7 +385,7 @@ void pcp_ctx_destroy(pcp_ctx* c) {
   if (!c) return;
   hipError_t e = hipSetDevice(c->device);
   (void)e;
-  void* ptrs[] = {c->d_fnodes, c->d_unit_root, c->d_ad_tab, c->d_ad_vars, c->d_ad_mask, c->d_brec, c->d_badj, c->d_adjp4, c->d_seed_always, c->d_mul_off, c->d_gdesc, c->d_sum_off, c->d_sum_mem, c->d_recs, c->d_adj_off, c->d_adj, c->d_const, c->d_stats, c->d_live, c->d_team, c->d_stage, c->d_rec_unit, c->d_unit_first, c->d_recs8, c->d_child_base, c->d_bnb_empty, c->d_retry, c->d_tile_ctr, c->d_dbg, c->d_wdesc, c->d_adjp};
+  void* ptrs[] = {c->d_fnodes, c->d_unit_root, c->d_ad_tab, c->d_ad_vars, c->d_ad_mask, c->d_brec, c->d_badj, c->d_adjp4, c->d_seed_always, c->d_mul_off, c->d_gdesc, c->d_sum_off, c->d_sum_mem, c->d_recs, c->d_adj_off, c->d_adj, c->d_const, c->d_stats, c->d_live, c->d_team, c->d_stage, c->d_rec_unit, c->d_unit_first, c->d_recs8, c->d_child_base, c->d_enum_pick, c->d_enum_cnt, c->d_bnb_empty, c->d_retry, c->d_tile_ctr, c->d_dbg, c->d_wdesc, c->d_adjp};
   for (void* p : ptrs)
     if (p) { e = hipFree(p); (void)e; }
   if (c->ev_start) { e = hipEventDestroy(c->ev_start); (void)e; }
@@ -1240,6 +1242,31 @@ int32_t pcp_branch_device_set(pcp_ctx* c, uint32_t n_nodes, const uint64_t* bits
   if (n_nodes == 0) { HIP_TRY(c, hipMemsetAsync(counts, 0, 20, stream)); return PCP_OK; }
   HIP_TRY(c, launch_set_branch(n_nodes, c->n_vars, c->set_words, c->hull_lo, active ? words : 0u, bits, lb, ub, active, status, child_bits, child_active,
                                c->d_child_base, counts, (uint32_t)c->opt_branch_reverse, stream));
+  return PCP_OK;
+}
+
+// Enumerate over nodes with exclusion lists (pcp_enum.hip): the status scan of the other branchers, then select / offsets / write.
+int32_t pcp_branch_device_excl(pcp_ctx* c, uint32_t n_nodes, const int32_t* lb, const int32_t* ub, const uint8_t* status, const uint32_t* excl_off,
+                               const pcp_excl* excl, uint32_t val, int32_t* child_lb, int32_t* child_ub, uint32_t* child_dirty, uint32_t* child_excl_off,
+                               pcp_excl* child_excl, uint32_t child_excl_capacity, uint32_t* counts, void* hip_stream) {
+  if (!c) return PCP_ERR_ARG;
+  if (!counts) return fail(c, PCP_ERR_ARG, "pcp_branch_device_excl: counts must not be null");
+  if (c->set_words) return fail(c, PCP_ERR_UNSUPPORTED, "pcp_branch_device_excl: interval mode only (set mode needs no exclusions: x != v is an exact set operation on `bits`)");
+  if (val > PCP_VAL_MIN) return fail(c, PCP_ERR_ARG, "pcp_branch_device_excl: val must be PCP_VAL_MIDDLE or PCP_VAL_MIN");
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (n_nodes == 0) { HIP_TRY(c, hipMemsetAsync(counts, 0, 8 * sizeof(uint32_t), stream)); return PCP_OK; }
+  if (!lb || !ub || !status || !child_lb || !child_ub || !child_excl_off) return fail(c, PCP_ERR_ARG, "pcp_branch_device_excl: null buffer");
+  if (excl_off && !excl) return fail(c, PCP_ERR_ARG, "pcp_branch_device_excl: excl must not be null when excl_off is given");
+  if (!child_excl && child_excl_capacity) return fail(c, PCP_ERR_ARG, "pcp_branch_device_excl: child_excl must not be null when child_excl_capacity > 0");
+  if (n_nodes > 0x7FFFFFFFu) return fail(c, PCP_ERR_ARG, "pcp_branch_device_excl: at most 2^31 - 1 nodes per call");
+  PCP_TRY(ensure(c, c->d_child_base, c->cap_child_base, n_nodes));
+  PCP_TRY(ensure(c, c->d_enum_pick, c->cap_enum_pick, n_nodes));
+  PCP_TRY(ensure(c, c->d_enum_cnt, c->cap_enum_cnt, 2 * (size_t)n_nodes));
+  HIP_TRY(c, hipMemsetAsync(counts, 0, 8 * sizeof(uint32_t), stream));
+  HIP_TRY(c, launch_branch_scan(n_nodes, status, c->d_child_base, counts, stream));
+  HIP_TRY(c, launch_enum_branch(n_nodes, c->n_vars, lb, ub, c->d_child_base, excl_off, excl, val, c->d_enum_pick, c->d_enum_cnt, child_lb, child_ub,
+                                child_dirty, child_excl_off, child_excl, child_excl_capacity, counts, (uint32_t)c->opt_branch_reverse, stream));
   return PCP_OK;
 }
 

@@ -152,6 +152,14 @@ hipError_t launch_branch(uint32_t n_nodes, uint32_t n_vars, uint32_t words, cons
                          const uint8_t* status, int32_t* child_lb, int32_t* child_ub, uint64_t* child_active, uint32_t* child_dirty, uint32_t* child_base,
                          uint32_t* counts, uint32_t reverse, hipStream_t stream);
 
+// Enumerate on the device (pcp_enum.hip, pcp_branch_device_excl), behind launch_branch_scan: per Unknown node the variable, the value and the
+// number of entries each child keeps (pick [n_nodes], cnt [2 n_nodes]: context scratch), the offsets of the child rows' lists, then the rows
+// and the kept entries.  counts[5] = entries written, counts[6] = error (the children are then left unwritten).
+hipError_t launch_enum_branch(uint32_t n_nodes, uint32_t n_vars, const int32_t* lb, const int32_t* ub, const uint32_t* child_base, const uint32_t* excl_off,
+                              const pcp_excl* excl, uint32_t val, uint2* pick, uint32_t* cnt, int32_t* child_lb, int32_t* child_ub, uint32_t* child_dirty,
+                              uint32_t* child_excl_off, pcp_excl* child_excl, uint32_t child_excl_capacity, uint32_t* counts, uint32_t reverse,
+                              hipStream_t stream);
+
 // Branch and bound (pcp_bnb.hip, pcp_propagate_device_bnb): the incumbent folded into each node's objective domain before the fixpoint
 // (empty[i] = 1: the fold would empty node i, its row is left as it was), then the empty nodes forced to PCP_FALSE and the best PCP_TRUE node
 // of the batch taken as the new incumbent if it beats it.  Interval mode: lb / ub rows; set mode: bits rows (lb / ub ignored by the fold).

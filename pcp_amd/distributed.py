@@ -243,6 +243,8 @@ def balance_stacks(stack, dist, info: Optional[dict] = None, sizes: Optional[Lis
     stack an eighth into the buffer for that) and shifts only when that hole is used up.  Returns rows sent (+) or received (-);
     ``info`` accumulates moved_rows / moved_bytes / record_bytes."""
     import torch
+    if getattr(stack, "brancher", "split") == "enumerate":
+        raise ValueError("balance_stacks: a search in Enumerate mode cannot be balanced (its nodes own exclusion lists, which are not moved between ranks)")
     world, rank = dist.get_world_size(), dist.get_rank()
     dev = stack.lb.device
     segmented = hasattr(stack, "segs")
@@ -355,6 +357,8 @@ def parallel_search_device(search, lb0, ub0, dist, all_solutions: bool = True, n
     Returns the global (nodes, solutions, failures, filter steps, moved records)."""
     import time
     import torch
+    if getattr(search, "brancher", "split") == "enumerate":
+        raise ValueError("parallel_search_device: a search in Enumerate mode runs on one GPU (exclusion lists are not moved between ranks)")
     dev = search.lb.device
     world = dist.get_world_size()
     seed_frontier(search, lb0, ub0, dist, min(seed_nodes, search.batch * world) if world > 1 else 0, all_solutions=all_solutions, base=base, node_limit=node_limit)

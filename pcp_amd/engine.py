@@ -25,7 +25,7 @@ ERRORS = {-1: "PCP_ERR_ARG", -2: "PCP_ERR_CONTRACT", -3: "PCP_ERR_HIP", -4: "PCP
 ABI_SYMBOLS = [
     "pcp_ctx_create", "pcp_ctx_destroy", "pcp_last_error", "pcp_strerror", "pcp_abi_version",
     "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull",
-    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
+    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
 ]
 
 
@@ -58,6 +58,8 @@ class Objective(C.Structure):
 
 pcp_objective = Objective
 MINIMIZE, MAXIMIZE = 0, 1
+VAL_MIDDLE, VAL_MIN = 0, 1  # PCP_VAL_MIDDLE / PCP_VAL_MIN
+VAL_MODES = {"middle": VAL_MIDDLE, "min": VAL_MIN}
 BOUND_MAX = 0x1FFFFFFF  # PCP_BOUND_MAX
 OBJ_MODES = {"min": MINIMIZE, "max": MAXIMIZE}
 
@@ -140,6 +142,7 @@ def load_library():
     L.pcp_unpack_rows.argtypes = [vp, u32, vp, vp, vp, vp]
     L.pcp_branch_device_cells.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
     L.pcp_branch_device_set.argtypes = [vp, u32] + [vp] * 9
+    L.pcp_branch_device_excl.argtypes = [vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp]
     L.pcp_dfs_device.argtypes = [vp, C.POINTER(DfsState), u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_set.argtypes = [vp, C.POINTER(ForestState), u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_split_set.argtypes = [vp, C.POINTER(ForestState), u32, vp, vp, vp]
@@ -392,6 +395,20 @@ class Context:
             return None if t is None else C.c_void_p(t.data_ptr())
         self._check(self._L.pcp_branch_device_set(self._h, n_nodes, p(bits), p(lb), p(ub), p(active), p(status), p(child_bits), p(child_active),
                                                   p(counts), C.c_void_p(stream_ptr)))
+
+    def branch_device_excl(self, n_nodes: int, lb, ub, status, excl_off, excl, val, child_lb, child_ub, child_excl_off, child_excl, child_excl_capacity: int,
+                           counts, stream_ptr: int = 0, child_dirty=None):
+        """pcp_branch_device_excl: Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate> over a propagated batch whose node i carries the
+        exclusions excl[excl_off[i] : excl_off[i + 1]] (int32 device tensors as in propagate_device_excl; excl_off = None: no node has any).
+        val: "middle" / "min" (or VAL_MIDDLE / VAL_MIN).  The children's rows go to child_lb / child_ub ([2 n] rows capacity), their lists to
+        child_excl ([child_excl_capacity, 2]) with the CSR offsets of the child rows in child_excl_off ([2 n + 1], from 0); counts: int32[8] =
+        n_children, n_true, n_false, n_unknown, n_other, n_child_excl, error, 0.  Nothing is synchronised; an error is reported in counts[6]
+        only (search.branch_enumerate is the same brancher on the host and raises instead)."""
+        def p(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self._L.pcp_branch_device_excl(self._h, n_nodes, p(lb), p(ub), p(status), p(excl_off), p(excl), int(VAL_MODES.get(val, val)), p(child_lb),
+                                                   p(child_ub), p(child_dirty), p(child_excl_off), p(child_excl), int(child_excl_capacity), p(counts),
+                                                   C.c_void_p(stream_ptr)))
 
     def dfs_device(self, lb0, ub0, n_steps: int, capacity: int = 4096, stop_on_solution: bool = True, node_limit: int = 0, chunk: int = 256):
         """pcp_dfs_device: the reference's one-node-per-step DFS entirely on the device.  Runs until the stack is empty, a stop

@@ -8,6 +8,9 @@ is exactly the reference's left-first DFS (search/engine/one_solution.rs:46-51, 
 With ``objective=(var, "min" | "max")`` the round propagates through `pcp_propagate_device_bnb` instead (branch and bound,
 search/branch_and_bound.rs:64-84): the incumbent stays on the device, is folded into every node of the batch before the fixpoint
 and replaced by the batch's best Satisfiable node after it; it comes back in the same copy as the counts.
+With ``brancher="enumerate"`` the round is `pcp_propagate_device_excl` + `pcp_branch_device_excl` (Brancher<FirstSmallestVar, MiddleVal | MinVal,
+Enumerate>, search/branching/enumerate.rs:33-60): every open node owns a list of value exclusions, the lists live in a device arena next to the
+rows and are written by the brancher — rows, hints and lists stay on the GPU from the root to the leaves.
 PyTorch provides the device buffers; every kernel is this repository's.
 """
 from __future__ import annotations
@@ -41,11 +44,27 @@ class DeviceSearch:
     the children straight above them, in reverse order, as a new segment: nothing is copied or reordered.  The popped
     parents leave a hole below the new segment; it is reclaimed when that segment is used up (LIFO)."""
 
-    def __init__(self, ctx, batch: int = 1024, capacity: int = 0, device=None, implicit: bool = False, hints=None, cells: bool = False, objective=None):
+    def __init__(self, ctx, batch: int = 1024, capacity: int = 0, device=None, implicit: bool = False, hints=None, cells: bool = False, objective=None,
+                 brancher: str = "split", val: str = "middle", excl_capacity: int = 0):
         import torch
         self.torch = torch
         self.ctx = ctx
         self.batch = int(batch)
+        # brancher="enumerate": children x = v / x != v instead of BinarySplit's x <= v / x > v; val: MiddleVal or MinVal (Enumerate only)
+        if brancher not in ("split", "enumerate"):
+            raise ValueError(f"brancher must be 'split' or 'enumerate', not {brancher!r}")
+        self.brancher, self.val = brancher, val
+        if brancher == "enumerate":
+            if val not in ("middle", "min"):
+                raise ValueError(f"val must be 'middle' or 'min', not {val!r}")
+            if cells:
+                raise ValueError("Enumerate runs on int32 rows: cells=True is refused")
+            if objective is not None:
+                raise ValueError("Enumerate takes no objective (branch and bound runs under BinarySplit)")
+            if getattr(ctx, "set_words", 0):
+                raise ValueError("Enumerate is for interval mode (in set mode x != v is an exact set operation: no exclusion lists)")
+            if not implicit and ctx.words:
+                raise ValueError("Enumerate needs implicit nodes (pcp_propagate_device_excl takes no `active` rows)")
         self.dev = device if device is not None else torch.device("cuda", ctx.device)
         V, W = ctx.n_vars, max(ctx.words, 1)
         self.V, self.W = V, W
@@ -94,6 +113,20 @@ class DeviceSearch:
             self.best_bits = torch.zeros((V, self.set_words), dtype=i64, device=self.dev) if self.set_words else None
         self.segs: List[List[int]] = []  # [start, length], bottom to top
         self.stats = DeviceSearchStats()
+        if brancher == "enumerate":
+            # The exclusion arena, managed like the row buffer.  Segment i of `segs` (rows [s, s + l)) owns esegs[i] = [o, e0, n, m]: its l + 1
+            # offsets eoff[o : o + l + 1] (relative to e0, the first one 0) and the contiguous run of entries ex[e0 : e0 + n]; m bounds the
+            # entries of any ONE of its nodes (a child has at most one more than its parent).  A round writes the children's entries above the
+            # top segment's, their offsets above its offsets; the popped parents leave holes that are reclaimed with the rows (LIFO).
+            # A round over n nodes that own k entries writes at most 2 k + n entries (include/pcp_hip.h): the default holds as many bytes as the rows.
+            self.ecap = int(excl_capacity) if excl_capacity else self.cap * max(V, 16)
+            self.ex = torch.empty((self.ecap + 1, 2), dtype=i32, device=self.dev)  # (+ 1: no slice of it is empty)
+            self.eoff = torch.zeros(2 * self.cap + 4, dtype=i32, device=self.dev)  # (a segment's o is at most twice its s)
+            self.esegs: List[List[int]] = []
+            # counts[8] and, behind them, the entries the top segment keeps after the pop: the round's one copy to the host reads both
+            self.round_buf = torch.zeros(9, dtype=i32, device=self.dev)
+            self.counts = self.round_buf[:8]
+            self.arena_events = {"merge": 0, "compact": 0, "fewer": 0}
 
     # ---- the stack as the drivers see it ------------------------------------------------------------------------------
     @property
@@ -121,6 +154,29 @@ class DeviceSearch:
             rows = rows + (self.dirty,)
         return rows if self.bits is None else rows + (self.bits,)
 
+    @staticmethod
+    def _move(t, dst: int, src: int, k: int):
+        """t[dst : dst + k] = t[src : src + k] for dst <= src (the ranges may overlap)."""
+        if k and dst != src:
+            t[dst:dst + k] = t[src:src + k].clone() if src < dst + k else t[src:src + k]
+
+    def _arena_take(self, n: int, exact: bool = False) -> int:
+        """Enumerate: how many of the top segment's n top nodes the arena can branch in one round (their children's entries go above the
+        segment's); 0 when not even one fits.  From what the host knows — the segment's entries and a bound on one node's —, or, ``exact``,
+        from the segment's offsets (a copy from the device: only a round that the bound turns away pays it; it also renews the bound)."""
+        o, e0, cnt, m = self.esegs[-1]
+        room = self.ecap - (e0 + cnt)
+        if 2 * min(cnt, n * m) + n <= room:
+            return n
+        if not exact:
+            return min(n, room // (2 * m + 1))
+        l = self.segs[-1][1]
+        off = self.eoff[o:o + l + 1].cpu().numpy().astype(np.int64)
+        self.esegs[-1][3] = int(np.diff(off).max())
+        while n and 2 * int(off[l] - off[l - n]) + n > room:
+            n -= 1
+        return n
+
     def _merge_top(self, want: int):
         """Close the holes under the top segments until the top segment holds `want` nodes (or is the only one): only
         the small segments on top are moved, never the bulk of the stack."""
@@ -132,18 +188,38 @@ class DeviceSearch:
                 for t in self._rows():
                     t[dest:dest + l2] = t[s2:s2 + l2].clone() if s2 < dest + l2 else t[s2:s2 + l2]
             self.segs[-1][1] = l1 + l2
+            if self.brancher == "enumerate":
+                # the moved rows' entries go behind the lower segment's, their offsets (relative to the run's start) grow by its count
+                o2, e2, n2, m2 = self.esegs.pop()
+                o1, e1, n1, m1 = self.esegs[-1]
+                self._move(self.ex, e1 + n1, e2, n2)
+                self.eoff[o1 + l1 + 1:o1 + l1 + 1 + l2] = self.eoff[o2 + 1:o2 + l2 + 1] + n1
+                self.esegs[-1] = [o1, e1, n1 + n2, max(m1, m2)]
+                self.arena_events["merge"] += 1
 
     def compact(self):
         """Make the open nodes one segment starting at row 0 (order kept)."""
         if len(self.segs) == 1 and self.segs[0][0] == 0:
             return
         pos = 0
-        for s, l in self.segs:
+        epos, emax = 0, 0
+        for i, (s, l) in enumerate(self.segs):
             if l and s != pos:
                 for t in self._rows():
                     t[pos:pos + l] = t[s:s + l].clone() if s < pos + l else t[s:s + l]
+            if self.brancher == "enumerate":
+                o, e0, cnt, m = self.esegs[i]
+                self._move(self.ex, epos, e0, cnt)
+                if i == 0:
+                    self._move(self.eoff, 0, o, l + 1)
+                else:
+                    self.eoff[pos + 1:pos + l + 1] = self.eoff[o + 1:o + l + 1] + epos
+                epos, emax = epos + cnt, max(emax, m)
             pos += l
         self.segs = [[0, pos]] if pos else []
+        if self.brancher == "enumerate":
+            self.esegs = [[0, 0, epos, emax]] if pos else []
+            self.arena_events["compact"] += 1
 
     def reset(self, lb0, ub0, base: int = 0):
         """Start a new search: the stack holds the root (set mode: the variables as IntervalSet::new(lb0, ub0), value v = bit
@@ -167,6 +243,9 @@ class DeviceSearch:
             self.dirty[0] = -1  # the root is propagated from scratch
         self.segs = [[0, 1]]
         self.stats = DeviceSearchStats()
+        if self.brancher == "enumerate":
+            self.eoff[0:2] = 0  # the root has no exclusions
+            self.esegs = [[0, 0, 0, 0]]
         if self.objective is not None:
             from .engine import no_incumbent
             self.best.fill_(no_incumbent(self.objective[1]))
@@ -183,6 +262,7 @@ class DeviceSearch:
         With an objective, ``all_solutions`` is ignored: branch and bound runs to the end of the search."""
         torch, ctx, st = self.torch, self.ctx, self.stats
         bnb = self.objective is not None
+        enum = self.brancher == "enumerate"
         if bnb:
             all_solutions = True
             obj = {"var": self.objective[0], "mode": self.objective[1], "best": self.best, "best_lb": self.best_lb, "best_ub": self.best_ub,
@@ -200,7 +280,7 @@ class DeviceSearch:
             top = start + length
             # the children (at most 2n rows) go right above the popped parents: when the buffer is nearly full, first
             # squeeze out the holes, then take fewer nodes (a deeper, narrower dive) instead of overflowing
-            if self.cap - top < 2 * min(batch, length):
+            if self.cap - top < 2 * min(batch, length) or (enum and self._arena_take(min(batch, length)) < min(batch, length)):
                 self.compact()
                 start, length = self.segs[-1]
                 top = start + length
@@ -208,6 +288,16 @@ class DeviceSearch:
             if room < 2:
                 raise RuntimeError(f"open-node stack full ({self.size} of {self.cap}); raise `capacity`")
             n = min(batch, length, room // 2)
+            if enum:
+                # the same for the exclusion arena: what the children's lists may need has to fit above the top segment's entries
+                fit = self._arena_take(n)
+                if fit < n:
+                    fit = self._arena_take(n, exact=True)
+                if fit < 1:
+                    raise RuntimeError(f"exclusion arena full ({self.esegs[-1][1] + self.esegs[-1][2]} of {self.ecap} entries in use); raise `excl_capacity`")
+                if fit < n:
+                    self.arena_events["fewer"] += 1
+                n = fit
             for cap_nodes in (node_limit, stop_at):
                 if cap_nodes:
                     n = min(n, cap_nodes - st.num_nodes)
@@ -217,7 +307,15 @@ class DeviceSearch:
             lb, ub = self.lb[lo:top], (None if self.cells else self.ub[lo:top])
             act = None if self.act is None else self.act[lo:top]
             status = self.status[:n]
-            if self.cells:
+            if enum:
+                o, e0, cnt, emax = self.esegs[-1]
+                k = lo - start  # the batch's first row within its segment
+                poff, pex, etop, oc = self.eoff[o + k:o + length + 1], self.ex[e0:], e0 + cnt, o + length + 1
+                ctx.propagate_device_excl(n, lb, ub, lb, ub, None, status, poff, pex, stream, dirty=None if self.dirty is None else self.dirty[lo:top])
+                ctx.branch_device_excl(n, lb, ub, status, poff, pex, self.val, self.lb[top:], self.ub[top:], self.eoff[oc:], self.ex[etop:], self.ecap - etop,
+                                       self.counts, stream, child_dirty=None if self.dirty is None else self.dirty[top:])
+                self.round_buf[8:9].copy_(self.eoff[o + k:o + k + 1])  # where the popped nodes' entries begin: what the segment keeps
+            elif self.cells:
                 dirty = None if self.dirty is None else self.dirty[lo:top]
                 ctx.propagate_device(n, lb, None, lb, None, None, None, status, stream, dirty=dirty, cells=True)
                 ctx.branch_device_cells(n, lb, status, self.lb[top:], self.counts, stream, child_dirty=None if self.dirty is None else self.dirty[top:])
@@ -247,6 +345,11 @@ class DeviceSearch:
                     self._improved_seen = improved
                     st.best = best
                     st.incumbents.append(best)
+            elif enum:
+                n_children, n_true, n_false, _, n_other, n_child_excl, error, _, kept = (int(x) for x in self.round_buf.cpu().tolist())  # the round's only D2H sync
+                if error and not n_other:
+                    raise RuntimeError({1: "the exclusion arena was sized too small for this round", 3: "Cannot select a variable in a space where all variables are assigned.",
+                                        4: "Cannot select a value: every value of the variable is excluded."}.get(error, f"pcp_branch_device_excl: error {error}"))
             else:
                 n_children, n_true, n_false, _, n_other = (int(x) for x in self.counts.cpu().tolist())  # the round's only D2H sync
             if n_other:
@@ -274,13 +377,19 @@ class DeviceSearch:
                     st.solutions.append(r)
             # pop the parents; the children, already in left-first order (branch_reverse), become the new top segment
             self.segs[-1][1] = length - n
+            if enum:
+                self.esegs[-1][2] = kept
             if self.segs[-1][1] == 0:
                 self.segs.pop()
+                if enum:
+                    self.esegs.pop()
             if n_true and not all_solutions:
                 done = True
                 break
             if n_children:
                 self.segs.append([top, n_children])
+                if enum:
+                    self.esegs.append([oc, etop, n_child_excl, emax + 1])
             st.max_open = max(st.max_open, self.size)
         ctx.set_option("branch_reverse", 0)
         if bnb and st.best is not None:
