@@ -164,6 +164,15 @@ def _np_ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _ptr(t):  # the device pointer of a torch tensor (None: a null pointer)
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _batch(cells=False, **tensors) -> DeviceBatch:
+    """pcp_device_batch over torch tensors, by field name (a field not named: a null pointer)."""
+    return DeviceBatch(cell_format=1 if cells else 0, **{k: _ptr(t) for k, t in tensors.items()})
+
+
 class Context:
     """One pcp_ctx == one constraint store (CStore) on one GPU."""
 
@@ -316,30 +325,24 @@ class Context:
         [n,V,set_words] (lb_in/ub_in ignored); dirty int32 [n]: per node the one variable in which it differs from a fixpoint of this
         model, -1 / >= n_vars = none (pcp_device_batch.dirty_var).  cells=True (pcp_device_batch.cell_format PCP_CELLS_PACKED16): lb_in / lb_out
         are int32 [n,V] tensors of packed CELLS (pack_rows), ub_* ignored."""
-        def p(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-        bt = DeviceBatch(p(lb_in), p(ub_in), p(lb_out), p(ub_out), p(active_in), p(active_out), p(status), p(bits_in), p(bits_out), p(dirty),
-                         1 if cells else 0, 0)
+        bt = _batch(lb_in=lb_in, ub_in=ub_in, lb_out=lb_out, ub_out=ub_out, active_in=active_in, active_out=active_out, status=status,
+                    bits_in=bits_in, bits_out=bits_out, dirty_var=dirty, cells=cells)
         self._check(self._L.pcp_propagate_device(self._h, n_nodes, C.byref(bt), C.c_void_p(stream_ptr)))
 
     def propagate_device_units(self, n_nodes: int, lb_in, ub_in, lb_out, ub_out, active_in, active_out, status, unit_off, units, stream_ptr: int = 0):
         """pcp_propagate_device_units (ABI v8): the batch of `propagate_device` where node i also carries its own unary propagators
         units[unit_off[i] : unit_off[i + 1]] — `unit_off` an int32 device tensor [n + 1], `units` a uint8 device tensor holding the pcp_prop
         records (model.PROP_DTYPE bytes).  Enumerate's x != v children (search/branching/enumerate.rs:48-59) in one launch."""
-        def p(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-        bt = DeviceBatch(p(lb_in), p(ub_in), p(lb_out), p(ub_out), p(active_in), p(active_out), p(status), None, None, None, 0, 0)
-        self._check(self._L.pcp_propagate_device_units(self._h, n_nodes, C.byref(bt), p(unit_off), p(units), C.c_void_p(stream_ptr)))
+        bt = _batch(lb_in=lb_in, ub_in=ub_in, lb_out=lb_out, ub_out=ub_out, active_in=active_in, active_out=active_out, status=status)
+        self._check(self._L.pcp_propagate_device_units(self._h, n_nodes, C.byref(bt), _ptr(unit_off), _ptr(units), C.c_void_p(stream_ptr)))
 
     def propagate_device_excl(self, n_nodes: int, lb_in, ub_in, lb_out, ub_out, active_out, status, excl_off, excl, stream_ptr: int = 0, dirty=None):
         """pcp_propagate_device_excl: the batch of `propagate_device` (implicit nodes, int32 rows, an all-XNeqY model on the assignment-driven
         kernel) where node i also carries the value exclusions excl[excl_off[i] : excl_off[i + 1]] — `excl_off` an int32 device tensor [n + 1],
         `excl` an int32 device tensor [m, 2] of (var, value) pairs (the bytes of pcp_excl): Enumerate's x != v right branches
         (search/branching/enumerate.rs:54-59) at any store size that fits LDS.  excl_off = None: exactly propagate_device."""
-        def p(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-        bt = DeviceBatch(p(lb_in), p(ub_in), p(lb_out), p(ub_out), None, p(active_out), p(status), None, None, p(dirty), 0, 0)
-        self._check(self._L.pcp_propagate_device_excl(self._h, n_nodes, C.byref(bt), p(excl_off), p(excl), C.c_void_p(stream_ptr)))
+        bt = _batch(lb_in=lb_in, ub_in=ub_in, lb_out=lb_out, ub_out=ub_out, active_out=active_out, status=status, dirty_var=dirty)
+        self._check(self._L.pcp_propagate_device_excl(self._h, n_nodes, C.byref(bt), _ptr(excl_off), _ptr(excl), C.c_void_p(stream_ptr)))
 
     def propagate_device_bnb(self, n_nodes: int, lb_in, ub_in, lb_out, ub_out, active_in, active_out, status, objective, stream_ptr: int = 0,
                              bits_in=None, bits_out=None):
@@ -348,15 +351,14 @@ class Context:
         ("min" / "max" or MINIMIZE / MAXIMIZE), `best` (int32 [1] tensor) and optionally `best_lb`, `best_ub`, `best_bits`, `improved`
         (int32 tensors [n_vars], int64 [n_vars, set_words], int32 [1]); or an Objective.  No hint (dirty) is taken: nodes are propagated
         from scratch."""
-        def p(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
         if isinstance(objective, Objective):
             ob = objective
         else:
             g = objective.get
-            ob = Objective(int(g("var")), int(OBJ_MODES.get(g("mode"), g("mode"))), p(g("best")), p(g("best_lb")), p(g("best_ub")), p(g("best_bits")),
-                           p(g("improved")), 0)
-        bt = DeviceBatch(p(lb_in), p(ub_in), p(lb_out), p(ub_out), p(active_in), p(active_out), p(status), p(bits_in), p(bits_out), None, 0, 0)
+            ob = Objective(int(g("var")), int(OBJ_MODES.get(g("mode"), g("mode"))), _ptr(g("best")), _ptr(g("best_lb")), _ptr(g("best_ub")), _ptr(g("best_bits")),
+                           _ptr(g("improved")), 0)
+        bt = _batch(lb_in=lb_in, ub_in=ub_in, lb_out=lb_out, ub_out=ub_out, active_in=active_in, active_out=active_out, status=status,
+                    bits_in=bits_in, bits_out=bits_out)
         self._check(self._L.pcp_propagate_device_bnb(self._h, n_nodes, C.byref(bt), C.byref(ob), C.c_void_p(stream_ptr)))
 
     def pack_rows(self, lb, ub, cells=None, stream_ptr: int = 0):
@@ -377,24 +379,18 @@ class Context:
 
     def branch_device_cells(self, n_nodes: int, cells, status, child_cells, counts, stream_ptr: int = 0, child_dirty=None):
         """pcp_branch_device_cells: branch_device over rows of packed cells (implicit nodes)."""
-        def p(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self._L.pcp_branch_device_cells(self._h, n_nodes, p(cells), p(status), p(child_cells), p(child_dirty), p(counts), C.c_void_p(stream_ptr)))
+        self._check(self._L.pcp_branch_device_cells(self._h, n_nodes, _ptr(cells), _ptr(status), _ptr(child_cells), _ptr(child_dirty), _ptr(counts), C.c_void_p(stream_ptr)))
 
     def branch_device(self, n_nodes: int, lb, ub, active, status, child_lb, child_ub, child_active, counts, stream_ptr: int = 0, child_dirty=None):
         """pcp_branch_device(_hint) on torch tensors of this context's device (counts: int32[5]; child_dirty: int32 [2 n] capacity, receives
         the variable each child was branched on); nothing is synchronised."""
-        def p(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self._L.pcp_branch_device_hint(self._h, n_nodes, p(lb), p(ub), p(active), p(status), p(child_lb), p(child_ub), p(child_active),
-                                                   p(child_dirty), p(counts), C.c_void_p(stream_ptr)))
+        self._check(self._L.pcp_branch_device_hint(self._h, n_nodes, _ptr(lb), _ptr(ub), _ptr(active), _ptr(status), _ptr(child_lb), _ptr(child_ub), _ptr(child_active),
+                                                   _ptr(child_dirty), _ptr(counts), C.c_void_p(stream_ptr)))
 
     def branch_device_set(self, n_nodes: int, bits, lb, ub, active, status, child_bits, child_active, counts, stream_ptr: int = 0):
         """pcp_branch_device_set (set mode) on torch tensors of this context's device (counts: int32[5])."""
-        def p(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self._L.pcp_branch_device_set(self._h, n_nodes, p(bits), p(lb), p(ub), p(active), p(status), p(child_bits), p(child_active),
-                                                  p(counts), C.c_void_p(stream_ptr)))
+        self._check(self._L.pcp_branch_device_set(self._h, n_nodes, _ptr(bits), _ptr(lb), _ptr(ub), _ptr(active), _ptr(status), _ptr(child_bits), _ptr(child_active),
+                                                  _ptr(counts), C.c_void_p(stream_ptr)))
 
     def branch_device_excl(self, n_nodes: int, lb, ub, status, excl_off, excl, val, child_lb, child_ub, child_excl_off, child_excl, child_excl_capacity: int,
                            counts, stream_ptr: int = 0, child_dirty=None):
@@ -404,10 +400,8 @@ class Context:
         child_excl ([child_excl_capacity, 2]) with the CSR offsets of the child rows in child_excl_off ([2 n + 1], from 0); counts: int32[8] =
         n_children, n_true, n_false, n_unknown, n_other, n_child_excl, error, 0.  Nothing is synchronised; an error is reported in counts[6]
         only (search.branch_enumerate is the same brancher on the host and raises instead)."""
-        def p(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self._L.pcp_branch_device_excl(self._h, n_nodes, p(lb), p(ub), p(status), p(excl_off), p(excl), int(VAL_MODES.get(val, val)), p(child_lb),
-                                                   p(child_ub), p(child_dirty), p(child_excl_off), p(child_excl), int(child_excl_capacity), p(counts),
+        self._check(self._L.pcp_branch_device_excl(self._h, n_nodes, _ptr(lb), _ptr(ub), _ptr(status), _ptr(excl_off), _ptr(excl), int(VAL_MODES.get(val, val)), _ptr(child_lb),
+                                                   _ptr(child_ub), _ptr(child_dirty), _ptr(child_excl_off), _ptr(child_excl), int(child_excl_capacity), _ptr(counts),
                                                    C.c_void_p(stream_ptr)))
 
     def dfs_device(self, lb0, ub0, n_steps: int, capacity: int = 4096, stop_on_solution: bool = True, node_limit: int = 0, chunk: int = 256):

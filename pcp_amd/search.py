@@ -28,7 +28,8 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
-from .model import FALSE, TRUE, UNKNOWN
+from .engine import full_active
+from .model import FALSE, TRUE, UNKNOWN, interval_bits
 
 
 def first_smallest_var(lb: np.ndarray, ub: np.ndarray) -> np.ndarray:
@@ -139,20 +140,13 @@ def bfs_frontier(ctx, lb0: np.ndarray, ub0: np.ndarray, n_open: int, max_rounds:
     return L[ok][:n_open], U[ok][:n_open], (None if A is None else A[ok][:n_open]), st
 
 
-def dfs(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = False, node_limit: int = 0, batch: int = 1, objective=None) -> SearchStats:
-    """Depth-first search with a LIFO stack of open nodes (gcollections::VectorStack in the reference).  With
-    ``batch=1`` the node order is exactly the reference's left-first DFS (one_solution.rs:46-51, 92-105); with
-    ``batch>1`` the top ``batch`` open nodes are propagated in one launch (batched subtree propagation).
-    ``objective=(var, "min" | "max")``: branch and bound on that variable (module docstring); the search runs to the end
-    whatever ``all_solutions`` says, and ``best`` / ``best_solution`` / ``incumbents`` of the result report it."""
-    from .engine import full_active
+def _search(kind, root, all_solutions: bool, node_limit: int, batch: int, obj=None) -> SearchStats:
+    """The depth-first loop of dfs / dfs_set / dfs_enumerate over a LIFO stack of open nodes.  ``kind`` says what a node is:
+    ``kind.propagate(st, take, obj)`` stacks the popped nodes, propagates them (counting launches and filter steps in ``st``) and returns
+    (lb rows, status, the propagated batch); ``kind.branch(batch, unk)`` returns the children of its rows ``unk``: two nodes per row, left then right."""
     st = SearchStats()
-    obj = _objective(objective)
-    if obj is not None:
-        all_solutions = True
-    stack: List[Tuple[np.ndarray, np.ndarray, np.ndarray]] = [
-        (np.ascontiguousarray(lb0, np.int32), np.ascontiguousarray(ub0, np.int32), full_active(1, ctx.n_units)[0])
-    ]
+    all_solutions = all_solutions or obj is not None
+    stack = [root]
     while stack:
         take = stack[-batch:][::-1]  # top of the stack first
         del stack[-batch:]
@@ -160,46 +154,62 @@ def dfs(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = False, node
             take = take[: max(0, node_limit - st.num_nodes)]
             if not take:
                 break
-        L = np.stack([t[0] for t in take])
-        U = np.stack([t[1] for t in take])
-        A = np.stack([t[2] for t in take])
-        if obj is not None and st.best is not None:  # the bound propagator, folded (an emptied node fails without a launch)
+        lb, status, done_batch = kind.propagate(st, take, obj)
+        st.num_nodes += len(take)
+        at_limit = bool(node_limit and st.num_nodes >= node_limit)
+        if at_limit:
+            # StopNode hands EndOfSearch to the monitor for the node that reaches the limit (stop_node.rs:57-62 under Monitor,
+            # stop_node.rs:90-97): it is counted as a node, never as a solution or a failure
+            status[-1] = UNKNOWN
+        st.num_failed_node += int((status == FALSE).sum())
+        true = np.nonzero(status == TRUE)[0]
+        st.num_solution += len(true)
+        st.solutions += [lb[r].copy() for r in true]
+        if obj is not None:
+            _improve(st, obj, lb, status)
+        if (len(true) and not all_solutions) or at_limit:
+            break
+        unk = np.nonzero(status == UNKNOWN)[0]
+        if len(unk):
+            # push so that the first taken node's left child ends on top: the parents in reverse, right then left
+            stack += kind.branch(done_batch, unk)[::-1]
+    return st
+
+
+class _IntervalRows:
+    """A node is (lb, ub, active).  The incumbent is folded into the bounds; a node with lb > ub is failed without a launch."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def propagate(self, st, take, obj):
+        L, U, A = (np.stack(c) for c in zip(*take))
+        if obj is not None and st.best is not None:  # the bound propagator, folded
             if obj[1]:
                 U[:, obj[0]] = np.minimum(U[:, obj[0]], st.best - 1)
             else:
                 L[:, obj[0]] = np.maximum(L[:, obj[0]], st.best + 1)
         ok = (L <= U).all(axis=1)
-        lb, ub, act, status = L.copy(), U.copy(), A.copy(), np.zeros(L.shape[0], np.uint8)
+        status = np.zeros(L.shape[0], np.uint8)
         if ok.any():
-            plb, pub, pact, pst, s = ctx.propagate(L[ok], U[ok], A[ok])
-            lb[ok], ub[ok], act[ok], status[ok] = plb, pub, pact, pst
+            L[ok], U[ok], A[ok], status[ok], s = self.ctx.propagate(L[ok], U[ok], A[ok])
             st.launches += 1
             st.filter_steps += s["steps"] + s["steps3"]
-        st.num_nodes += L.shape[0]
-        if node_limit and st.num_nodes >= node_limit:
-            # StopNode hands EndOfSearch to the monitor for the node that reaches the limit (stop_node.rs:57-62 under Monitor,
-            # stop_node.rs:90-97): it is counted as a node, never as a solution or a failure
-            status = status.copy()
-            status[-1] = UNKNOWN
-        st.num_failed_node += int((status == FALSE).sum())
-        done = False
-        for r in np.nonzero(status == TRUE)[0]:
-            st.num_solution += 1
-            st.solutions.append(lb[r].copy())
-            if not all_solutions:
-                done = True
-        if obj is not None:
-            _improve(st, obj, lb, status)
-        if done or (node_limit and st.num_nodes >= node_limit):
-            break
-        unk = np.nonzero(status == UNKNOWN)[0]
-        if len(unk):
-            cl, cu, ca = branch(lb[unk], ub[unk], act[unk])
-            # push so that the first taken node's left child ends on top: iterate parents in reverse, right then left
-            for k in range(len(unk) - 1, -1, -1):
-                stack.append((cl[2 * k + 1], cu[2 * k + 1], ca[2 * k + 1]))
-                stack.append((cl[2 * k], cu[2 * k], ca[2 * k]))
-    return st
+        return L, status, (L, U, A)
+
+    def branch(self, done_batch, unk):
+        return list(zip(*branch(*(a[unk] for a in done_batch))))
+
+
+def dfs(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = False, node_limit: int = 0, batch: int = 1, objective=None) -> SearchStats:
+    """Depth-first search with a LIFO stack of open nodes (gcollections::VectorStack in the reference).  With
+    ``batch=1`` the node order is exactly the reference's left-first DFS (one_solution.rs:46-51, 92-105); with
+    ``batch>1`` the top ``batch`` open nodes are propagated in one launch (batched subtree propagation).
+    ``objective=(var, "min" | "max")``: branch and bound on that variable (module docstring); the search runs to the end
+    whatever ``all_solutions`` says, and ``best`` / ``best_solution`` / ``incumbents`` of the result report it."""
+    obj = _objective(objective)
+    root = (np.ascontiguousarray(lb0, np.int32), np.ascontiguousarray(ub0, np.int32), full_active(1, ctx.n_units)[0])
+    return _search(_IntervalRows(ctx), root, all_solutions, node_limit, batch, obj)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -270,28 +280,19 @@ def branch_enumerate(lb: np.ndarray, ub: np.ndarray, excl_off=None, excl=None, v
     return L, U, np.asarray(off2, np.int32), excl2, np.repeat(x, 2).astype(np.int32)
 
 
-def dfs_enumerate(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = False, node_limit: int = 0, batch: int = 1, val: str = "middle",
-                  record: Optional[list] = None, hints: bool = True) -> SearchStats:
-    """The batched host-stepped depth-first search of ``dfs`` under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>: the top
-    ``batch`` open nodes go through ``ctx.propagate_device_excl`` in one launch, each with its own exclusions (and, with ``hints``, the
-    variable it was branched on as its dirty-variable hint).  ``record``: a list that receives, per node in the order propagated,
-    (lb_in, ub_in, exclusions [k, 2], status, lb_out, ub_out)."""
-    import torch
-    st = SearchStats()
-    dev = torch.device("cuda", ctx.device)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    V = ctx.n_vars
-    steps0 = ctx.stats_read(stream)
-    stack = [(np.ascontiguousarray(lb0, np.int32).reshape(V), np.ascontiguousarray(ub0, np.int32).reshape(V), np.zeros((0, 2), np.int32), -1)]
-    while stack:
-        take = stack[-batch:][::-1]  # top of the stack first
-        del stack[-batch:]
-        if node_limit:
-            take = take[: max(0, node_limit - st.num_nodes)]
-            if not take:
-                break
-        L = np.stack([t[0] for t in take])
-        U = np.stack([t[1] for t in take])
+class _ExclRows:
+    """A node is (lb, ub, exclusions [k, 2], dirty variable), propagated on torch tensors through ``ctx.propagate_device_excl``.  There is no
+    objective and no emptiness check: the children of branch_enumerate are never empty."""
+
+    def __init__(self, ctx, val, record, hints):
+        import torch
+        self.torch, self.ctx, self.val, self.record, self.hints = torch, ctx, val, record, hints
+        self.dev = torch.device("cuda", ctx.device)
+        self.stream = torch.cuda.current_stream(self.dev).cuda_stream
+
+    def propagate(self, st, take, obj):
+        torch, dev = self.torch, self.dev
+        L, U = (np.stack([t[i] for t in take]) for i in (0, 1))
         N = L.shape[0]
         off = np.zeros(N + 1, np.int32)
         off[1:] = np.cumsum([len(t[2]) for t in take])
@@ -300,40 +301,37 @@ def dfs_enumerate(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = F
         t_st = torch.zeros(N, dtype=torch.uint8, device=dev)
         t_off = torch.from_numpy(off).to(dev)
         t_ex = torch.from_numpy(flat if len(flat) else np.zeros((1, 2), np.int32)).to(dev)  # (never a null pointer: an empty list is offsets alone)
-        t_dirty = torch.tensor([t[3] for t in take], dtype=torch.int32, device=dev) if hints else None
-        ctx.propagate_device_excl(N, t_lb, t_ub, t_lb, t_ub, None, t_st, t_off, t_ex, stream, dirty=t_dirty)
+        t_dirty = torch.tensor([t[3] for t in take], dtype=torch.int32, device=dev) if self.hints else None
+        self.ctx.propagate_device_excl(N, t_lb, t_ub, t_lb, t_ub, None, t_st, t_off, t_ex, self.stream, dirty=t_dirty)
         lb, ub, status = t_lb.cpu().numpy(), t_ub.cpu().numpy(), t_st.cpu().numpy()
         st.launches += 1
         if (status > UNKNOWN).any():
             raise RuntimeError("dfs_enumerate: the engine refused a node (PCP_STATUS_HULL)")
-        if record is not None:
-            for i in range(N):
-                record.append((L[i].copy(), U[i].copy(), take[i][2].copy(), int(status[i]), lb[i].copy(), ub[i].copy()))
-        st.num_nodes += N
-        if node_limit and st.num_nodes >= node_limit:  # StopNode: the node that reaches the limit is a node, never a solution or a failure
-            status = status.copy()
-            status[-1] = UNKNOWN
-        st.num_failed_node += int((status == FALSE).sum())
-        done = False
-        for r in np.nonzero(status == TRUE)[0]:
-            st.num_solution += 1
-            st.solutions.append(lb[r].copy())
-            if not all_solutions:
-                done = True
-        if done or (node_limit and st.num_nodes >= node_limit):
-            break
-        unk = np.nonzero(status == UNKNOWN)[0]
-        if len(unk):
-            poff = np.zeros(len(unk) + 1, np.int64)
-            poff[1:] = np.cumsum([len(take[u][2]) for u in unk])
-            pex = np.concatenate([take[u][2] for u in unk]).reshape(-1, 2)
-            cl, cu, coff, cex, cd = branch_enumerate(lb[unk], ub[unk], poff, pex, val=val)
-            # push so that the first taken node's left child ends on top: iterate parents in reverse, right then left
-            for k in range(len(unk) - 1, -1, -1):
-                for c in (2 * k + 1, 2 * k):
-                    stack.append((cl[c], cu[c], cex[coff[c]:coff[c + 1]].copy(), int(cd[c])))
-    steps1 = ctx.stats_read(stream)
-    st.filter_steps = (steps1["steps"] + steps1["steps3"]) - (steps0["steps"] + steps0["steps3"])
+        if self.record is not None:
+            self.record += [(L[i].copy(), U[i].copy(), take[i][2].copy(), int(status[i]), lb[i].copy(), ub[i].copy()) for i in range(N)]
+        return lb, status, (lb, ub, take)
+
+    def branch(self, done_batch, unk):
+        lb, ub, take = done_batch
+        poff = np.zeros(len(unk) + 1, np.int64)
+        poff[1:] = np.cumsum([len(take[u][2]) for u in unk])
+        pex = np.concatenate([take[u][2] for u in unk]).reshape(-1, 2)
+        cl, cu, coff, cex, cd = branch_enumerate(lb[unk], ub[unk], poff, pex, val=self.val)
+        return [(cl[c], cu[c], cex[coff[c]:coff[c + 1]].copy(), int(cd[c])) for c in range(len(cl))]
+
+
+def dfs_enumerate(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = False, node_limit: int = 0, batch: int = 1, val: str = "middle",
+                  record: Optional[list] = None, hints: bool = True) -> SearchStats:
+    """The batched host-stepped depth-first search of ``dfs`` under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>: the top
+    ``batch`` open nodes go through ``ctx.propagate_device_excl`` in one launch, each with its own exclusions (and, with ``hints``, the
+    variable it was branched on as its dirty-variable hint).  ``record``: a list that receives, per node in the order propagated,
+    (lb_in, ub_in, exclusions [k, 2], status, lb_out, ub_out)."""
+    kind, V = _ExclRows(ctx, val, record, hints), ctx.n_vars
+    steps0 = ctx.stats_read(kind.stream)
+    root = (np.ascontiguousarray(lb0, np.int32).reshape(V), np.ascontiguousarray(ub0, np.int32).reshape(V), np.zeros((0, 2), np.int32), -1)
+    st = _search(kind, root, all_solutions, node_limit, batch)
+    steps1 = ctx.stats_read(kind.stream)
+    st.filter_steps = (steps1["steps"] + steps1["steps3"]) - (steps0["steps"] + steps0["steps3"])  # over the whole call, not per launch
     return st
 
 
@@ -373,64 +371,42 @@ def branch_set(bits: np.ndarray, lb: np.ndarray, ub: np.ndarray, base: int, acti
     return B, A
 
 
+class _Sets:
+    """A node is (bits, active or None).  The incumbent is folded through interval_bits; a node with an emptied set is failed without a launch."""
+
+    def __init__(self, ctx, base, implicit):
+        self.ctx, self.base, self.implicit = ctx, base, implicit
+
+    def propagate(self, st, take, obj):
+        sw, base = self.ctx.set_words, self.base
+        Bt = np.stack([t[0] for t in take])
+        A = None if self.implicit else np.stack([t[1] for t in take])
+        if obj is not None and st.best is not None:
+            top = base + 64 * sw - 1
+            keep = interval_bits(base, min(st.best - 1, top), sw, base) if obj[1] else interval_bits(max(st.best + 1, base), top, sw, base)
+            Bt[:, obj[0]] &= keep
+        ok = Bt.any(axis=2).all(axis=1)
+        status = np.zeros(Bt.shape[0], np.uint8)
+        lb = np.ones(Bt.shape[:2], np.int32); ub = np.zeros(Bt.shape[:2], np.int32)
+        if ok.any():
+            lb[ok], ub[ok], Bt[ok], pact, status[ok], s = self.ctx.propagate_set(Bt[ok], None if A is None else A[ok])
+            if A is not None:
+                A[ok] = pact
+            st.launches += 1
+            st.filter_steps += s["steps"] + s["steps3"]
+        return lb, status, (Bt, lb, ub, A)
+
+    def branch(self, done_batch, unk):
+        Bt, lb, ub, A = done_batch
+        cb, ca = branch_set(Bt[unk], lb[unk], ub[unk], self.base, None if A is None else A[unk])
+        return [(cb[c], None if ca is None else ca[c]) for c in range(len(cb))]
+
+
 def dfs_set(ctx, lb0: np.ndarray, ub0: np.ndarray, base: int, all_solutions: bool = False, node_limit: int = 0, batch: int = 1,
             implicit: bool = True, objective=None) -> SearchStats:
     """Depth-first search over set-mode nodes (FDSpace): the variables are allocated as IntervalSet::new(lb0, ub0)
     (example/src/nqueens.rs:32-35); with batch = 1 the node order is the reference's left-first DFS.  ``objective``: as in dfs;
     the bound clears the objective's values >= best (min) or <= best (max) from its set."""
-    from .engine import full_active
-    from .model import interval_bits
-    st = SearchStats()
     obj = _objective(objective)
-    if obj is not None:
-        all_solutions = True
-    sw = ctx.set_words
-    root = interval_bits(np.asarray(lb0), np.asarray(ub0), sw, base)
-    stack: List[Tuple[np.ndarray, Optional[np.ndarray]]] = [(root, None if implicit else full_active(1, ctx.n_units)[0])]
-    while stack:
-        take = stack[-batch:][::-1]
-        del stack[-batch:]
-        if node_limit:
-            take = take[: max(0, node_limit - st.num_nodes)]
-            if not take:
-                break
-        Bt = np.stack([t[0] for t in take])
-        A = None if implicit else np.stack([t[1] for t in take])
-        if obj is not None and st.best is not None:
-            top = base + 64 * sw - 1
-            keep = interval_bits(base, min(st.best - 1, top), sw, base) if obj[1] else interval_bits(max(st.best + 1, base), top, sw, base)
-            Bt[:, obj[0]] &= keep
-        ok = Bt.any(axis=2).all(axis=1)  # a folded branch can empty a set: that child is failed without a launch
-        status = np.zeros(Bt.shape[0], np.uint8)
-        lb = np.ones(Bt.shape[:2], np.int32); ub = np.zeros(Bt.shape[:2], np.int32)
-        act = None if A is None else A.copy()
-        if ok.any():
-            plb, pub, pbits, pact, pst, s = ctx.propagate_set(Bt[ok], None if A is None else A[ok])
-            Bt[ok], lb[ok], ub[ok], status[ok] = pbits, plb, pub, pst
-            if act is not None:
-                act[ok] = pact
-            st.launches += 1
-            st.filter_steps += s["steps"] + s["steps3"]
-        st.num_nodes += Bt.shape[0]
-        at_limit = bool(node_limit and st.num_nodes >= node_limit)
-        if at_limit:  # the node that reaches the limit is a node, never a solution or a failure (StopNode under Monitor, stop_node.rs:57-62, 90-97)
-            status = status.copy()
-            status[-1] = UNKNOWN
-        st.num_failed_node += int((status == FALSE).sum())
-        done = False
-        for r in np.nonzero(status == TRUE)[0]:
-            st.num_solution += 1
-            st.solutions.append(lb[r].copy())
-            if not all_solutions:
-                done = True
-        if obj is not None:
-            _improve(st, obj, lb, status)
-        if done or at_limit:
-            break
-        unk = np.nonzero(status == UNKNOWN)[0]
-        if len(unk):
-            cb, ca = branch_set(Bt[unk], lb[unk], ub[unk], base, None if act is None else act[unk])
-            for k in range(len(unk) - 1, -1, -1):
-                stack.append((cb[2 * k + 1], None if ca is None else ca[2 * k + 1]))
-                stack.append((cb[2 * k], None if ca is None else ca[2 * k]))
-    return st
+    root = (interval_bits(np.asarray(lb0), np.asarray(ub0), ctx.set_words, base), None if implicit else full_active(1, ctx.n_units)[0])
+    return _search(_Sets(ctx, base, implicit), root, all_solutions, node_limit, batch, obj)

@@ -38,6 +38,146 @@ class DeviceSearchStats:
     incumbents: List[int] = field(default_factory=list)  # every improvement, one per round at most
 
 
+def _cut(t, lo: int, hi=None):
+    """t[lo:hi] of a buffer the search may not keep (None)."""
+    return None if t is None else t[lo:hi]
+
+
+class _Int32Rows:
+    """The node kind of a DeviceSearch: the buffers only it needs, the two engine calls of a round, and what happens to its side structures when
+    segments are merged, the stack is compacted, a batch is popped and children are pushed (nothing, but for Enumerate).
+    This one: int32 rows (lb, ub), with or without `active` rows, hints and an objective."""
+    n_counts = 5  # round_buf: the brancher's counts[5], then (branch and bound) the incumbent and the improvement count
+
+    def __init__(self, s):
+        self.s = s
+
+    def _nothing(self, *args): pass
+    # the hooks of a kind with side structures: a new search starts; the top segment (l2 rows) was moved behind the one below (l1 rows); the
+    # segments are about to become one; the round's buffer has arrived; its parents were popped (emptied: the top segment's last); its children pushed
+    reset = merge = compact = check = pop = push = _nothing
+
+    def take(self, n: int, final: bool = True) -> int: return n  # how many of the top n nodes a round may take (final: it is about to be launched)
+
+    def unpacked(self, rows, stream):
+        return rows
+
+    def launch(self, n, lo, top, status, stream):
+        s, ctx = self.s, self.s.ctx
+        lb, ub, act = s.lb[lo:top], s.ub[lo:top], _cut(s.act, lo, top)
+        if s.objective is None:
+            ctx.propagate_device(n, lb, ub, lb, ub, act, act, status, stream, dirty=_cut(s.dirty, lo, top))
+        else:
+            ctx.propagate_device_bnb(n, lb, ub, lb, ub, act, act, status, s._obj, stream)
+        ctx.branch_device(n, lb, ub, act, status, s.lb[top:], s.ub[top:], _cut(s.act, top), s.counts, stream, child_dirty=_cut(s.dirty, top))
+
+
+class _Cells(_Int32Rows):
+    """Rows of packed cells: `lb` holds the cells, there is no `ub`."""
+
+    def unpacked(self, rows, stream):
+        return self.s.ctx.unpack_rows(rows.contiguous(), stream_ptr=stream)[0]
+
+    def launch(self, n, lo, top, status, stream):
+        s, ctx = self.s, self.s.ctx
+        ctx.propagate_device(n, s.lb[lo:top], None, s.lb[lo:top], None, None, None, status, stream, dirty=_cut(s.dirty, lo, top), cells=True)
+        ctx.branch_device_cells(n, s.lb[lo:top], status, s.lb[top:], s.counts, stream, child_dirty=_cut(s.dirty, top))
+
+
+class _Sets(_Int32Rows):
+    """Sets (`bits`), with or without an objective; lb / ub receive the sets' bounds."""
+
+    def launch(self, n, lo, top, status, stream):
+        s, ctx = self.s, self.s.ctx
+        lb, ub, act, bits = s.lb[lo:top], s.ub[lo:top], _cut(s.act, lo, top), s.bits[lo:top]
+        if s.objective is None:
+            ctx.propagate_device(n, None, None, lb, ub, act, act, status, stream, bits_in=bits, bits_out=bits)
+        else:
+            ctx.propagate_device_bnb(n, None, None, lb, ub, act, act, status, s._obj, stream, bits_in=bits, bits_out=bits)
+        ctx.branch_device_set(n, bits, lb, ub, act, status, s.bits[top:], _cut(s.act, top), s.counts, stream)
+
+
+class _Enumerate(_Int32Rows):
+    """Rows with exclusion lists.  The exclusion arena is managed like the row buffer.  Segment i of `segs` (rows [s, s + l)) owns
+    esegs[i] = [o, e0, n, m]: its l + 1 offsets eoff[o : o + l + 1] (relative to e0, the first one 0) and the contiguous run of entries
+    ex[e0 : e0 + n]; m bounds the entries of any ONE of its nodes (a child has at most one more than its parent).  A round writes the children's
+    entries above the top segment's, their offsets above its offsets; the popped parents leave holes that are reclaimed with the rows (LIFO)."""
+    n_counts = 8  # round_buf: the brancher's counts[8] and, behind them, the entries the top segment keeps after the pop
+
+    def __init__(self, s, excl_capacity: int):
+        self.s, torch = s, s.torch
+        # A round over n nodes that own k entries writes at most 2 k + n entries (include/pcp_hip.h): the default holds as many bytes as the rows.
+        s.ecap = int(excl_capacity) if excl_capacity else s.cap * max(s.V, 16)
+        s.ex = torch.empty((s.ecap + 1, 2), dtype=torch.int32, device=s.dev)  # (+ 1: no slice of it is empty)
+        s.eoff = torch.zeros(2 * s.cap + 4, dtype=torch.int32, device=s.dev)  # (a segment's o is at most twice its s)
+        s.esegs = []
+        s.arena_events = {"merge": 0, "compact": 0, "fewer": 0}
+
+    def reset(self):
+        self.s.eoff[0:2] = 0  # the root has no exclusions
+        self.s.esegs = [[0, 0, 0, 0]]
+
+    def merge(self, l1, l2):
+        """The moved rows' entries go behind the lower segment's, their offsets (relative to the run's start) grow by its count."""
+        s = self.s
+        o2, e2, n2, m2 = s.esegs.pop()
+        o1, e1, n1, m1 = s.esegs[-1]
+        s._move(s.ex, e1 + n1, e2, n2)
+        s.eoff[o1 + l1 + 1:o1 + l1 + 1 + l2] = s.eoff[o2 + 1:o2 + l2 + 1] + n1
+        s.esegs[-1] = [o1, e1, n1 + n2, max(m1, m2)]
+        s.arena_events["merge"] += 1
+
+    def compact(self, segs):
+        s = self.s
+        pos = epos = emax = 0
+        for i, ((_, l), (o, e0, cnt, m)) in enumerate(zip(segs, s.esegs)):
+            s._move(s.ex, epos, e0, cnt)
+            if i == 0:
+                s._move(s.eoff, 0, o, l + 1)
+            else:
+                s.eoff[pos + 1:pos + l + 1] = s.eoff[o + 1:o + l + 1] + epos
+            pos, epos, emax = pos + l, epos + cnt, max(emax, m)
+        s.esegs = [[0, 0, epos, emax]] if pos else []
+        s.arena_events["compact"] += 1
+
+    def take(self, n, final=True):
+        """As for the rows: what the children's lists may need has to fit above the top segment's entries."""
+        s = self.s
+        fit = s._arena_take(n)
+        if not final or fit == n:
+            return fit
+        fit = s._arena_take(n, exact=True)
+        if fit < 1:
+            raise RuntimeError(f"exclusion arena full ({s.esegs[-1][1] + s.esegs[-1][2]} of {s.ecap} entries in use); raise `excl_capacity`")
+        s.arena_events["fewer"] += fit < n
+        return fit
+
+    def launch(self, n, lo, top, status, stream):
+        s, ctx = self.s, self.s.ctx
+        (start, length), (o, e0, cnt, emax) = s.segs[-1], s.esegs[-1]
+        k = lo - start  # the batch's first row within its segment
+        lb, ub, poff, pex, etop, oc = s.lb[lo:top], s.ub[lo:top], s.eoff[o + k:o + length + 1], s.ex[e0:], e0 + cnt, o + length + 1
+        ctx.propagate_device_excl(n, lb, ub, lb, ub, None, status, poff, pex, stream, dirty=_cut(s.dirty, lo, top))
+        ctx.branch_device_excl(n, lb, ub, status, poff, pex, s.val, s.lb[top:], s.ub[top:], s.eoff[oc:], s.ex[etop:], s.ecap - etop, s.counts, stream,
+                               child_dirty=_cut(s.dirty, top))
+        s.round_buf[8:9].copy_(s.eoff[o + k:o + k + 1])  # where the popped nodes' entries begin: what the segment keeps
+        self.children = [oc, etop, emax + 1]  # the children's segment, should there be any
+
+    def check(self, buf):
+        if buf[6]:
+            raise RuntimeError({1: "the exclusion arena was sized too small for this round", 3: "Cannot select a variable in a space where all variables are assigned.",
+                                4: "Cannot select a value: every value of the variable is excluded."}.get(buf[6], f"pcp_branch_device_excl: error {buf[6]}"))
+
+    def pop(self, buf, emptied):
+        self.s.esegs[-1][2] = buf[8]
+        if emptied:
+            self.s.esegs.pop()
+
+    def push(self, buf):
+        oc, etop, m = self.children
+        self.s.esegs.append([oc, etop, buf[5], m])
+
+
 class DeviceSearch:
     """The open nodes live in one device buffer of ``capacity`` rows as a list of SEGMENTS (start, length), the last
     one on top.  A round propagates the top ``n`` rows of the last segment in place and lets `pcp_branch_device` write
@@ -47,9 +187,7 @@ class DeviceSearch:
     def __init__(self, ctx, batch: int = 1024, capacity: int = 0, device=None, implicit: bool = False, hints=None, cells: bool = False, objective=None,
                  brancher: str = "split", val: str = "middle", excl_capacity: int = 0):
         import torch
-        self.torch = torch
-        self.ctx = ctx
-        self.batch = int(batch)
+        self.torch, self.ctx, self.batch = torch, ctx, int(batch)
         # brancher="enumerate": children x = v / x != v instead of BinarySplit's x <= v / x > v; val: MiddleVal or MinVal (Enumerate only)
         if brancher not in ("split", "enumerate"):
             raise ValueError(f"brancher must be 'split' or 'enumerate', not {brancher!r}")
@@ -66,8 +204,7 @@ class DeviceSearch:
             if not implicit and ctx.words:
                 raise ValueError("Enumerate needs implicit nodes (pcp_propagate_device_excl takes no `active` rows)")
         self.dev = device if device is not None else torch.device("cuda", ctx.device)
-        V, W = ctx.n_vars, max(ctx.words, 1)
-        self.V, self.W = V, W
+        self.V, self.W = V, W = ctx.n_vars, max(ctx.words, 1)
         self.cap = int(capacity) if capacity else 8 * self.batch + 64
         i32, i64, u8 = torch.int32, torch.int64, torch.uint8
         # cells: the open nodes are rows of packed cells (pcp_device_batch.cell_format PCP_CELLS_PACKED16; all-XNeqY models with a declared hull
@@ -103,30 +240,19 @@ class DeviceSearch:
         want = bool(getattr(ctx, "supports_hints", False)) and self.implicit and not self.set_words and self.objective is None  # (bnb: no hints)
         self.dirty = torch.full((self.cap,), -1, dtype=i32, device=self.dev) if (want if hints is None else (hints and want)) else None
         self.status = torch.zeros(self.batch, dtype=u8, device=self.dev)
-        self.counts = torch.zeros(5, dtype=i32, device=self.dev)
-        if self.objective is not None:
-            # counts, the incumbent and the improvement count side by side: the round's one copy to the host reads all three
-            self.round_buf = torch.zeros(7, dtype=i32, device=self.dev)
-            self.counts, self.best, self.improved = self.round_buf[:5], self.round_buf[5:6], self.round_buf[6:7]
-            self.best_lb = torch.zeros(V, dtype=i32, device=self.dev)
-            self.best_ub = torch.zeros(V, dtype=i32, device=self.dev)
-            self.best_bits = torch.zeros((V, self.set_words), dtype=i64, device=self.dev) if self.set_words else None
         self.segs: List[List[int]] = []  # [start, length], bottom to top
         self.stats = DeviceSearchStats()
-        if brancher == "enumerate":
-            # The exclusion arena, managed like the row buffer.  Segment i of `segs` (rows [s, s + l)) owns esegs[i] = [o, e0, n, m]: its l + 1
-            # offsets eoff[o : o + l + 1] (relative to e0, the first one 0) and the contiguous run of entries ex[e0 : e0 + n]; m bounds the
-            # entries of any ONE of its nodes (a child has at most one more than its parent).  A round writes the children's entries above the
-            # top segment's, their offsets above its offsets; the popped parents leave holes that are reclaimed with the rows (LIFO).
-            # A round over n nodes that own k entries writes at most 2 k + n entries (include/pcp_hip.h): the default holds as many bytes as the rows.
-            self.ecap = int(excl_capacity) if excl_capacity else self.cap * max(V, 16)
-            self.ex = torch.empty((self.ecap + 1, 2), dtype=i32, device=self.dev)  # (+ 1: no slice of it is empty)
-            self.eoff = torch.zeros(2 * self.cap + 4, dtype=i32, device=self.dev)  # (a segment's o is at most twice its s)
-            self.esegs: List[List[int]] = []
-            # counts[8] and, behind them, the entries the top segment keeps after the pop: the round's one copy to the host reads both
-            self.round_buf = torch.zeros(9, dtype=i32, device=self.dev)
-            self.counts = self.round_buf[:8]
-            self.arena_events = {"merge": 0, "compact": 0, "fewer": 0}
+        self.kind = (_Enumerate(self, excl_capacity) if brancher == "enumerate" else _Cells(self) if self.cells else _Sets(self) if self.set_words
+                     else _Int32Rows(self))
+        # what a round brings back, side by side: its one copy to the host reads all of it
+        self.round_buf = torch.zeros(9, dtype=i32, device=self.dev)
+        self.counts = self.round_buf[:self.kind.n_counts]
+        if self.objective is not None:
+            self.best, self.improved = self.round_buf[5:6], self.round_buf[6:7]
+            self.best_lb, self.best_ub = torch.zeros(V, dtype=i32, device=self.dev), torch.zeros(V, dtype=i32, device=self.dev)
+            self.best_bits = torch.zeros((V, self.set_words), dtype=i64, device=self.dev) if self.set_words else None
+            self._obj = {"var": self.objective[0], "mode": self.objective[1], "best": self.best, "best_lb": self.best_lb, "best_ub": self.best_ub,
+                         "best_bits": self.best_bits, "improved": self.improved}
 
     # ---- the stack as the drivers see it ------------------------------------------------------------------------------
     @property
@@ -138,21 +264,13 @@ class DeviceSearch:
         """Rows [0, n) are the open nodes (used by balance_stacks after it has moved rows around a compacted stack)."""
         self.segs = [[0, int(n)]] if n > 0 else []
 
-    def _top_row(self) -> int:
-        return self.segs[-1][0] + self.segs[-1][1] if self.segs else 0
-
     def _stream(self) -> int:
         """The HIP stream the engine is launched on (torch's current stream of this GPU; 0 off the GPU: the CPU tests drive
         this class with an oracle-backed stand-in context)."""
         return self.torch.cuda.current_stream(self.dev).cuda_stream if self.dev.type == "cuda" else 0
 
     def _rows(self):
-        rows = (self.lb, self.ub) if self.act is None else (self.lb, self.ub, self.act)
-        if self.cells:
-            rows = (self.lb,)
-        if self.dirty is not None:
-            rows = rows + (self.dirty,)
-        return rows if self.bits is None else rows + (self.bits,)
+        return tuple(t for t in (self.lb, self.ub, self.act, self.dirty, self.bits) if t is not None)
 
     @staticmethod
     def _move(t, dst: int, src: int, k: int):
@@ -183,71 +301,45 @@ class DeviceSearch:
         while len(self.segs) > 1 and self.segs[-1][1] < want:
             s2, l2 = self.segs.pop()
             s1, l1 = self.segs[-1]
-            dest = s1 + l1
-            if l2 and s2 != dest:
-                for t in self._rows():
-                    t[dest:dest + l2] = t[s2:s2 + l2].clone() if s2 < dest + l2 else t[s2:s2 + l2]
+            for t in self._rows():
+                self._move(t, s1 + l1, s2, l2)
             self.segs[-1][1] = l1 + l2
-            if self.brancher == "enumerate":
-                # the moved rows' entries go behind the lower segment's, their offsets (relative to the run's start) grow by its count
-                o2, e2, n2, m2 = self.esegs.pop()
-                o1, e1, n1, m1 = self.esegs[-1]
-                self._move(self.ex, e1 + n1, e2, n2)
-                self.eoff[o1 + l1 + 1:o1 + l1 + 1 + l2] = self.eoff[o2 + 1:o2 + l2 + 1] + n1
-                self.esegs[-1] = [o1, e1, n1 + n2, max(m1, m2)]
-                self.arena_events["merge"] += 1
+            self.kind.merge(l1, l2)
 
     def compact(self):
         """Make the open nodes one segment starting at row 0 (order kept)."""
         if len(self.segs) == 1 and self.segs[0][0] == 0:
             return
+        self.kind.compact(self.segs)
         pos = 0
-        epos, emax = 0, 0
-        for i, (s, l) in enumerate(self.segs):
-            if l and s != pos:
-                for t in self._rows():
-                    t[pos:pos + l] = t[s:s + l].clone() if s < pos + l else t[s:s + l]
-            if self.brancher == "enumerate":
-                o, e0, cnt, m = self.esegs[i]
-                self._move(self.ex, epos, e0, cnt)
-                if i == 0:
-                    self._move(self.eoff, 0, o, l + 1)
-                else:
-                    self.eoff[pos + 1:pos + l + 1] = self.eoff[o + 1:o + l + 1] + epos
-                epos, emax = epos + cnt, max(emax, m)
+        for s, l in self.segs:
+            for t in self._rows():
+                self._move(t, pos, s, l)
             pos += l
         self.segs = [[0, pos]] if pos else []
-        if self.brancher == "enumerate":
-            self.esegs = [[0, 0, epos, emax]] if pos else []
-            self.arena_events["compact"] += 1
 
     def reset(self, lb0, ub0, base: int = 0):
         """Start a new search: the stack holds the root (set mode: the variables as IntervalSet::new(lb0, ub0), value v = bit
         v - base, base = the hull's lower bound declared on the context)."""
         torch, ctx = self.torch, self.ctx
-        from .engine import full_active
+        from .engine import full_active, no_incumbent
+        from .model import interval_bits
         if self.bits is not None:
-            from .model import interval_bits
             self.base = int(base)
             self.bits[0] = torch.from_numpy(interval_bits(np.asarray(lb0), np.asarray(ub0), self.set_words, self.base).view(np.int64)).to(self.dev)
+        l0, u0 = (torch.from_numpy(np.ascontiguousarray(b, np.int32)).to(self.dev) for b in (lb0, ub0))
         if self.cells:
-            l0 = torch.from_numpy(np.ascontiguousarray(lb0, np.int32)).to(self.dev).reshape(1, -1)
-            u0 = torch.from_numpy(np.ascontiguousarray(ub0, np.int32)).to(self.dev).reshape(1, -1)
-            ctx.pack_rows(l0, u0, self.lb[0:1], self._stream())
+            ctx.pack_rows(l0.reshape(1, -1), u0.reshape(1, -1), self.lb[0:1], self._stream())
         else:
-            self.lb[0] = torch.from_numpy(np.ascontiguousarray(lb0, np.int32)).to(self.dev)
-            self.ub[0] = torch.from_numpy(np.ascontiguousarray(ub0, np.int32)).to(self.dev)
+            self.lb[0], self.ub[0] = l0, u0
         if self.act is not None:
             self.act[0] = torch.from_numpy(full_active(1, ctx.n_units).view(np.int64)[0]).to(self.dev)
         if self.dirty is not None:
             self.dirty[0] = -1  # the root is propagated from scratch
         self.segs = [[0, 1]]
         self.stats = DeviceSearchStats()
-        if self.brancher == "enumerate":
-            self.eoff[0:2] = 0  # the root has no exclusions
-            self.esegs = [[0, 0, 0, 0]]
+        self.kind.reset()
         if self.objective is not None:
-            from .engine import no_incumbent
             self.best.fill_(no_incumbent(self.objective[1]))
             self.improved.zero_()
             self._improved_seen = 0
@@ -260,136 +352,72 @@ class DeviceSearch:
         else.  ``stop_at`` only ends this call after that many nodes in total (a caller's chunk of a larger budget, e.g. one rank's share
         between two exchanges of parallel_search_device): every node's status counts.
         With an objective, ``all_solutions`` is ignored: branch and bound runs to the end of the search."""
-        torch, ctx, st = self.torch, self.ctx, self.stats
+        torch, ctx, st, kind = self.torch, self.ctx, self.stats, self.kind
         bnb = self.objective is not None
-        enum = self.brancher == "enumerate"
-        if bnb:
-            all_solutions = True
-            obj = {"var": self.objective[0], "mode": self.objective[1], "best": self.best, "best_lb": self.best_lb, "best_ub": self.best_ub,
-                   "best_bits": self.best_bits, "improved": self.improved}
+        all_solutions = all_solutions or bnb
         stream = self._stream()
         batch = min(int(batch) if batch else self.batch, self.batch)
-        rounds = 0
-        done = False
+        first_round, done = st.rounds, False
         ctx.set_option("branch_reverse", 1)  # children arrive in pop order (a context-wide knob: restored below)
         while self.segs:
-            if max_rounds and rounds >= max_rounds:
+            if max_rounds and st.rounds - first_round >= max_rounds:
                 break
             self._merge_top(batch)
             start, length = self.segs[-1]
             top = start + length
-            # the children (at most 2n rows) go right above the popped parents: when the buffer is nearly full, first
-            # squeeze out the holes, then take fewer nodes (a deeper, narrower dive) instead of overflowing
-            if self.cap - top < 2 * min(batch, length) or (enum and self._arena_take(min(batch, length)) < min(batch, length)):
+            # the children (at most 2n rows, and for Enumerate their lists) go right above the popped parents: when a buffer is nearly full,
+            # first squeeze out the holes, then take fewer nodes (a deeper, narrower dive) instead of overflowing
+            want = min(batch, length)
+            if self.cap - top < 2 * want or kind.take(want, final=False) < want:
                 self.compact()
                 start, length = self.segs[-1]
                 top = start + length
             room = self.cap - top
             if room < 2:
                 raise RuntimeError(f"open-node stack full ({self.size} of {self.cap}); raise `capacity`")
-            n = min(batch, length, room // 2)
-            if enum:
-                # the same for the exclusion arena: what the children's lists may need has to fit above the top segment's entries
-                fit = self._arena_take(n)
-                if fit < n:
-                    fit = self._arena_take(n, exact=True)
-                if fit < 1:
-                    raise RuntimeError(f"exclusion arena full ({self.esegs[-1][1] + self.esegs[-1][2]} of {self.ecap} entries in use); raise `excl_capacity`")
-                if fit < n:
-                    self.arena_events["fewer"] += 1
-                n = fit
-            for cap_nodes in (node_limit, stop_at):
-                if cap_nodes:
-                    n = min(n, cap_nodes - st.num_nodes)
+            n = kind.take(min(batch, length, room // 2))
+            n = min([n] + [cap_nodes - st.num_nodes for cap_nodes in (node_limit, stop_at) if cap_nodes])
             if n <= 0:
                 break
             lo = top - n
-            lb, ub = self.lb[lo:top], (None if self.cells else self.ub[lo:top])
-            act = None if self.act is None else self.act[lo:top]
             status = self.status[:n]
-            if enum:
-                o, e0, cnt, emax = self.esegs[-1]
-                k = lo - start  # the batch's first row within its segment
-                poff, pex, etop, oc = self.eoff[o + k:o + length + 1], self.ex[e0:], e0 + cnt, o + length + 1
-                ctx.propagate_device_excl(n, lb, ub, lb, ub, None, status, poff, pex, stream, dirty=None if self.dirty is None else self.dirty[lo:top])
-                ctx.branch_device_excl(n, lb, ub, status, poff, pex, self.val, self.lb[top:], self.ub[top:], self.eoff[oc:], self.ex[etop:], self.ecap - etop,
-                                       self.counts, stream, child_dirty=None if self.dirty is None else self.dirty[top:])
-                self.round_buf[8:9].copy_(self.eoff[o + k:o + k + 1])  # where the popped nodes' entries begin: what the segment keeps
-            elif self.cells:
-                dirty = None if self.dirty is None else self.dirty[lo:top]
-                ctx.propagate_device(n, lb, None, lb, None, None, None, status, stream, dirty=dirty, cells=True)
-                ctx.branch_device_cells(n, lb, status, self.lb[top:], self.counts, stream, child_dirty=None if self.dirty is None else self.dirty[top:])
-            elif bnb and self.bits is None:
-                ctx.propagate_device_bnb(n, lb, ub, lb, ub, act, act, status, obj, stream)
-                ctx.branch_device(n, lb, ub, act, status, self.lb[top:], self.ub[top:], None if self.act is None else self.act[top:],
-                                  self.counts, stream)
-            elif bnb:
-                bits = self.bits[lo:top]
-                ctx.propagate_device_bnb(n, None, None, lb, ub, act, act, status, obj, stream, bits_in=bits, bits_out=bits)
-                ctx.branch_device_set(n, bits, lb, ub, act, status, self.bits[top:], None if self.act is None else self.act[top:], self.counts, stream)
-            elif self.bits is None and self.dirty is not None:
-                ctx.propagate_device(n, lb, ub, lb, ub, act, act, status, stream, dirty=self.dirty[lo:top])
-                ctx.branch_device(n, lb, ub, act, status, self.lb[top:], self.ub[top:], None if self.act is None else self.act[top:],
-                                  self.counts, stream, child_dirty=self.dirty[top:])
-            elif self.bits is None:
-                ctx.propagate_device(n, lb, ub, lb, ub, act, act, status, stream)
-                ctx.branch_device(n, lb, ub, act, status, self.lb[top:], self.ub[top:], None if self.act is None else self.act[top:],
-                                  self.counts, stream)
-            else:
-                bits = self.bits[lo:top]
-                ctx.propagate_device(n, None, None, lb, ub, act, act, status, stream, bits_in=bits, bits_out=bits)
-                ctx.branch_device_set(n, bits, lb, ub, act, status, self.bits[top:], None if self.act is None else self.act[top:], self.counts, stream)
-            if bnb:
-                n_children, n_true, n_false, _, n_other, best, improved = (int(x) for x in self.round_buf.cpu().tolist())  # the round's only D2H sync
-                if improved != self._improved_seen:
-                    self._improved_seen = improved
-                    st.best = best
-                    st.incumbents.append(best)
-            elif enum:
-                n_children, n_true, n_false, _, n_other, n_child_excl, error, _, kept = (int(x) for x in self.round_buf.cpu().tolist())  # the round's only D2H sync
-                if error and not n_other:
-                    raise RuntimeError({1: "the exclusion arena was sized too small for this round", 3: "Cannot select a variable in a space where all variables are assigned.",
-                                        4: "Cannot select a value: every value of the variable is excluded."}.get(error, f"pcp_branch_device_excl: error {error}"))
-            else:
-                n_children, n_true, n_false, _, n_other = (int(x) for x in self.counts.cpu().tolist())  # the round's only D2H sync
+            kind.launch(n, lo, top, status, stream)
+            buf = self.round_buf.cpu().tolist()  # the round's only D2H sync
+            n_children, n_true, n_false, _, n_other = buf[:5]
             if n_other:
                 raise RuntimeError(f"{n_other} nodes were refused by the engine (bounds outside the declared hull): the search cannot continue")
-            rounds += 1
+            kind.check(buf)
+            if bnb and buf[6] != self._improved_seen:
+                self._improved_seen = buf[6]
+                st.best = buf[5]
+                st.incumbents.append(buf[5])
             st.rounds += 1
             st.num_nodes += n
-            limit_row_true = False
+            s_last = None
             if node_limit and st.num_nodes >= node_limit:
                 # the node that reaches the limit (the last one in pop order: the lowest row of the round) is counted as a node, never as a
                 # solution or a failure: StopNode hands EndOfSearch to the monitor (stop_node.rs:57-62 under Monitor, stop_node.rs:90-97)
                 s_last = int(status[0].item())
-                limit_row_true = s_last == TRUE
-                n_true -= int(s_last == TRUE)
-                n_false -= int(s_last == FALSE)
+                n_true, n_false = n_true - (s_last == TRUE), n_false - (s_last == FALSE)
             st.num_solution += n_true
             st.num_failed_node += n_false
             if n_true and len(st.solutions) < keep_solutions:
                 rows = torch.nonzero(status == TRUE).flatten()
-                if limit_row_true:
+                if s_last == TRUE:
                     rows = rows[rows != 0]  # (not counted: not kept either)
                 rows = rows[: keep_solutions - len(st.solutions)]
-                sol = ctx.unpack_rows(lb[rows].contiguous(), stream_ptr=stream)[0] if self.cells else lb[rows]
-                for r in sol.cpu().numpy():
-                    st.solutions.append(r)
+                st.solutions += list(kind.unpacked(self.lb[lo:top][rows], stream).cpu().numpy())
             # pop the parents; the children, already in left-first order (branch_reverse), become the new top segment
             self.segs[-1][1] = length - n
-            if enum:
-                self.esegs[-1][2] = kept
-            if self.segs[-1][1] == 0:
+            kind.pop(buf, length == n)
+            if length == n:
                 self.segs.pop()
-                if enum:
-                    self.esegs.pop()
             if n_true and not all_solutions:
                 done = True
                 break
             if n_children:
                 self.segs.append([top, n_children])
-                if enum:
-                    self.esegs.append([oc, etop, n_child_excl, emax + 1])
+                kind.push(buf)
             st.max_open = max(st.max_open, self.size)
         ctx.set_option("branch_reverse", 0)
         if bnb and st.best is not None:
@@ -408,8 +436,6 @@ class DeviceSearch:
         """The k open nodes on top of the stack (device tensors, views)."""
         if self.segs and self.segs[-1][1] < min(k, self.size):
             self.compact()
-        if not self.segs:
-            return self.lb[0:0], (None if self.cells else self.ub[0:0]), (None if self.act is None else self.act[0:0])
-        s, l = self.segs[-1]
+        s, l = self.segs[-1] if self.segs else (0, 0)
         lo = max(s, s + l - k)
-        return self.lb[lo:s + l], (None if self.cells else self.ub[lo:s + l]), (None if self.act is None else self.act[lo:s + l])
+        return self.lb[lo:s + l], _cut(self.ub, lo, s + l), _cut(self.act, lo, s + l)
