@@ -357,6 +357,28 @@ int32_t pcp_branch_device_hint(pcp_ctx* ctx, uint32_t n_nodes, const int32_t* lb
 int32_t pcp_branch_device_set(pcp_ctx* ctx, uint32_t n_nodes, const uint64_t* bits, const int32_t* lb, const int32_t* ub, const uint64_t* active,
                               const uint8_t* status, uint64_t* child_bits, uint64_t* child_active, uint32_t* counts, void* hip_stream);
 
+/* Enumerate over FDSpace (set mode):
+ * ≡ Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>::enter (search/branching/brancher.rs:52-71, search/branching/enumerate.rs:47-60)
+ * applied to every PCP_UNKNOWN node of a propagated set-mode batch.  On an IntervalSet XEqY(x, Constant v) intersects x with {v} and
+ * XNeqY(x, Constant v) removes v wherever it sits, and both are then entailed: both children are folded into the variable's set, there are
+ * no exclusion lists and the children are propagated like any other set-mode row.
+ *   variable = first index among the variables of minimal CARDINALITY > 1   (first_smallest_var.rs:30-39 on Domain::size())
+ *   value    = PCP_VAL_MIN: m = lb of the variable (min_val.rs:25-27: lower(), always a member);  PCP_VAL_MIDDLE: m = (lb + ub) / 2 on a 64-bit
+ *              sum, truncated toward zero (middle_val.rs:25-27).  The value is the member of the set nearest to m, m - d before m + d: m
+ *              itself when it is a member — the reference; when it is not, the reference's left child fails, its right child is the parent
+ *              again and the search does not end.
+ *   children = `x = value` (the variable's set becomes {value}) then `x != value` (that bit is cleared); neither is ever empty.
+ *   bits, lb, ub, active, child_bits, child_active : as for pcp_branch_device_set (active / child_active both NULL for implicit nodes)
+ *   counts   : device uint32[8] out = { n_children, n_true, n_false, n_unknown, n_other, 0, error, 0 }, the first five as in
+ *              pcp_branch_device.  error: 0 none; 3 an Unknown node without a variable of cardinality > 1 (the reference panics,
+ *              first_smallest_var.rs:36).  On an error the children are unspecified and the inputs untouched.
+ * Children come in tree order, two per Unknown node, x = value first; option branch_reverse reverses the rows as for pcp_branch_device.
+ * Interval-mode model: PCP_ERR_UNSUPPORTED.  val > PCP_VAL_MIN or a null required pointer: PCP_ERR_ARG.  n_nodes == 0: PCP_OK, counts zeroed.
+ * Everything is enqueued on hip_stream, nothing is synchronised.  (PCP_VAL_MIDDLE / PCP_VAL_MIN: below.) */
+int32_t pcp_branch_device_set_enum(pcp_ctx* ctx, uint32_t n_nodes, const uint64_t* bits, const int32_t* lb, const int32_t* ub, const uint64_t* active,
+                                   const uint8_t* status, uint32_t val, uint64_t* child_bits, uint64_t* child_active, uint32_t* counts,
+                                   void* hip_stream);
+
 /* The brancher that WRITES exclusion lists — the other half of pcp_propagate_device_excl:
  * ≡ Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>::enter (search/branching/brancher.rs:52-71, search/branching/enumerate.rs:47-60)
  * applied to every PCP_UNKNOWN node of a propagated batch whose node i carries the entries excl[excl_off[i] .. excl_off[i + 1]) (excl_off NULL =
@@ -468,6 +490,14 @@ typedef struct {
   uint32_t* solution_flag;
 } pcp_forest_state;
 int32_t pcp_dfs_forest_device_set(pcp_ctx* ctx, const pcp_forest_state* st, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream);
+/* The same loop under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate> (enumerate.rs:47-60): a level is `x = value, then x != value`
+ * instead of `x <= value, then x > value`; variable and value as pcp_branch_device_set_enum chooses them (val: PCP_VAL_MIDDLE / PCP_VAL_MIN;
+ * anything else: PCP_ERR_ARG), both children folded into the set through the trail.  State, counters, StopNode, first solution and errors
+ * are those of pcp_dfs_forest_device_set; a level records its distributor (levels[..][3]: bit 0 = given away, bit 1 = Enumerate), so
+ * pcp_dfs_forest_split_set hands over the right branch of either.  Roots expanded with pcp_branch_device_set_enum under the same val make
+ * the union one Enumerate tree. */
+int32_t pcp_dfs_forest_device_set_enum(pcp_ctx* ctx, const pcp_forest_state* st, uint32_t val, uint32_t n_steps, uint32_t stop_on_solution,
+                                       uint64_t node_limit, void* hip_stream);
 /* Between two calls of pcp_dfs_forest_device_set: finished trees take over work from trees that still have some.  pairs = n_pairs x
  * (donor, receiver) tree indices (device uint32).  For every pair whose receiver is finished and whose donor has an open right branch
  * left, the donor's OLDEST open right branch (the subtree nearest its root) becomes the receiver's new root — built from the donor's

@@ -197,6 +197,9 @@ extern "C" {
     pub fn pcp_branch_device_set(ctx: *mut pcp_ctx, n_nodes: u32, bits: *const u64, lb: *const i32, ub: *const i32, active: *const u64,
                                  status: *const u8, child_bits: *mut u64, child_active: *mut u64, counts: *mut u32,
                                  hip_stream: *mut c_void) -> i32; // the same brancher over IntervalSet domains
+    pub fn pcp_branch_device_set_enum(ctx: *mut pcp_ctx, n_nodes: u32, bits: *const u64, lb: *const i32, ub: *const i32, active: *const u64,
+                                      status: *const u8, val: u32, child_bits: *mut u64, child_active: *mut u64, counts: *mut u32,
+                                      hip_stream: *mut c_void) -> i32; // Enumerate over IntervalSet domains: x = v / x != v folded into the sets; counts: [8]
     pub fn pcp_branch_device_excl(ctx: *mut pcp_ctx, n_nodes: u32, lb: *const i32, ub: *const i32, status: *const u8, excl_off: *const u32,
                                   excl: *const pcp_excl, val: u32, child_lb: *mut i32, child_ub: *mut i32, child_dirty: *mut u32,
                                   child_excl_off: *mut u32, child_excl: *mut pcp_excl, child_excl_capacity: u32, counts: *mut u32,
@@ -205,6 +208,8 @@ extern "C" {
                                  hip_stream: *mut c_void) -> i32; // st's arrays are [n_trees]-strided: tree t is a pcp_dfs_device instance
     pub fn pcp_dfs_forest_device_set(ctx: *mut pcp_ctx, st: *const pcp_forest_state, n_steps: u32, stop_on_solution: u32, node_limit: u64,
                                      hip_stream: *mut c_void) -> i32;
+    pub fn pcp_dfs_forest_device_set_enum(ctx: *mut pcp_ctx, st: *const pcp_forest_state, val: u32, n_steps: u32, stop_on_solution: u32,
+                                          node_limit: u64, hip_stream: *mut c_void) -> i32; // the same loop under Enumerate (val: PCP_VAL_*)
     pub fn pcp_dfs_forest_split_set(ctx: *mut pcp_ctx, st: *const pcp_forest_state, n_pairs: u32, pairs: *const u32, done: *mut u32,
                                     hip_stream: *mut c_void) -> i32; // pairs = n_pairs x (donor, receiver), device memory
     pub fn pcp_dfs_device(ctx: *mut pcp_ctx, st: *const pcp_dfs_state, n_steps: u32, stop_on_solution: u32, node_limit: u64,

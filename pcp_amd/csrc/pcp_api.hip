@@ -967,8 +967,11 @@ static int32_t dfs_enqueue_steps(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n
   return rc;
 }
 
-int32_t pcp_dfs_forest_device_set(pcp_ctx* c, const pcp_forest_state* st, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
+// The search loop over FDSpace under either distributor: BinarySplit on MiddleVal (pcp_dfs_forest_device_set) or Enumerate on `val`.
+static int32_t dfs_forest_set(pcp_ctx* c, const pcp_forest_state* st, bool enumerate, uint32_t val, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
+                              void* hip_stream) {
   if (!c || !st) return PCP_ERR_ARG;
+  if (enumerate && val > PCP_VAL_MIN) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_enum: val must be PCP_VAL_MIDDLE or PCP_VAL_MIN");
   if (!c->set_words) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set needs a set-mode model (pcp_model_reset with set_words > 0)");
   if (!c->hull_set) return fail(c, PCP_ERR_CONTRACT, "set mode needs the hull of the initial domains (pcp_model_set_hull)");
   if ((int64_t)c->hull_hi - c->hull_lo >= (int64_t)c->set_words * 64) return fail(c, PCP_ERR_CONTRACT, "the declared hull does not fit set_words * 64 values");
@@ -993,13 +996,23 @@ int32_t pcp_dfs_forest_device_set(pcp_ctx* c, const pcp_forest_state* st, uint32
   a.bits = st->bits; a.tree = st->tree; a.levels = reinterpret_cast<uint4*>(st->levels); a.trail = reinterpret_cast<uint4*>(st->trail);
   a.counters = reinterpret_cast<unsigned long long*>(st->counters); a.total_nodes = reinterpret_cast<unsigned long long*>(st->total_nodes);
   a.stop = st->stop; a.first_solution = st->first_solution; a.solution_flag = st->solution_flag; a.stats = c->d_stats;
+  a.val_mode = val;
   if (!n_steps) return PCP_OK;
   c->last_plan = pcp_plan{1u, 1u, 0u, 0u, 0u, 0u, 1u, 1u, st->n_trees, 1024u, (uint32_t)lds, cap, 0u};
   if (c->opt_time_kernels) HIP_TRY(c, hipEventRecord(c->ev_start, stream));
-  HIP_TRY(c, launch_setdfs(a, stream));
+  HIP_TRY(c, launch_setdfs(a, enumerate, stream));
   if (c->opt_time_kernels) HIP_TRY(c, hipEventRecord(c->ev_stop, stream));
   c->ev_valid = c->opt_time_kernels != 0;
   return PCP_OK;
+}
+
+int32_t pcp_dfs_forest_device_set(pcp_ctx* c, const pcp_forest_state* st, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
+  return dfs_forest_set(c, st, false, PCP_VAL_MIDDLE, n_steps, stop_on_solution, node_limit, hip_stream);
+}
+
+int32_t pcp_dfs_forest_device_set_enum(pcp_ctx* c, const pcp_forest_state* st, uint32_t val, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
+                                       void* hip_stream) {
+  return dfs_forest_set(c, st, true, val, n_steps, stop_on_solution, node_limit, hip_stream);
 }
 
 int32_t pcp_dfs_forest_split_set(pcp_ctx* c, const pcp_forest_state* st, uint32_t n_pairs, const uint32_t* pairs, uint32_t* done, void* hip_stream) {
@@ -1242,6 +1255,27 @@ int32_t pcp_branch_device_set(pcp_ctx* c, uint32_t n_nodes, const uint64_t* bits
   if (n_nodes == 0) { HIP_TRY(c, hipMemsetAsync(counts, 0, 20, stream)); return PCP_OK; }
   HIP_TRY(c, launch_set_branch(n_nodes, c->n_vars, c->set_words, c->hull_lo, active ? words : 0u, bits, lb, ub, active, status, child_bits, child_active,
                                c->d_child_base, counts, (uint32_t)c->opt_branch_reverse, stream));
+  return PCP_OK;
+}
+
+// Enumerate over set-mode rows (pcp_set.hip): both children are folded into the sets, so this is pcp_branch_device_set with another kernel.
+int32_t pcp_branch_device_set_enum(pcp_ctx* c, uint32_t n_nodes, const uint64_t* bits, const int32_t* lb, const int32_t* ub, const uint64_t* active,
+                                   const uint8_t* status, uint32_t val, uint64_t* child_bits, uint64_t* child_active, uint32_t* counts, void* hip_stream) {
+  if (!c) return PCP_ERR_ARG;
+  if (!counts) return fail(c, PCP_ERR_ARG, "pcp_branch_device_set_enum: counts must not be null");
+  if (!c->set_words) return fail(c, PCP_ERR_UNSUPPORTED, "pcp_branch_device_set_enum: set mode only (interval mode: pcp_branch_device_excl)");
+  if (val > PCP_VAL_MIN) return fail(c, PCP_ERR_ARG, "pcp_branch_device_set_enum: val must be PCP_VAL_MIDDLE or PCP_VAL_MIN");
+  if (!c->hull_set) return fail(c, PCP_ERR_CONTRACT, "set mode needs the hull of the initial domains (pcp_model_set_hull)");
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint32_t words = (c->n_units + 63) / 64;
+  if (n_nodes && (!status || (c->n_vars && (!bits || !lb || !ub || !child_bits)) || (words && ((active == nullptr) != (child_active == nullptr)))))
+    return fail(c, PCP_ERR_ARG, "pcp_branch_device_set_enum: null buffer");
+  PCP_TRY(ensure(c, c->d_child_base, c->cap_child_base, std::max<uint32_t>(n_nodes, 1)));
+  HIP_TRY(c, hipMemsetAsync(counts, 0, 8 * sizeof(uint32_t), stream));
+  if (n_nodes == 0) return PCP_OK;
+  HIP_TRY(c, launch_set_branch_enum(n_nodes, c->n_vars, c->set_words, c->hull_lo, active ? words : 0u, bits, lb, ub, active, status, val, child_bits, child_active,
+                                    c->d_child_base, counts, (uint32_t)c->opt_branch_reverse, stream));
   return PCP_OK;
 }
 

@@ -122,7 +122,7 @@ struct SetDfsArgs {
   unsigned long long node_limit;
   uint64_t* bits;                 // [n_trees][n_vars][set_words]: each tree's current node
   uint32_t* tree;                 // [n_trees][4]: levels, trail length, pending variable, finished
-  uint4* levels;                  // [n_trees][level_cap]: (variable, value, trail mark, -)
+  uint4* levels;                  // [n_trees][level_cap]: (variable, value, trail mark, kLevelGiven | kLevelEnum)
   uint4* trail;                   // [n_trees][trail_cap]: (word index, variable, removed bits lo, hi)
   unsigned long long* counters;   // [n_trees][4]: nodes, solutions, failed, error
   unsigned long long* total_nodes;
@@ -130,9 +130,13 @@ struct SetDfsArgs {
   int32_t* first_solution;
   uint32_t* solution_flag;
   pcp_stats* stats;
+  uint32_t val_mode;              // the Enumerate loop only: PCP_VAL_MIDDLE / PCP_VAL_MIN
 };
+// a level's flags (levels[..].w): its right branch went to another tree (setdfs_split_kernel); its distributor is Enumerate (x = v, then
+// x != v) instead of BinarySplit (x <= v, then x > v)
+constexpr uint32_t kLevelGiven = 1u, kLevelEnum = 2u;
 size_t lds_bytes_set_dfs(uint32_t n_vars, uint32_t n_slots, uint32_t set_words, uint32_t list_cap);
-hipError_t launch_setdfs(const SetDfsArgs& a, hipStream_t stream);
+hipError_t launch_setdfs(const SetDfsArgs& a, bool enumerate, hipStream_t stream);
 hipError_t launch_setdfs_split(const SetDfsArgs& a, uint32_t n_pairs, const uint32_t* pairs, uint32_t* done, hipStream_t stream);
 
 hipError_t launch_branch_scan(uint32_t n_nodes, const uint8_t* status, uint32_t* child_base, uint32_t* counts, hipStream_t stream);
@@ -140,6 +144,12 @@ hipError_t launch_branch_scan(uint32_t n_nodes, const uint8_t* status, uint32_t*
 hipError_t launch_set_branch(uint32_t n_nodes, uint32_t n_vars, uint32_t set_words, int32_t base, uint32_t words, const uint64_t* bits, const int32_t* lb,
                              const int32_t* ub, const uint64_t* active, const uint8_t* status, uint64_t* child_bits, uint64_t* child_active,
                              uint32_t* child_base, uint32_t* counts, uint32_t reverse, hipStream_t stream);
+
+// Set-mode branching under Enumerate (pcp_branch_device_set_enum): the same variable, the member of its set nearest to MiddleVal's / MinVal's
+// value, children x = v / x != v folded into the set.  counts[6] = error (3: an Unknown node without a variable of cardinality > 1).
+hipError_t launch_set_branch_enum(uint32_t n_nodes, uint32_t n_vars, uint32_t set_words, int32_t base, uint32_t words, const uint64_t* bits, const int32_t* lb,
+                                  const int32_t* ub, const uint64_t* active, const uint8_t* status, uint32_t val, uint64_t* child_bits, uint64_t* child_active,
+                                  uint32_t* child_base, uint32_t* counts, uint32_t reverse, hipStream_t stream);
 
 // One step of the device-side DFS after the fixpoint of the top node: count it, branch it in place (right child over the parent's
 // row, left child on top) or pop it, keep the first solution.

@@ -609,6 +609,24 @@ constexpr uint32_t kDfsFull = 0xFFFFFFFFu;
 constexpr uint32_t kDfsChunk = 8;  // nodes a tree reserves from the forest's counter at a time
 
 struct SetDfsCarve { SetCarve c; size_t touched, adjo, total; };
+
+// The member of one variable's set (words w[0 .. sw), value = base + bit index) nearest to m, m - d before m + d, as a key for a minimum:
+// 2 d for the nearest member <= m, 2 d + 1 for the nearest >= m (m itself: 0).  A word is reduced at once — the highest member <= m and the
+// lowest member >= m of the masked word —, never value by value; the caller takes the minimum over the words.  ~0: no member in this word.
+__device__ __forceinline__ unsigned long long nearest_member_key(unsigned long long w, long long word_lo, long long m) {
+  const long long t = m - word_lo;  // m's bit in this word, if 0 <= t < 64
+  const unsigned long long le = t < 0 ? 0ull : (t >= 63 ? ~0ull : ((2ull << t) - 1ull));  // the values <= m
+  const unsigned long long ge = t <= 0 ? ~0ull : (t >= 64 ? 0ull : (~0ull << t));         // the values >= m
+  unsigned long long key = ~0ull;
+  const unsigned long long below = w & le, above = w & ge;
+  if (below) key = 2ull * (unsigned long long)(m - (word_lo + 63 - __clzll((long long)below)));
+  if (above) key = min(key, 2ull * (unsigned long long)(word_lo + (__ffsll((long long)above) - 1) - m) + 1ull);
+  return key;
+}
+__device__ __forceinline__ long long nearest_member_value(unsigned long long key, long long m) {
+  const long long d = (long long)(key >> 1);
+  return (key & 1ull) ? m + d : m - d;
+}
 __host__ __device__ inline SetDfsCarve set_dfs_carve(uint32_t V, uint32_t S, uint32_t sw, uint32_t cap) {
   SetDfsCarve d;
   d.c = set_carve(V, S, sw, cap);
@@ -618,6 +636,10 @@ __host__ __device__ inline SetDfsCarve set_dfs_carve(uint32_t V, uint32_t S, uin
   return d;
 }
 
+// ENUM: the loop under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate> (enumerate.rs:47-60) — a level is `x = v, then x != v`,
+// v the member of the set nearest to the selector's value (a.val_mode).  A template parameter, not a scalar branch: the BinarySplit
+// instantiation is the code it was before the parameter existed.
+template <bool ENUM>
 __global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t tid = threadIdx.x, nth = blockDim.x, lane = tid & 63;
@@ -901,9 +923,28 @@ __global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a)
       if (n_levels >= a.level_cap) { c_err = 1; --c_nodes; pending = kDfsFull; if (tid == 0) atomicAdd(a.total_nodes, ~0ull); break; }
       const uint32_t var = (uint32_t)key;
       const int2 d = bnd[var];
-      const int val = (int)(((long long)d.x + (long long)d.y) / 2);  // MiddleVal (middle_val.rs:25-27)
-      if (tid == 0) levels[n_levels] = make_uint4(var, (uint32_t)val, tlen, 0u);
-      restrict_var(var, (long long)val + 1, d.y);  // the left child x <= val (binary_split.rs:46-57)
+      if constexpr (ENUM) {
+        // MinVal: lower() (min_val.rs:25-27), a member; MiddleVal: (lower + upper) / 2 (middle_val.rs:25-27) or, when that is a hole of the
+        // set, the member nearest to it, the lower one first.  Wavefront 0 alone needs the value: one lane per word, a minimum across lanes.
+        if (wv == 0) {
+          long long v = d.x;
+          if (a.val_mode != PCP_VAL_MIN) {
+            const long long m = ((long long)d.x + (long long)d.y) / 2;
+            unsigned long long nk = ~0ull;
+            for (uint32_t k = lane; k < sw; k += 64) nk = min(nk, nearest_member_key(bits[(size_t)var * sw + k], (long long)a.base + 64ll * (long long)k, m));
+            for (int o = 32; o > 0; o >>= 1) nk = min(nk, (unsigned long long)__shfl_xor(nk, o));
+            v = nearest_member_value(nk, m);
+          }
+          if (tid == 0) levels[n_levels] = make_uint4(var, (uint32_t)(int)v, tlen, kLevelEnum);
+          // the left child x = v (enumerate.rs:47-53): everything below v and everything above it leaves the set
+          restrict_var(var, d.x, v - 1);
+          restrict_var(var, v + 1, d.y);
+        }
+      } else {
+        const int val = (int)(((long long)d.x + (long long)d.y) / 2);  // MiddleVal (middle_val.rs:25-27)
+        if (tid == 0) levels[n_levels] = make_uint4(var, (uint32_t)val, tlen, 0u);
+        restrict_var(var, (long long)val + 1, d.y);  // the left child x <= val (binary_split.rs:46-57)
+      }
       ++n_levels;
       pending = var;
       descend = true;
@@ -911,7 +952,7 @@ __global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a)
     if (!descend) {
       // ---- backtrack: the deepest level whose right branch is still open (a level whose right branch was given to another tree
       // is undone like any other and skipped) ------------------------------------------------------------------------------
-      uint4 lv = make_uint4(0u, 0u, 0u, 1u);
+      uint4 lv = make_uint4(0u, 0u, 0u, kLevelGiven);
       uint32_t from = tlen;
       while (n_levels) {
         --n_levels;
@@ -922,16 +963,17 @@ __global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a)
           atomicOr(&touched[e.y >> 5], 1u << (e.y & 31u));
         }
         from = lv.z;
-        if (!lv.w) break;
+        if (!(lv.w & kLevelGiven)) break;
       }
-      if (lv.w) { finished = true; break; }  // nothing left that is this tree's
+      if (lv.w & kLevelGiven) { finished = true; break; }  // nothing left that is this tree's
       __syncthreads();
       if (tid == 0) { misc[S_TRAILLEN] = from; misc[S_FAIL] = 0; }
       for (uint32_t v = tid; v < V; v += nth)
         if ((touched[v >> 5] >> (v & 31u)) & 1u) bnd[v] = scan_bounds(bits + (size_t)v * sw, sw, a.base);
       __syncthreads();
       for (uint32_t i = tid; i < Wv; i += nth) touched[i] = 0;
-      restrict_var(lv.x, bnd[lv.x].x, (long long)(int)lv.y);  // the right child x > val
+      // the right child, by the level's own distributor: x > val (binary_split.rs:52-57) or x != val (enumerate.rs:54-59)
+      restrict_var(lv.x, (lv.w & kLevelEnum) ? (long long)(int)lv.y : (long long)bnd[lv.x].x, (long long)(int)lv.y);
       pending = lv.x;
     }
     if (tid == 0) { misc[S_OPEN] = 0; misc[S_TOTAL] = 0; misc[S_TOTAL2] = 0; if (last) atomicExch(a.stop, 1u); }  // (a node's last round leaves its count behind)
@@ -994,14 +1036,16 @@ __global__ void __launch_bounds__(256) setdfs_split_kernel(const SetDfsArgs a, c
     atomicOr(&dst[e.x], ((unsigned long long)e.w << 32) | e.z);
   }
   __syncthreads();
-  // the right child x > val: the values up to val leave the variable's set (binary_split.rs:52-57)
+  // the right child, by the level's own distributor — x > val: the values up to val leave the variable's set (binary_split.rs:52-57);
+  // x != val: val alone does (enumerate.rs:54-59)
   for (uint32_t k = tid; k < sw; k += nth) {
     const long long t = (long long)(int)lv.y - ((long long)a.base + 64ll * (long long)k);
-    const unsigned long long le = t < 0 ? 0ull : (t >= 63 ? ~0ull : ((2ull << t) - 1ull));
-    dst[(size_t)lv.x * sw + k] &= ~le;
+    unsigned long long gone = t < 0 ? 0ull : (t >= 63 ? ~0ull : ((2ull << t) - 1ull));
+    if (lv.w & kLevelEnum) gone = (t < 0 || t > 63) ? 0ull : (1ull << t);
+    dst[(size_t)lv.x * sw + k] &= ~gone;
   }
   if (tid == 0) {
-    lvp->w = 1u;
+    lvp->w = lv.w | kLevelGiven;
     td[3] = (td[3] & 0xFFu) | ((given + 1) << 8);
     tr[0] = 0; tr[1] = 0; tr[2] = lv.x; tr[3] = 0;
     done[blockIdx.x] = 1;
@@ -1013,11 +1057,16 @@ size_t lds_bytes_set_dfs(uint32_t n_vars, uint32_t n_slots, uint32_t set_words, 
   return c.total <= 160 * 1024 ? c.total : 0;
 }
 
-hipError_t launch_setdfs(const SetDfsArgs& a, hipStream_t stream) {
+hipError_t launch_setdfs(const SetDfsArgs& a, bool enumerate, hipStream_t stream) {
   const size_t lds = set_dfs_carve(a.m.n_vars, a.m.n_slots, a.set_words, a.list_cap).total;
   hipError_t e;
-  if (lds > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void*>(setdfs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
-  hipLaunchKernelGGL(setdfs_kernel, dim3(a.n_trees), dim3(kSetThreads), lds, stream, a);
+  if (enumerate) {
+    if (lds > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void*>(setdfs_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
+    hipLaunchKernelGGL(setdfs_kernel<true>, dim3(a.n_trees), dim3(kSetThreads), lds, stream, a);
+  } else {
+    if (lds > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void*>(setdfs_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
+    hipLaunchKernelGGL(setdfs_kernel<false>, dim3(a.n_trees), dim3(kSetThreads), lds, stream, a);
+  }
   return hipGetLastError();
 }
 
@@ -1110,6 +1159,84 @@ hipError_t launch_set_branch(uint32_t n_nodes, uint32_t n_vars, uint32_t set_wor
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(set_branch_kernel, dim3(n_nodes), dim3(256), 0, stream, n_vars, set_words, base, words, bits, lb, ub, active, child_base, child_bits,
                      child_active, counts, reverse);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>::enter over FDSpace (search/branching/brancher.rs:52-71,
+// search/branching/enumerate.rs:47-60): the variable of set_branch_kernel; the member of its set nearest to the selector's value
+// (min_val.rs:25-27: lb; middle_val.rs:25-27: (lb + ub) / 2), the lower one first — the value itself whenever it is a member;
+// children `x = v` (the set becomes {v}) and `x != v` (bit v cleared), rows as set_branch_kernel writes them.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) set_branch_enum_kernel(uint32_t V, uint32_t sw, int32_t base, uint32_t words, const uint64_t* __restrict__ bits,
+                                                              const int32_t* __restrict__ lb, const int32_t* __restrict__ ub,
+                                                              const uint64_t* __restrict__ active, const uint32_t* __restrict__ child_base,
+                                                              uint32_t val_mode, uint64_t* __restrict__ child_bits, uint64_t* __restrict__ child_active,
+                                                              uint32_t* __restrict__ counts, uint32_t reverse) {
+  const uint32_t node = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
+  const uint32_t slot = child_base[node];
+  if (slot == 0xFFFFFFFFu) return;
+  const uint32_t rowL = reverse ? counts[0] - 1 - slot : slot;
+  const uint32_t rowR = reverse ? rowL - 1 : slot + 1;
+  __shared__ unsigned long long best[4], near[4];
+  const uint64_t* pb = bits + (size_t)node * V * sw;
+  unsigned long long key = ~0ull;
+  for (uint32_t v = tid; v < V; v += nth) {
+    unsigned long long size = 0;
+    for (uint32_t k = 0; k < sw; ++k) size += (unsigned long long)__popcll(pb[(size_t)v * sw + k]);
+    if (size > 1) key = min(key, (size << 32) | v);
+  }
+  for (int o = 32; o > 0; o >>= 1) key = min(key, (unsigned long long)__shfl_down(key, o));
+  if ((tid & 63) == 0) best[tid >> 6] = key;
+  __syncthreads();
+  key = best[0];
+  for (uint32_t w = 1; w < (nth >> 6); ++w) key = min(key, best[w]);
+  if (key == ~0ull) {
+    // Unknown, yet no variable with more than one value: the reference panics here (first_smallest_var.rs:36); the rows stay unwritten
+    if (tid == 0) atomicMax(&counts[6], 3u);
+    return;
+  }
+  const uint32_t var = (uint32_t)key;
+  const long long lo = lb[(size_t)node * V + var], hi = ub[(size_t)node * V + var];
+  const long long m = val_mode == PCP_VAL_MIN ? lo : (lo + hi) / 2;
+  unsigned long long nk = ~0ull;
+  for (uint32_t k = tid; k < sw; k += nth) nk = min(nk, nearest_member_key(pb[(size_t)var * sw + k], (long long)base + 64ll * (long long)k, m));
+  for (int o = 32; o > 0; o >>= 1) nk = min(nk, (unsigned long long)__shfl_down(nk, o));
+  if ((tid & 63) == 0) near[tid >> 6] = nk;
+  __syncthreads();
+  nk = near[0];
+  for (uint32_t w = 1; w < (nth >> 6); ++w) nk = min(nk, near[w]);
+  const long long vbit = nearest_member_value(nk, m) - (long long)base;  // (the set has two members or more: one was found)
+  const uint32_t vword = (uint32_t)(vbit >> 6);
+  const uint64_t one = 1ull << (vbit & 63);
+  uint64_t* b0 = child_bits + (size_t)rowL * V * sw;
+  uint64_t* b1 = child_bits + (size_t)rowR * V * sw;
+  for (size_t i = tid; i < (size_t)V * sw; i += nth) {
+    const uint64_t w = pb[i];
+    if ((uint32_t)(i / sw) == var) {
+      const bool here = (uint32_t)(i % sw) == vword;
+      b0[i] = here ? one : 0ull;    // x = v
+      b1[i] = here ? w & ~one : w;  // x != v
+    } else {
+      b0[i] = w;
+      b1[i] = w;
+    }
+  }
+  if (active) {
+    const uint64_t* pa = active + (size_t)node * words;
+    uint64_t* a0 = child_active + (size_t)rowL * words;
+    uint64_t* a1 = child_active + (size_t)rowR * words;
+    for (uint32_t w = tid; w < words; w += nth) { const uint64_t x = pa[w]; a0[w] = x; a1[w] = x; }
+  }
+}
+
+hipError_t launch_set_branch_enum(uint32_t n_nodes, uint32_t n_vars, uint32_t set_words, int32_t base, uint32_t words, const uint64_t* bits, const int32_t* lb,
+                                  const int32_t* ub, const uint64_t* active, const uint8_t* status, uint32_t val, uint64_t* child_bits, uint64_t* child_active,
+                                  uint32_t* child_base, uint32_t* counts, uint32_t reverse, hipStream_t stream) {
+  hipError_t e = launch_branch_scan(n_nodes, status, child_base, counts, stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(set_branch_enum_kernel, dim3(n_nodes), dim3(256), 0, stream, n_vars, set_words, base, words, bits, lb, ub, active, child_base, val,
+                     child_bits, child_active, counts, reverse);
   return hipGetLastError();
 }
 

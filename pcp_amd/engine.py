@@ -25,7 +25,7 @@ ERRORS = {-1: "PCP_ERR_ARG", -2: "PCP_ERR_CONTRACT", -3: "PCP_ERR_HIP", -4: "PCP
 ABI_SYMBOLS = [
     "pcp_ctx_create", "pcp_ctx_destroy", "pcp_last_error", "pcp_strerror", "pcp_abi_version",
     "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull",
-    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
+    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
 ]
 
 
@@ -142,9 +142,11 @@ def load_library():
     L.pcp_unpack_rows.argtypes = [vp, u32, vp, vp, vp, vp]
     L.pcp_branch_device_cells.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
     L.pcp_branch_device_set.argtypes = [vp, u32] + [vp] * 9
+    L.pcp_branch_device_set_enum.argtypes = [vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.pcp_branch_device_excl.argtypes = [vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp]
     L.pcp_dfs_device.argtypes = [vp, C.POINTER(DfsState), u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_set.argtypes = [vp, C.POINTER(ForestState), u32, u32, C.c_uint64, vp]
+    L.pcp_dfs_forest_device_set_enum.argtypes = [vp, C.POINTER(ForestState), u32, u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_split_set.argtypes = [vp, C.POINTER(ForestState), u32, vp, vp, vp]
     L.pcp_dfs_forest_device.argtypes = [vp, C.POINTER(DfsState), u32, u32, u32, C.c_uint64, vp]
     L.pcp_stats_reset.argtypes = [vp, vp]
@@ -154,7 +156,7 @@ def load_library():
     L.pcp_last_plan.argtypes = [vp, C.POINTER(PcpPlan)]
     L.pcp_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
     for f in ("pcp_ctx_create", "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull", "pcp_model_set_hull",
-              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
+              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
         getattr(L, f).restype = i32
     _lib = L
     return L
@@ -190,6 +192,7 @@ class Context:
         self.n_units = 0
         self.set_words = 0
         self.supports_hints = True  # pcp_device_batch.dirty_var / pcp_branch_device_hint (ABI v7): search drivers keep a hint per open node
+        self.supports_set_enumerate = True  # pcp_branch_device_set_enum / pcp_dfs_forest_device_set_enum: Enumerate over set-mode stores
         for kv in filter(None, os.environ.get("PCP_SET_OPTIONS", "").split(",")):  # experiments: pcp_set_option on every new context (k=v,k=v)
             k_, v_ = kv.split("=")
             self.set_option(k_, int(v_))
@@ -392,6 +395,14 @@ class Context:
         self._check(self._L.pcp_branch_device_set(self._h, n_nodes, _ptr(bits), _ptr(lb), _ptr(ub), _ptr(active), _ptr(status), _ptr(child_bits), _ptr(child_active),
                                                   _ptr(counts), C.c_void_p(stream_ptr)))
 
+    def branch_device_set_enum(self, n_nodes: int, bits, lb, ub, active, status, val, child_bits, child_active, counts, stream_ptr: int = 0):
+        """pcp_branch_device_set_enum: Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate> over a propagated set-mode batch (rows as for
+        branch_device_set).  val: "middle" / "min" (or VAL_MIDDLE / VAL_MIN).  counts: int32[8] = n_children, n_true, n_false, n_unknown,
+        n_other, 0, error, 0; an error (3: an Unknown node without a variable of two values or more) is reported there only.  Nothing is
+        synchronised; search.branch_enumerate_set is the same brancher on the host and raises instead."""
+        self._check(self._L.pcp_branch_device_set_enum(self._h, n_nodes, _ptr(bits), _ptr(lb), _ptr(ub), _ptr(active), _ptr(status), int(VAL_MODES.get(val, val)),
+                                                       _ptr(child_bits), _ptr(child_active), _ptr(counts), C.c_void_p(stream_ptr)))
+
     def branch_device_excl(self, n_nodes: int, lb, ub, status, excl_off, excl, val, child_lb, child_ub, child_excl_off, child_excl, child_excl_capacity: int,
                            counts, stream_ptr: int = 0, child_dirty=None):
         """pcp_branch_device_excl: Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate> over a propagated batch whose node i carries the
@@ -491,13 +502,18 @@ class Context:
 
     def dfs_forest_set(self, root_bits, stop_on_solution: bool = False, node_limit: int = 0, steps_per_launch: int = 256,
                        level_capacity: int = 0, trail_capacity: int = 0, max_launches: int = 1 << 30, want_solution: bool = True,
-                       info: dict | None = None, rebalance: bool = True):
+                       info: dict | None = None, rebalance: bool = True, brancher: str = "split", val: str = "middle"):
         """pcp_dfs_forest_device_set: the reference's search loop over FDSpace on the device, one tree per workgroup, the current
-        node in LDS, an undo trail in HBM.  root_bits: [n_trees, n_vars, set_words] uint64 (numpy or a CUDA int64 tensor): the roots,
+        node in LDS, an undo trail in HBM.  brancher="enumerate": the same loop under Enumerate on MiddleVal (val="middle") or MinVal ("min"),
+        pcp_dfs_forest_device_set_enum; val is ignored under "split" (BinarySplit on MiddleVal).  root_bits: [n_trees, n_vars, set_words] uint64 (numpy or a CUDA int64 tensor): the roots,
         not yet propagated.  Launches of steps_per_launch nodes per tree are repeated until every tree is finished, the forest
         stopped (solution / node limit / error) or max_launches is reached.
         Returns dict(nodes, solutions, failed, error, finished_trees, stopped, launches, first_solution, per_tree=[n_trees, 4])."""
         import torch
+        if brancher not in ("split", "enumerate"):
+            raise ValueError(f"brancher must be 'split' or 'enumerate', not {brancher!r}")
+        if brancher == "enumerate" and val not in VAL_MODES:
+            raise ValueError(f"val must be 'middle' or 'min', not {val!r}")
         dev = torch.device("cuda", self.device)
         V, sw = self.n_vars, self.set_words
         # 0 = the model's own bound: a trail entry takes at least one value out of a set and is popped before the value can return, so a
@@ -523,7 +539,11 @@ class Context:
         stream = torch.cuda.current_stream(dev).cuda_stream
         launches = splits = 0
         while launches < max_launches:
-            self._check(self._L.pcp_dfs_forest_device_set(self._h, C.byref(st), int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit), C.c_void_p(stream)))
+            if brancher == "enumerate":
+                self._check(self._L.pcp_dfs_forest_device_set_enum(self._h, C.byref(st), VAL_MODES[val], int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit),
+                                                                   C.c_void_p(stream)))
+            else:
+                self._check(self._L.pcp_dfs_forest_device_set(self._h, C.byref(st), int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit), C.c_void_p(stream)))
             launches += 1
             g = glob.cpu().tolist()  # (the launch's only synchronisation)
             ts = tree.cpu().numpy()

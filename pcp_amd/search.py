@@ -410,3 +410,89 @@ def dfs_set(ctx, lb0: np.ndarray, ub0: np.ndarray, base: int, all_solutions: boo
     obj = _objective(objective)
     root = (interval_bits(np.asarray(lb0), np.asarray(ub0), ctx.set_words, base), None if implicit else full_active(1, ctx.n_units)[0])
     return _search(_Sets(ctx, base, implicit), root, all_solutions, node_limit, batch, obj)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Enumerate over sets (search/branching/enumerate.rs:33-60 on FDSpace).  On an IntervalSet XEqY(x, Constant v) intersects x with {v}
+# and XNeqY(x, Constant v) removes v wherever it sits; both are then entailed.  So both children fold into the variable's set: no
+# exclusion lists, and the propagation is dfs_set's.  The value rule is DESIGN.md §2 "Value selection on a set".
+# ---------------------------------------------------------------------------------------------------------------------
+def set_members(words: np.ndarray, base: int) -> np.ndarray:
+    """The values of one variable's set (words: [set_words] uint64, value v = bit v - base), ascending."""
+    w = np.ascontiguousarray(words, np.uint64).reshape(-1)
+    on = (w[:, None] >> np.arange(64, dtype=np.uint64)[None, :]) & np.uint64(1)
+    return np.nonzero(on.reshape(-1))[0].astype(np.int64) + int(base)
+
+
+def enumerate_value_set(words: np.ndarray, lo: int, hi: int, base: int, val: str = "middle") -> int:
+    """The value Enumerate branches a set on.  MinVal: lo (min_val.rs:25-27).  MiddleVal: m = (lo + hi) / 2 truncated toward zero
+    (middle_val.rs:25-27).  The value taken is the member of the set nearest to that, m - d before m + d: m itself whenever it is a member
+    (always, for MinVal on the set's own lower bound), otherwise — where the reference would branch on an absent value for ever — the
+    nearest one."""
+    if val not in ("middle", "min"):
+        raise ValueError(f"val must be 'middle' or 'min', not {val!r}")
+    s = int(lo) + int(hi)
+    m = int(lo) if val == "min" else (abs(s) // 2) * (1 if s >= 0 else -1)
+    mem = set_members(words, base)
+    if not len(mem):
+        raise RuntimeError("Cannot select a value: the variable's set is empty.")
+    key = 2 * np.abs(mem - m) + (mem > m)
+    return int(mem[key.argmin()])
+
+
+def branch_enumerate_set(bits: np.ndarray, lb: np.ndarray, ub: np.ndarray, base: int, active: Optional[np.ndarray], val: str = "middle", var=None):
+    """Enumerate children of each (Unknown, propagated) set-mode row, folded into the sets: returns (bits2, active2), 2 rows per input row,
+    ``x = v`` (the variable's set becomes {v}) then ``x != v`` (bit v cleared) — the reference's order, enumerate.rs:47-60.  The variable is
+    FirstSmallestVar's on cardinalities (``var``: an index or one per row instead, as the reference's test_distributor distributes); the value
+    is enumerate_value_set's on the row's bounds lb / ub.  Neither child is ever empty: the variable has two values or more and v is one of
+    them.  Everything else is copied.  This is the specification pcp_branch_device_set_enum is compared with."""
+    if val not in ("middle", "min"):
+        raise ValueError(f"val must be 'middle' or 'min', not {val!r}")
+    bits = np.ascontiguousarray(bits, np.uint64)
+    bits = bits[None] if bits.ndim == 2 else bits
+    n, V, sw = bits.shape
+    lb = np.asarray(lb).reshape(n, V)
+    ub = np.asarray(ub).reshape(n, V)
+    size = _popcount64(bits).sum(axis=2)
+    rows = np.arange(n)
+    if var is None:
+        big = np.iinfo(np.int64).max
+        key = np.where(size > 1, size, big)
+        x = key.argmin(axis=1)
+    else:
+        x = np.broadcast_to(np.asarray(var, np.int64), (n,))
+    if n and (size[rows, x] <= 1).any():
+        raise RuntimeError("Cannot select a variable in a space where all variables are assigned.")
+    B = np.repeat(bits, 2, axis=0)
+    for i in range(n):
+        v = enumerate_value_set(bits[i, x[i]], lb[i, x[i]], ub[i, x[i]], base, val)
+        k, bit = divmod(v - int(base), 64)
+        one = np.uint64(1) << np.uint64(bit)
+        B[2 * i, x[i]] = 0
+        B[2 * i, x[i], k] = one        # x = v
+        B[2 * i + 1, x[i], k] &= ~one  # x != v
+    A = None if active is None else np.repeat(active, 2, axis=0)
+    return B, A
+
+
+class _SetsEnumerate(_Sets):
+    """_Sets under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>."""
+
+    def __init__(self, ctx, base, implicit, val):
+        super().__init__(ctx, base, implicit)
+        self.val = val
+
+    def branch(self, done_batch, unk):
+        Bt, lb, ub, A = done_batch
+        cb, ca = branch_enumerate_set(Bt[unk], lb[unk], ub[unk], self.base, None if A is None else A[unk], val=self.val)
+        return [(cb[c], None if ca is None else ca[c]) for c in range(len(cb))]
+
+
+def dfs_enumerate_set(ctx, lb0: np.ndarray, ub0: np.ndarray, base: int, all_solutions: bool = False, node_limit: int = 0, batch: int = 1,
+                      val: str = "middle", implicit: bool = True) -> SearchStats:
+    """dfs_set under Enumerate: the same nodes, propagated by the same ``ctx.propagate_set``, branched by branch_enumerate_set.  With
+    batch = 1 the node order is the reference's left-first DFS under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>."""
+    if val not in ("middle", "min"):
+        raise ValueError(f"val must be 'middle' or 'min', not {val!r}")
+    root = (interval_bits(np.asarray(lb0), np.asarray(ub0), ctx.set_words, base), None if implicit else full_active(1, ctx.n_units)[0])
+    return _search(_SetsEnumerate(ctx, base, implicit, val), root, all_solutions, node_limit, batch)

@@ -10,7 +10,9 @@ search/branch_and_bound.rs:64-84): the incumbent stays on the device, is folded 
 and replaced by the batch's best Satisfiable node after it; it comes back in the same copy as the counts.
 With ``brancher="enumerate"`` the round is `pcp_propagate_device_excl` + `pcp_branch_device_excl` (Brancher<FirstSmallestVar, MiddleVal | MinVal,
 Enumerate>, search/branching/enumerate.rs:33-60): every open node owns a list of value exclusions, the lists live in a device arena next to the
-rows and are written by the brancher — rows, hints and lists stay on the GPU from the root to the leaves.
+rows and are written by the brancher — rows, hints and lists stay on the GPU from the root to the leaves.  Over a set-mode context the same
+``brancher="enumerate"`` needs none of that: x = v and x != v are exact operations on the sets, so the round is `pcp_propagate_device` +
+`pcp_branch_device_set_enum` on the rows of the BinarySplit search (no arena, no hints).
 PyTorch provides the device buffers; every kernel is this repository's.
 """
 from __future__ import annotations
@@ -95,6 +97,21 @@ class _Sets(_Int32Rows):
         else:
             ctx.propagate_device_bnb(n, None, None, lb, ub, act, act, status, s._obj, stream, bits_in=bits, bits_out=bits)
         ctx.branch_device_set(n, bits, lb, ub, act, status, s.bits[top:], _cut(s.act, top), s.counts, stream)
+
+
+class _SetsEnumerate(_Sets):
+    """Sets under Enumerate: the round of _Sets with the other brancher (x = v / x != v folded into the sets)."""
+    n_counts = 8  # round_buf: the brancher's counts[8]
+
+    def launch(self, n, lo, top, status, stream):
+        s, ctx = self.s, self.s.ctx
+        lb, ub, act, bits = s.lb[lo:top], s.ub[lo:top], _cut(s.act, lo, top), s.bits[lo:top]
+        ctx.propagate_device(n, None, None, lb, ub, act, act, status, stream, bits_in=bits, bits_out=bits)
+        ctx.branch_device_set_enum(n, bits, lb, ub, act, status, s.val, s.bits[top:], _cut(s.act, top), s.counts, stream)
+
+    def check(self, buf):
+        if buf[6]:
+            raise RuntimeError({3: "Cannot select a variable in a space where all variables are assigned."}.get(buf[6], f"pcp_branch_device_set_enum: error {buf[6]}"))
 
 
 class _Enumerate(_Int32Rows):
@@ -199,8 +216,8 @@ class DeviceSearch:
                 raise ValueError("Enumerate runs on int32 rows: cells=True is refused")
             if objective is not None:
                 raise ValueError("Enumerate takes no objective (branch and bound runs under BinarySplit)")
-            if getattr(ctx, "set_words", 0):
-                raise ValueError("Enumerate is for interval mode (in set mode x != v is an exact set operation: no exclusion lists)")
+            if getattr(ctx, "set_words", 0) and not getattr(ctx, "supports_set_enumerate", False):
+                raise ValueError("Enumerate in set mode needs a context that offers branch_device_set_enum (pcp_branch_device_set_enum): this one does not")
             if not implicit and ctx.words:
                 raise ValueError("Enumerate needs implicit nodes (pcp_propagate_device_excl takes no `active` rows)")
         self.dev = device if device is not None else torch.device("cuda", ctx.device)
@@ -242,8 +259,8 @@ class DeviceSearch:
         self.status = torch.zeros(self.batch, dtype=u8, device=self.dev)
         self.segs: List[List[int]] = []  # [start, length], bottom to top
         self.stats = DeviceSearchStats()
-        self.kind = (_Enumerate(self, excl_capacity) if brancher == "enumerate" else _Cells(self) if self.cells else _Sets(self) if self.set_words
-                     else _Int32Rows(self))
+        self.kind = ((_SetsEnumerate(self) if self.set_words else _Enumerate(self, excl_capacity)) if brancher == "enumerate"
+                     else _Cells(self) if self.cells else _Sets(self) if self.set_words else _Int32Rows(self))
         # what a round brings back, side by side: its one copy to the host reads all of it
         self.round_buf = torch.zeros(9, dtype=i32, device=self.dev)
         self.counts = self.round_buf[:self.kind.n_counts]

@@ -19,11 +19,12 @@ def share_of_budget(node_limit: int, seeded_nodes: int, rank: int, world: int) -
     return left // world + (1 if rank < left % world else 0)
 
 
-def seed_roots(ctx, lb0, ub0, base: int, want: int):
-    """Breadth-first expansion of the root to at least `want` open nodes (or until the tree is exhausted).
+def seed_roots(ctx, lb0, ub0, base: int, want: int, brancher: str = "split", val: str = "middle"):
+    """Breadth-first expansion of the root to at least `want` open nodes (or until the tree is exhausted) under the distributor
+    ``brancher`` ("split": BinarySplit on MiddleVal; "enumerate": Enumerate on ``val``, "middle" or "min").
     Returns (roots [k, V, set_words] int64 CUDA tensor, stats of the expansion)."""
     from .search_device import DeviceSearch
-    ds = DeviceSearch(ctx, batch=max(want, 1), capacity=4 * max(want, 1) + 64, implicit=True)
+    ds = DeviceSearch(ctx, batch=max(want, 1), capacity=4 * max(want, 1) + 64, implicit=True, brancher=brancher, val=val)
     ds.reset(lb0, ub0, base)
     while 0 < ds.size < want:
         if ds.advance(all_solutions=True, max_rounds=1, keep_solutions=0):
@@ -41,14 +42,16 @@ def trail_bound(ctx) -> int:
 
 
 def forest_search_set(ctx, lb0, ub0, base: int = 0, node_limit: int = 0, n_trees: int = 512, steps_per_launch: int = 2048, rank: int = 0, world: int = 1,
-                      trail_capacity: int = 0, level_capacity: int = 0, info: dict | None = None) -> dict:
+                      trail_capacity: int = 0, level_capacity: int = 0, info: dict | None = None, brancher: str = "split", val: str = "middle") -> dict:
     """All solutions of the space below (lb0, ub0) — or the first `node_limit` nodes of this rank's share of it.
+    brancher / val: the distributor of the expansion AND of the trees ("enumerate": Enumerate on MiddleVal or MinVal), so that their union is
+    one tree of that distributor.
     trail_capacity / level_capacity 0 = derived from the model (trail_bound): every trail entry takes at least one value out of one
     set and is popped before that value can come back, so a tree's trail never holds more entries than the root has values —
     n_vars * set_words * 64 at most.  (N-queens-1000: 1 024 000 entries = 16 MB per tree; a 100-variable model: 100 KB.)
     Returns dict(nodes, solutions, failed, error, seeded_nodes, trees, launches); with world > 1 the expansion's counters are
     reported by rank 0 only, so that a sum over the ranks counts every node once."""
-    roots, st = seed_roots(ctx, lb0, ub0, base, n_trees * world)
+    roots, st = seed_roots(ctx, lb0, ub0, base, n_trees * world, brancher=brancher, val=val)
     mine = roots[rank::world].contiguous()
     out = {"seeded_nodes": st.num_nodes if rank == 0 else 0, "trees": int(mine.shape[0]), "launches": 0,
            "nodes": st.num_nodes if rank == 0 else 0, "solutions": st.num_solution if rank == 0 else 0, "failed": st.num_failed_node if rank == 0 else 0,
@@ -63,7 +66,7 @@ def forest_search_set(ctx, lb0, ub0, base: int = 0, node_limit: int = 0, n_trees
     bound = trail_bound(ctx)
     r = ctx.dfs_forest_set(mine, node_limit=budget, steps_per_launch=steps_per_launch, trail_capacity=trail_capacity or bound,
                            level_capacity=level_capacity or min(bound, 1 << 14),
-                           want_solution=False, info=info)
+                           want_solution=False, info=info, brancher=brancher, val=val)
     out["nodes"] += r["nodes"]; out["solutions"] += r["solutions"]; out["failed"] += r["failed"]
     out["error"] = r["error"]; out["launches"] = r["launches"]
     return out
