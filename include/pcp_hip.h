@@ -498,6 +498,33 @@ int32_t pcp_dfs_forest_device_set(pcp_ctx* ctx, const pcp_forest_state* st, uint
  * the union one Enumerate tree. */
 int32_t pcp_dfs_forest_device_set_enum(pcp_ctx* ctx, const pcp_forest_state* st, uint32_t val, uint32_t n_steps, uint32_t stop_on_solution,
                                        uint64_t node_limit, void* hip_stream);
+/* Branch and bound around that loop — BranchAndBound<Propagation<Brancher<..>>> over FDSpace (search/branch_and_bound.rs:64-84; its test,
+ * branch_and_bound.rs:112-138, runs this composition), under either distributor (enumerate 0: BinarySplit on MiddleVal; 1: Enumerate on val,
+ * PCP_VAL_MIDDLE / PCP_VAL_MIN).  The forest shares ONE incumbent, the device word *best.  A tree entering a node — a root, a child, a right
+ * branch, the node a launch resumes, a node received through pcp_dfs_forest_split_set — first clears from the objective's set the values
+ * >= *best (minimize) or <= *best (maximize), read at that moment: the bound propagator of pcp_propagate_device_bnb, folded.  The removal
+ * goes through the trail, so a backtrack undoes it and the right child folds again; a node whose objective the fold empties is a node and a
+ * failed node.  On a solution the tree records var.lower() and the node's lower bounds as ITS latest — within a tree each beats the one
+ * before — and then lowers / raises *best atomically.  Nothing is copied per node: the bound costs one device load and, when it narrows,
+ * one trail entry per word.
+ *   var, mode : the objective variable (< n_vars), PCP_MINIMIZE / PCP_MAXIMIZE
+ *   best      : device int32[1], in/out: the incumbent; "no solution yet" as for pcp_objective: the fold is then a no-op.  A caller that
+ *               seeds it with a known bound gets only solutions that beat it.
+ *   tree_best : device [n_trees], the caller initialises every entry to that "no solution yet" value: the value of each tree's latest solution
+ *   tree_row  : device [n_trees][n_vars] or NULL: the lower bounds of that solution.  Afterwards the optimum's row is tree_row[t] of any tree
+ *               with tree_best[t] == *best (none: no solution beat the seeded incumbent).
+ * State, counters, errors, StopNode (node_limit) and pcp_dfs_forest_split_set between calls are those of pcp_dfs_forest_device_set; there is no
+ * stop on a solution — branch and bound runs to the end — and st->first_solution / st->solution_flag are ignored.  With n_trees = 1 the nodes
+ * are the reference's, one for one; with several trees the optimum is the same and the node count depends on when each tree saw which incumbent.
+ * Interval-mode model, var >= n_vars, mode > PCP_MAXIMIZE, enumerate > 1, val > PCP_VAL_MIN, a null best / tree_best: PCP_ERR_ARG. */
+typedef struct {
+  uint32_t var, mode;
+  int32_t* best;
+  int32_t* tree_best;
+  int32_t* tree_row;
+} pcp_forest_objective;
+int32_t pcp_dfs_forest_device_set_bnb(pcp_ctx* ctx, const pcp_forest_state* st, const pcp_forest_objective* obj, uint32_t enumerate, uint32_t val,
+                                      uint32_t n_steps, uint64_t node_limit, void* hip_stream);
 /* Between two calls of pcp_dfs_forest_device_set: finished trees take over work from trees that still have some.  pairs = n_pairs x
  * (donor, receiver) tree indices (device uint32).  For every pair whose receiver is finished and whose donor has an open right branch
  * left, the donor's OLDEST open right branch (the subtree nearest its root) becomes the receiver's new root — built from the donor's

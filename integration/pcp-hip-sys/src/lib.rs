@@ -153,6 +153,17 @@ pub struct pcp_forest_state {
     pub solution_flag: *mut u32,
 }
 
+/// The objective of `pcp_dfs_forest_device_set_bnb`: branch and bound in the set-mode forest, one incumbent word for all trees.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct pcp_forest_objective {
+    pub var: u32,
+    pub mode: u32,            // PCP_MINIMIZE / PCP_MAXIMIZE
+    pub best: *mut i32,       // device int32[1], in/out
+    pub tree_best: *mut i32,  // [n_trees], initialised to the "no solution yet" value
+    pub tree_row: *mut i32,   // [n_trees][n_vars] or null
+}
+
 /// `pcp_debug_counters` slots (ABI v6): which code paths ran since the last `pcp_stats_reset`.
 pub const PCP_DBG_BIG_DENSE: usize = 0;
 pub const PCP_DBG_BIG_SPARSE: usize = 1;
@@ -210,6 +221,8 @@ extern "C" {
                                      hip_stream: *mut c_void) -> i32;
     pub fn pcp_dfs_forest_device_set_enum(ctx: *mut pcp_ctx, st: *const pcp_forest_state, val: u32, n_steps: u32, stop_on_solution: u32,
                                           node_limit: u64, hip_stream: *mut c_void) -> i32; // the same loop under Enumerate (val: PCP_VAL_*)
+    pub fn pcp_dfs_forest_device_set_bnb(ctx: *mut pcp_ctx, st: *const pcp_forest_state, obj: *const pcp_forest_objective, enumerate: u32, val: u32,
+                                         n_steps: u32, node_limit: u64, hip_stream: *mut c_void) -> i32; // BranchAndBound around either loop
     pub fn pcp_dfs_forest_split_set(ctx: *mut pcp_ctx, st: *const pcp_forest_state, n_pairs: u32, pairs: *const u32, done: *mut u32,
                                     hip_stream: *mut c_void) -> i32; // pairs = n_pairs x (donor, receiver), device memory
     pub fn pcp_dfs_device(ctx: *mut pcp_ctx, st: *const pcp_dfs_state, n_steps: u32, stop_on_solution: u32, node_limit: u64,

@@ -967,17 +967,23 @@ static int32_t dfs_enqueue_steps(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n
   return rc;
 }
 
-// The search loop over FDSpace under either distributor: BinarySplit on MiddleVal (pcp_dfs_forest_device_set) or Enumerate on `val`.
-static int32_t dfs_forest_set(pcp_ctx* c, const pcp_forest_state* st, bool enumerate, uint32_t val, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
-                              void* hip_stream) {
+// The search loop over FDSpace under either distributor: BinarySplit on MiddleVal (pcp_dfs_forest_device_set) or Enumerate on `val`;
+// obj != nullptr: under branch and bound (pcp_dfs_forest_device_set_bnb).
+static int32_t dfs_forest_set(pcp_ctx* c, const pcp_forest_state* st, const pcp_forest_objective* obj, bool enumerate, uint32_t val, uint32_t n_steps,
+                              uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
   if (!c || !st) return PCP_ERR_ARG;
   if (enumerate && val > PCP_VAL_MIN) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_enum: val must be PCP_VAL_MIDDLE or PCP_VAL_MIN");
   if (!c->set_words) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set needs a set-mode model (pcp_model_reset with set_words > 0)");
+  if (obj) {
+    if (obj->var >= c->n_vars) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_bnb: objective variable out of range");
+    if (obj->mode > PCP_MAXIMIZE) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_bnb: mode must be PCP_MINIMIZE or PCP_MAXIMIZE");
+    if (!obj->best || !obj->tree_best) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_bnb: best and tree_best are required");
+  }
   if (!c->hull_set) return fail(c, PCP_ERR_CONTRACT, "set mode needs the hull of the initial domains (pcp_model_set_hull)");
   if ((int64_t)c->hull_hi - c->hull_lo >= (int64_t)c->set_words * 64) return fail(c, PCP_ERR_CONTRACT, "the declared hull does not fit set_words * 64 values");
   if (!st->n_trees || !st->bits || !st->tree || !st->levels || !st->trail || !st->counters || !st->total_nodes || !st->stop || !st->level_capacity || !st->trail_capacity)
     return fail(c, PCP_ERR_ARG, "null buffer / zero capacity");
-  if ((st->first_solution == nullptr) != (st->solution_flag == nullptr)) return fail(c, PCP_ERR_ARG, "first_solution and solution_flag go together");
+  if (!obj && (st->first_solution == nullptr) != (st->solution_flag == nullptr)) return fail(c, PCP_ERR_ARG, "first_solution and solution_flag go together");
   hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
   HIP_TRY(c, hipSetDevice(c->device));
   { const int32_t rcf = finalize_model(c); if (rcf) return rcf; }
@@ -997,22 +1003,34 @@ static int32_t dfs_forest_set(pcp_ctx* c, const pcp_forest_state* st, bool enume
   a.counters = reinterpret_cast<unsigned long long*>(st->counters); a.total_nodes = reinterpret_cast<unsigned long long*>(st->total_nodes);
   a.stop = st->stop; a.first_solution = st->first_solution; a.solution_flag = st->solution_flag; a.stats = c->d_stats;
   a.val_mode = val;
+  if (obj) {  // branch and bound runs to the end and keeps a row per tree instead of the forest's first solution
+    a.stop_on_solution = 0; a.first_solution = nullptr; a.solution_flag = nullptr;
+    a.obj_var = obj->var; a.obj_mode = obj->mode; a.obj_best = obj->best; a.tree_best = obj->tree_best; a.tree_row = obj->tree_row;
+  }
   if (!n_steps) return PCP_OK;
   c->last_plan = pcp_plan{1u, 1u, 0u, 0u, 0u, 0u, 1u, 1u, st->n_trees, 1024u, (uint32_t)lds, cap, 0u};
   if (c->opt_time_kernels) HIP_TRY(c, hipEventRecord(c->ev_start, stream));
-  HIP_TRY(c, launch_setdfs(a, enumerate, stream));
+  HIP_TRY(c, launch_setdfs(a, enumerate, obj != nullptr, stream));
   if (c->opt_time_kernels) HIP_TRY(c, hipEventRecord(c->ev_stop, stream));
   c->ev_valid = c->opt_time_kernels != 0;
   return PCP_OK;
 }
 
 int32_t pcp_dfs_forest_device_set(pcp_ctx* c, const pcp_forest_state* st, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
-  return dfs_forest_set(c, st, false, PCP_VAL_MIDDLE, n_steps, stop_on_solution, node_limit, hip_stream);
+  return dfs_forest_set(c, st, nullptr, false, PCP_VAL_MIDDLE, n_steps, stop_on_solution, node_limit, hip_stream);
 }
 
 int32_t pcp_dfs_forest_device_set_enum(pcp_ctx* c, const pcp_forest_state* st, uint32_t val, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
                                        void* hip_stream) {
-  return dfs_forest_set(c, st, true, val, n_steps, stop_on_solution, node_limit, hip_stream);
+  return dfs_forest_set(c, st, nullptr, true, val, n_steps, stop_on_solution, node_limit, hip_stream);
+}
+
+int32_t pcp_dfs_forest_device_set_bnb(pcp_ctx* c, const pcp_forest_state* st, const pcp_forest_objective* obj, uint32_t enumerate, uint32_t val, uint32_t n_steps,
+                                      uint64_t node_limit, void* hip_stream) {
+  if (!c || !st || !obj) return c ? fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_bnb: null state / objective") : PCP_ERR_ARG;
+  if (enumerate > 1) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_bnb: enumerate must be 0 or 1");
+  if (val > PCP_VAL_MIN) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_bnb: val must be PCP_VAL_MIDDLE or PCP_VAL_MIN");
+  return dfs_forest_set(c, st, obj, enumerate != 0, val, n_steps, 0, node_limit, hip_stream);
 }
 
 int32_t pcp_dfs_forest_split_set(pcp_ctx* c, const pcp_forest_state* st, uint32_t n_pairs, const uint32_t* pairs, uint32_t* done, void* hip_stream) {

@@ -131,12 +131,17 @@ struct SetDfsArgs {
   uint32_t* solution_flag;
   pcp_stats* stats;
   uint32_t val_mode;              // the Enumerate loop only: PCP_VAL_MIDDLE / PCP_VAL_MIN
+  // branch and bound only (setdfs_kernel<.., true>, pcp_dfs_forest_device_set_bnb)
+  uint32_t obj_var, obj_mode;     // the objective variable, PCP_MINIMIZE / PCP_MAXIMIZE
+  int32_t* obj_best;              // device int32[1]: the forest's incumbent
+  int32_t* tree_best;             // [n_trees]: the value of each tree's last solution
+  int32_t* tree_row;              // [n_trees][n_vars] or null: its lower bounds
 };
 // a level's flags (levels[..].w): its right branch went to another tree (setdfs_split_kernel); its distributor is Enumerate (x = v, then
 // x != v) instead of BinarySplit (x <= v, then x > v)
 constexpr uint32_t kLevelGiven = 1u, kLevelEnum = 2u;
 size_t lds_bytes_set_dfs(uint32_t n_vars, uint32_t n_slots, uint32_t set_words, uint32_t list_cap);
-hipError_t launch_setdfs(const SetDfsArgs& a, bool enumerate, hipStream_t stream);
+hipError_t launch_setdfs(const SetDfsArgs& a, bool enumerate, bool bnb, hipStream_t stream);
 hipError_t launch_setdfs_split(const SetDfsArgs& a, uint32_t n_pairs, const uint32_t* pairs, uint32_t* done, hipStream_t stream);
 
 hipError_t launch_branch_scan(uint32_t n_nodes, const uint8_t* status, uint32_t* child_base, uint32_t* counts, hipStream_t stream);

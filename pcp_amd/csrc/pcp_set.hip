@@ -639,7 +639,23 @@ __host__ __device__ inline SetDfsCarve set_dfs_carve(uint32_t V, uint32_t S, uin
 // ENUM: the loop under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate> (enumerate.rs:47-60) — a level is `x = v, then x != v`,
 // v the member of the set nearest to the selector's value (a.val_mode).  A template parameter, not a scalar branch: the BinarySplit
 // instantiation is the code it was before the parameter existed.
-template <bool ENUM>
+//
+// BNB: BranchAndBound<..> around either loop (branch_and_bound.rs:64-84; pcp_dfs_forest_device_set_bnb).  The forest shares ONE incumbent,
+// a device int32 (a.obj_best).  On entering a node — before its propagation — the bound  var < best  (minimize) /  var > best  (maximize) is
+// folded into the objective variable's set through restrict_var: XLessY(var, Constant(best)) narrows once and is then entailed (pcp_bnb.hip),
+// the removal is trailed and marks the variable changed, and a fold that empties the set fails the node on the round loop's first
+// scan_bounds like any other empty set (a node and a failure, as the reference counts it).  Before any solution the incumbent is the "no
+// solution yet" value of pcp_hip.h, which lies outside every set: the fold is a no-op.  The fold stands where a barrier already follows the
+// branch restriction (descend, backtrack) and once at launch start, for the node the tree enters first: a root, a node persisted by the
+// launch before, or one handed over by setdfs_split_kernel.  Its trail entries come after the level's mark, so a backtrack undoes them and
+// the right child folds again against the incumbent of that moment; the incumbent only improves, so nothing a fold removed could have
+// stayed.  The trail bound of the plain loop holds: a fold entry, like every other, takes at least one value out of a set and is popped
+// before that value can return.  On a solution v = lower(var) beats every earlier value of this tree (the node passed the fold): the tree
+// keeps v and the node's lower bounds (a.tree_best, a.tree_row) and then lowers / raises the incumbent atomically — another tree may hold a
+// better one already, so the winner's row is chosen on the host among the trees whose value equals the final incumbent.  There is no
+// stop-on-solution and no first solution: branch and bound runs to the end (or to the node limit).  The two BNB = false instantiations are
+// the code they were before the parameter existed.
+template <bool ENUM, bool BNB>
 __global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t tid = threadIdx.x, nth = blockDim.x, lane = tid & 63;
@@ -690,6 +706,11 @@ __global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a)
     if (b.x > b.y) atomicOr(&misc[S_FAIL], 1u);
   }
   if (pending != kDfsFull && tid == 0) cur[pending >> 5] = 1u << (pending & 31u);  // (a node persisted by the launch before)
+  if constexpr (BNB) {
+    // a persisted node was folded when it was entered, and that fold's mark went with the launch: the objective is marked again
+    // (a variable marked without need only runs records that are no-ops at a fixpoint)
+    if (pending != kDfsFull && tid == 0) cur[a.obj_var >> 5] |= 1u << (a.obj_var & 31u);
+  }
   __syncthreads();
 
   uint32_t narrow = 0;
@@ -739,6 +760,25 @@ __global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a)
     }
     if (__ballot(changed) != 0 && lane == 0) { atomicOr(&cur[var >> 5], 1u << (var & 31u)); ++narrow; }
   };
+  // BNB: the bound folded into the objective's set — the values >= best (minimize) / <= best (maximize) leave it.  Wavefront 0, as restrict_var.
+  auto fold_bound = [&]() {
+    if (wv != 0) return;
+    const long long best = (long long)__hip_atomic_load(a.obj_best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (a.obj_mode == PCP_MINIMIZE) restrict_var(a.obj_var, best, 1ll << 40);
+    else restrict_var(a.obj_var, -(1ll << 40), best);
+  };
+  if constexpr (BNB) {
+    // the node this launch enters first, against the incumbent of now.  The sweep of a root reads bnd before the round loop scans
+    // anything, so the objective's bounds are taken again here.
+    fold_bound();
+    __syncthreads();
+    if (tid == 0) {
+      const int2 b = scan_bounds(bits + (size_t)a.obj_var * sw, sw, a.base);
+      bnd[a.obj_var] = b;
+      if (b.x > b.y) misc[S_FAIL] = 1u;
+    }
+    __syncthreads();
+  }
 
   for (uint32_t step = 0; step < a.n_steps; ++step) {
     // ---- may this node run?  (stop flag of the forest, the node limit of all trees together: StopNode, stop_node.rs:57-62) ----
@@ -910,7 +950,18 @@ __global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a)
     } else if (!open && last) {
     } else if (!open) {  // a solution (monitor.rs:19-68); the first one of the forest is kept
       ++c_sols;
-      if (a.first_solution) {
+      if constexpr (BNB) {
+        const int v = bnd[a.obj_var].x;  // the incumbent is var.lower() in both modes (branch_and_bound.rs:73-77)
+        if (a.tree_row)
+          for (uint32_t u = tid; u < V; u += nth) a.tree_row[(size_t)t * V + u] = bnd[u].x;
+        if (tid == 0) {
+          a.tree_best[t] = v;
+          // (the old value is used, so the atomic has been performed before the backtrack below reads the incumbent for its fold)
+          const int old = a.obj_mode == PCP_MINIMIZE ? __hip_atomic_fetch_min(a.obj_best, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                                                     : __hip_atomic_fetch_max(a.obj_best, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          misc[S_CTL + 1] = (uint32_t)old;
+        }
+      } else if (a.first_solution) {
         if (tid == 0) misc[S_CTL + 1] = atomicCAS(a.solution_flag, 0u, 1u) == 0u ? 1u : 0u;
         __syncthreads();
         if (misc[S_CTL + 1])
@@ -945,6 +996,7 @@ __global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a)
         if (tid == 0) levels[n_levels] = make_uint4(var, (uint32_t)val, tlen, 0u);
         restrict_var(var, (long long)val + 1, d.y);  // the left child x <= val (binary_split.rs:46-57)
       }
+      if constexpr (BNB) fold_bound();
       ++n_levels;
       pending = var;
       descend = true;
@@ -974,6 +1026,7 @@ __global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a)
       for (uint32_t i = tid; i < Wv; i += nth) touched[i] = 0;
       // the right child, by the level's own distributor: x > val (binary_split.rs:52-57) or x != val (enumerate.rs:54-59)
       restrict_var(lv.x, (lv.w & kLevelEnum) ? (long long)(int)lv.y : (long long)bnd[lv.x].x, (long long)(int)lv.y);
+      if constexpr (BNB) fold_bound();
       pending = lv.x;
     }
     if (tid == 0) { misc[S_OPEN] = 0; misc[S_TOTAL] = 0; misc[S_TOTAL2] = 0; if (last) atomicExch(a.stop, 1u); }  // (a node's last round leaves its count behind)
@@ -1016,6 +1069,9 @@ __global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a)
 // largest it can give).  That node = the donor's current node with its trail undone down to the level's mark (the parent's fixpoint)
 // and the right branch applied; it is built straight into the receiver's row.  The donor's level is marked as given (levels[..].w):
 // its search loop undoes it like any other level and does not take the right branch.  Runs BETWEEN launches of setdfs_kernel.
+// Under branch and bound (setdfs_kernel<.., true>) nothing changes here: the level's mark was taken at the parent's fixpoint, the parent's
+// own fold lies below it on the trail, so the handed-over node is that fixpoint, fold included, plus the right branch; the receiver folds
+// the incumbent of the moment into it at its next launch start and marks the objective changed, as for a node it persisted itself.
 __global__ void __launch_bounds__(256) setdfs_split_kernel(const SetDfsArgs a, const uint32_t* __restrict__ pairs, uint32_t* __restrict__ done) {
   const uint32_t d = pairs[2 * blockIdx.x], r = pairs[2 * blockIdx.x + 1], tid = threadIdx.x, nth = blockDim.x;
   const uint32_t V = a.m.n_vars, sw = a.set_words;
@@ -1057,17 +1113,18 @@ size_t lds_bytes_set_dfs(uint32_t n_vars, uint32_t n_slots, uint32_t set_words, 
   return c.total <= 160 * 1024 ? c.total : 0;
 }
 
-hipError_t launch_setdfs(const SetDfsArgs& a, bool enumerate, hipStream_t stream) {
-  const size_t lds = set_dfs_carve(a.m.n_vars, a.m.n_slots, a.set_words, a.list_cap).total;
+template <bool ENUM, bool BNB>
+static hipError_t launch_setdfs_as(const SetDfsArgs& a, size_t lds, hipStream_t stream) {
   hipError_t e;
-  if (enumerate) {
-    if (lds > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void*>(setdfs_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
-    hipLaunchKernelGGL(setdfs_kernel<true>, dim3(a.n_trees), dim3(kSetThreads), lds, stream, a);
-  } else {
-    if (lds > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void*>(setdfs_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
-    hipLaunchKernelGGL(setdfs_kernel<false>, dim3(a.n_trees), dim3(kSetThreads), lds, stream, a);
-  }
+  if (lds > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void*>(setdfs_kernel<ENUM, BNB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
+  hipLaunchKernelGGL((setdfs_kernel<ENUM, BNB>), dim3(a.n_trees), dim3(kSetThreads), lds, stream, a);
   return hipGetLastError();
+}
+
+hipError_t launch_setdfs(const SetDfsArgs& a, bool enumerate, bool bnb, hipStream_t stream) {
+  const size_t lds = set_dfs_carve(a.m.n_vars, a.m.n_slots, a.set_words, a.list_cap).total;
+  if (bnb) return enumerate ? launch_setdfs_as<true, true>(a, lds, stream) : launch_setdfs_as<false, true>(a, lds, stream);
+  return enumerate ? launch_setdfs_as<true, false>(a, lds, stream) : launch_setdfs_as<false, false>(a, lds, stream);
 }
 
 hipError_t launch_setdfs_split(const SetDfsArgs& a, uint32_t n_pairs, const uint32_t* pairs, uint32_t* done, hipStream_t stream) {

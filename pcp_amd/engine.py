@@ -25,7 +25,7 @@ ERRORS = {-1: "PCP_ERR_ARG", -2: "PCP_ERR_CONTRACT", -3: "PCP_ERR_HIP", -4: "PCP
 ABI_SYMBOLS = [
     "pcp_ctx_create", "pcp_ctx_destroy", "pcp_last_error", "pcp_strerror", "pcp_abi_version",
     "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull",
-    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
+    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
 ]
 
 
@@ -79,6 +79,11 @@ class ForestState(C.Structure):
     _fields_ = [("n_trees", C.c_uint32), ("level_capacity", C.c_uint32), ("trail_capacity", C.c_uint32), ("reserved", C.c_uint32),
                 ("bits", C.c_void_p), ("tree", C.c_void_p), ("levels", C.c_void_p), ("trail", C.c_void_p), ("counters", C.c_void_p),
                 ("total_nodes", C.c_void_p), ("stop", C.c_void_p), ("first_solution", C.c_void_p), ("solution_flag", C.c_void_p)]
+
+
+class ForestObjective(C.Structure):
+    """pcp_forest_objective: the objective of pcp_dfs_forest_device_set_bnb (branch and bound in the set-mode forest)."""
+    _fields_ = [("var", C.c_uint32), ("mode", C.c_uint32), ("best", C.c_void_p), ("tree_best", C.c_void_p), ("tree_row", C.c_void_p)]
 
 
 DFS_FULL = 0xFFFFFFFF
@@ -147,6 +152,7 @@ def load_library():
     L.pcp_dfs_device.argtypes = [vp, C.POINTER(DfsState), u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_set.argtypes = [vp, C.POINTER(ForestState), u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_set_enum.argtypes = [vp, C.POINTER(ForestState), u32, u32, u32, C.c_uint64, vp]
+    L.pcp_dfs_forest_device_set_bnb.argtypes = [vp, C.POINTER(ForestState), C.POINTER(ForestObjective), u32, u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_split_set.argtypes = [vp, C.POINTER(ForestState), u32, vp, vp, vp]
     L.pcp_dfs_forest_device.argtypes = [vp, C.POINTER(DfsState), u32, u32, u32, C.c_uint64, vp]
     L.pcp_stats_reset.argtypes = [vp, vp]
@@ -156,7 +162,7 @@ def load_library():
     L.pcp_last_plan.argtypes = [vp, C.POINTER(PcpPlan)]
     L.pcp_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
     for f in ("pcp_ctx_create", "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull", "pcp_model_set_hull",
-              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
+              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
         getattr(L, f).restype = i32
     _lib = L
     return L
@@ -509,11 +515,26 @@ class Context:
         not yet propagated.  Launches of steps_per_launch nodes per tree are repeated until every tree is finished, the forest
         stopped (solution / node limit / error) or max_launches is reached.
         Returns dict(nodes, solutions, failed, error, finished_trees, stopped, launches, first_solution, per_tree=[n_trees, 4])."""
+        _check_brancher(brancher, val)
+
+        def launch(st, steps, stream):
+            if brancher == "enumerate":
+                return self._L.pcp_dfs_forest_device_set_enum(self._h, C.byref(st), VAL_MODES[val], steps, int(bool(stop_on_solution)), int(node_limit), C.c_void_p(stream))
+            return self._L.pcp_dfs_forest_device_set(self._h, C.byref(st), steps, int(bool(stop_on_solution)), int(node_limit), C.c_void_p(stream))
+
+        return self._run_forest_set(root_bits, launch, node_limit=node_limit, steps_per_launch=steps_per_launch, level_capacity=level_capacity,
+                                    trail_capacity=trail_capacity, max_launches=max_launches, want_solution=want_solution, info=info, rebalance=rebalance)
+
+    def _run_forest_set(self, root_bits, launch, node_limit: int = 0, steps_per_launch: int = 256, level_capacity: int = 0, trail_capacity: int = 0,
+                        max_launches: int = 1 << 30, want_solution: bool = False, info: dict | None = None, rebalance: bool = True, live=None,
+                        ramp_steps: int = 0):
+        """The host side of the set-mode forest, shared by dfs_forest_set and dfs_forest_set_bnb: the forest's buffers, then launches of
+        ``launch(st, steps, stream)`` (a pcp_dfs_forest_device_set* call, its return code) until every tree is finished, the forest stopped or
+        max_launches is reached; between launches finished trees take work through pcp_dfs_forest_split_set.  ``live`` ([n_trees] bool or
+        None = all): the trees that start with a root; the others start finished and only receive work.  ``ramp_steps`` > 0: launches of that
+        many nodes while trees are still idle at the start, so that the splits fill them (at most 2 log2(n_trees) + 4 such launches).
+        Returns the result dict of dfs_forest_set."""
         import torch
-        if brancher not in ("split", "enumerate"):
-            raise ValueError(f"brancher must be 'split' or 'enumerate', not {brancher!r}")
-        if brancher == "enumerate" and val not in VAL_MODES:
-            raise ValueError(f"val must be 'middle' or 'min', not {val!r}")
         dev = torch.device("cuda", self.device)
         V, sw = self.n_vars, self.set_words
         # 0 = the model's own bound: a trail entry takes at least one value out of a set and is popped before the value can return, so a
@@ -529,6 +550,8 @@ class Context:
         T = bits.shape[0]
         tree = torch.zeros((T, 4), dtype=torch.int32, device=dev)
         tree[:, 2] = -1  # PCP_DFS_FULL
+        if live is not None:
+            tree[:, 3] = torch.from_numpy(1 - np.asarray(live, bool).astype(np.int32).reshape(T)).to(dev)  # finished: nothing of its own
         levels = torch.empty((T, level_capacity, 4), dtype=torch.int32, device=dev)  # (written before they are read: no fill)
         trail = torch.empty((T, trail_capacity, 4), dtype=torch.int32, device=dev)
         counters = torch.zeros((T, 4), dtype=torch.int64, device=dev)
@@ -538,18 +561,16 @@ class Context:
                          glob.data_ptr(), glob.data_ptr() + 8, sol.data_ptr() if want_solution else None, glob.data_ptr() + 16 if want_solution else None)
         stream = torch.cuda.current_stream(dev).cuda_stream
         launches = splits = 0
+        ramp_left = (2 * max(T - 1, 1).bit_length() + 4) if ramp_steps else 0
         while launches < max_launches:
-            if brancher == "enumerate":
-                self._check(self._L.pcp_dfs_forest_device_set_enum(self._h, C.byref(st), VAL_MODES[val], int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit),
-                                                                   C.c_void_p(stream)))
-            else:
-                self._check(self._L.pcp_dfs_forest_device_set(self._h, C.byref(st), int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit), C.c_void_p(stream)))
+            self._check(launch(st, int(ramp_steps) if ramp_left else int(steps_per_launch), stream))
             launches += 1
             g = glob.cpu().tolist()  # (the launch's only synchronisation)
             ts = tree.cpu().numpy()
             fin = (ts[:, 3] & 1) != 0
             if (g[1] & 0xFFFFFFFF) or (node_limit and g[0] >= node_limit) or fin.all():
                 break
+            ramp_left = ramp_left - 1 if (ramp_left and fin.any()) else 0
             if rebalance and fin.any():
                 # finished trees take the oldest open right branch of the trees with the most levels left (pcp_dfs_forest_split_set)
                 left = np.where(fin, 0, ts[:, 0].astype(np.int64) - (ts[:, 3] >> 8))
@@ -568,6 +589,45 @@ class Context:
         return {"nodes": int(cn[:, 0].sum()), "solutions": int(cn[:, 1].sum()), "failed": int(cn[:, 2].sum()), "error": int(cn[:, 3].max()),
                 "finished_trees": int((tree[:, 3] & 1).sum().item()), "splits": splits, "stopped": bool(g[1] & 0xFFFFFFFF), "launches": launches, "total_nodes": int(g[0]),
                 "first_solution": sol.cpu().numpy() if (want_solution and (g[2] & 0xFFFFFFFF)) else None, "per_tree": cn}
+
+    def dfs_forest_set_bnb(self, root_bits, objective, live=None, best0=None, brancher: str = "split", val: str = "middle", steps_per_launch: int = 256,
+                           node_limit: int = 0, level_capacity: int = 0, trail_capacity: int = 0, rebalance: bool = True, info: dict | None = None,
+                           ramp_steps: int = 0, max_launches: int = 1 << 30):
+        """pcp_dfs_forest_device_set_bnb: branch and bound (branch_and_bound.rs:64-84) in the set-mode forest — the loop of dfs_forest_set under
+        either ``brancher``, every node entered with the forest's incumbent (one device word) folded into the set of the objective variable.
+        ``objective`` = (var, "min" | "max").  ``live``: which trees start with a root ([n_trees] bool; None: all); the others start finished
+        and receive work through pcp_dfs_forest_split_set.  ``best0``: a known bound to start from (only solutions that beat it are found).
+        ``ramp_steps``: see _run_forest_set.  Returns the counters of dfs_forest_set (first_solution: None) plus ``best`` (None: no solution and
+        no ``best0``), ``best_solution`` (the row of the lowest tree whose value is ``best``; None when no tree found one) and ``tree_best`` ([n_trees], a tree
+        without a solution: the "no solution yet" value)."""
+        import torch
+        _check_brancher(brancher, val)
+        var, mode = objective
+        if mode not in OBJ_MODES:
+            raise ValueError(f"objective mode must be 'min' or 'max', not {mode!r}")
+        if not 0 <= int(var) < self.n_vars:
+            raise ValueError(f"objective variable {var} out of range")
+        none = no_incumbent(mode)
+        dev = torch.device("cuda", self.device)
+        T = int(np.prod(root_bits.shape)) // (self.n_vars * self.set_words)
+        d_best = torch.full((1,), none if best0 is None else int(best0), dtype=torch.int32, device=dev)
+        tree_best = torch.full((T,), none, dtype=torch.int32, device=dev)
+        tree_row = torch.zeros((T, self.n_vars), dtype=torch.int32, device=dev)
+        obj = ForestObjective(int(var), OBJ_MODES[mode], d_best.data_ptr(), tree_best.data_ptr(), tree_row.data_ptr())
+
+        def launch(st, steps, stream):
+            return self._L.pcp_dfs_forest_device_set_bnb(self._h, C.byref(st), C.byref(obj), 1 if brancher == "enumerate" else 0, VAL_MODES.get(val, VAL_MIDDLE), steps,
+                                                         int(node_limit), C.c_void_p(stream))
+
+        out = self._run_forest_set(root_bits, launch, node_limit=node_limit, steps_per_launch=steps_per_launch, level_capacity=level_capacity,
+                                   trail_capacity=trail_capacity, max_launches=max_launches, info=info, rebalance=rebalance, live=live, ramp_steps=ramp_steps)
+        best = int(d_best.item())
+        tb = tree_best.cpu().numpy()
+        winners = np.nonzero(tb == best)[0] if best != none else []
+        out["tree_best"] = tb
+        out["best"] = None if best == none else best  # (a seeded incumbent nothing beat stays the best known value)
+        out["best_solution"] = tree_row[int(winners[0])].cpu().numpy() if len(winners) else None
+        return out
 
     def stats_reset(self, stream_ptr: int = 0):
         self._check(self._L.pcp_stats_reset(self._h, C.c_void_p(stream_ptr)))
@@ -597,6 +657,13 @@ class Context:
         ms = C.c_float()
         self._check(self._L.pcp_last_kernel_ms(self._h, C.byref(ms)))
         return float(ms.value)
+
+
+def _check_brancher(brancher, val):
+    if brancher not in ("split", "enumerate"):
+        raise ValueError(f"brancher must be 'split' or 'enumerate', not {brancher!r}")
+    if brancher == "enumerate" and val not in VAL_MODES:
+        raise ValueError(f"val must be 'middle' or 'min', not {val!r}")
 
 
 def full_active(n_nodes: int, n_units: int) -> np.ndarray:

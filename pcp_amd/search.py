@@ -489,10 +489,13 @@ class _SetsEnumerate(_Sets):
 
 
 def dfs_enumerate_set(ctx, lb0: np.ndarray, ub0: np.ndarray, base: int, all_solutions: bool = False, node_limit: int = 0, batch: int = 1,
-                      val: str = "middle", implicit: bool = True) -> SearchStats:
+                      val: str = "middle", implicit: bool = True, objective=None) -> SearchStats:
     """dfs_set under Enumerate: the same nodes, propagated by the same ``ctx.propagate_set``, branched by branch_enumerate_set.  With
-    batch = 1 the node order is the reference's left-first DFS under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>."""
+    batch = 1 the node order is the reference's left-first DFS under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>.
+    ``objective``: as in dfs_set — BranchAndBound wraps any brancher (branch_and_bound.rs:64-84), so the bound is folded into a node's
+    set before its propagation exactly as under BinarySplit; this is the host specification of pcp_dfs_forest_device_set_bnb's Enumerate loop."""
     if val not in ("middle", "min"):
         raise ValueError(f"val must be 'middle' or 'min', not {val!r}")
+    obj = _objective(objective)
     root = (interval_bits(np.asarray(lb0), np.asarray(ub0), ctx.set_words, base), None if implicit else full_active(1, ctx.n_units)[0])
-    return _search(_SetsEnumerate(ctx, base, implicit, val), root, all_solutions, node_limit, batch)
+    return _search(_SetsEnumerate(ctx, base, implicit, val), root, all_solutions, node_limit, batch, obj)

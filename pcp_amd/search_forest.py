@@ -72,6 +72,26 @@ def forest_search_set(ctx, lb0, ub0, base: int = 0, node_limit: int = 0, n_trees
     return out
 
 
+def forest_bnb_set(ctx, lb0, ub0, base: int, objective, n_trees: int = 256, ramp_steps: int = 16, steps_per_launch: int = 2048, brancher: str = "split",
+                   val: str = "middle", best0=None, node_limit: int = 0, trail_capacity: int = 0, level_capacity: int = 0, info: dict | None = None) -> dict:
+    """Branch and bound over FDSpace in the forest (branch_and_bound.rs:64-84 around the loop of forest_search_set): minimize / maximize
+    ``objective`` = (var, "min" | "max") below (lb0, ub0).  There is no expansion by DeviceSearch: the single root goes to tree 0, the
+    other trees start idle, and the incumbent is ONE device word from the root to the end (pcp_dfs_forest_device_set_bnb), so both
+    distributors work.  While trees are idle the launches are short (``ramp_steps`` nodes each) and the splits between them hand the
+    oldest open right branches to the idle trees; after that the launches are ``steps_per_launch`` nodes.
+    Returns the dict of Context.dfs_forest_set_bnb: counters, ``best``, ``best_solution``, ``tree_best``."""
+    from .model import interval_bits
+    V, sw = int(ctx.n_vars), int(ctx.set_words)
+    roots = np.zeros((int(n_trees), V, sw), np.uint64)
+    roots[0] = interval_bits(np.asarray(lb0), np.asarray(ub0), sw, base)
+    live = np.zeros(int(n_trees), bool)
+    live[0] = True
+    bound = trail_bound(ctx)
+    return ctx.dfs_forest_set_bnb(roots, objective, live=live, best0=best0, brancher=brancher, val=val, steps_per_launch=steps_per_launch, node_limit=node_limit,
+                                  trail_capacity=trail_capacity or bound, level_capacity=level_capacity or min(bound, 1 << 14), info=info,
+                                  ramp_steps=ramp_steps if n_trees > 1 else 0)
+
+
 def plan_refill(idle, donors):
     """Who sends how many open nodes to whom: ``idle[r]`` trees of rank r have nothing left, ``donors[r]`` trees of rank r have two or
     more open nodes (each can give one).  Only a rank without idle trees gives (one with both fixes itself locally first).  The plan is a
