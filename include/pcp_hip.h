@@ -582,7 +582,9 @@ int32_t pcp_last_plan(const pcp_ctx* ctx, pcp_plan* out);
 
 /* Knobs (all optional; the defaults pick everything from the model and the batch).  key:
  *   "block_threads" 256/512/1024, "nodes_per_block" 0 = auto, "force_path" (0 auto, 1 batch LDS kernel, 2 team kernel),
- *   "team" workgroups per node, "list_cap", "global_dom" 1 = domains stay in HBM (2: 10-bit LDS cells allowed), "dom10" 0 = never use
+ *   "team" workgroups per node, "list_cap" (the changed-variable list of a wake-up round, in LDS; 64..16384, default 2048; the interval kernels
+ *   halve it until the store fits; set mode — pcp_propagate* on sets and pcp_dfs_forest_device_set* — uses min(list_cap, 1024), and a round
+ *   with more changed variables than that sweeps every record instead), "global_dom" 1 = domains stay in HBM (2: 10-bit LDS cells allowed), "dom10" 0 = never use
  *   10-bit cells, "implicit_active" 0 = materialise rows for active_in NULL, "group_level" 0 = no group test, "packed" 0 = never use 16-bit cells,
  *   "word_level" 0 = never use the word-group sweep, "solo_cascade" 0 = a wake-up round with one changed variable is an ordinary round
  *   (1, the default: its records are re-run in place and a bound jumps over the values assigned neighbours forbid), "branch_reverse" 1 = pcp_branch_device writes child k of the batch
