@@ -24,7 +24,8 @@
 extern "C" {
 #endif
 
-#define PCP_ABI_VERSION 8
+#define PCP_ABI_VERSION 8 /* (formula units over set-mode stores came without a new number: no symbol and no layout changed, calls that
+                             were refused with PCP_ERR_UNSUPPORTED now work) */
 
 /* Operand encodings for pcp_prop.var[i]. */
 #define PCP_CONST 0xFFFFFFFFu /* operand is a term::Constant (term/constant.rs:43-68); off[i] = its value   */
@@ -144,11 +145,10 @@ uint32_t pcp_abi_version(void);
  *       Interval<i32> product (bounds only) IS pinned (5 vectors, x_eq_y_mul_z.rs tests) and is what interval mode runs.
  *     - Sum views over sets (term/sum.rs:56-92): Sum::read adds IntervalSets member by member — the same unpinned third-party algebra
  *       (IntervalSet + IntervalSet); the reference's only Sum users (cumulative.rs) are tested over Interval stores.
- *     - the reified layer over sets (Boolean / BooleanNeg / formula units): Disjunction::propagate and is_subsumed are domain-agnostic, but
- *       every reference test of logic/ runs over VStoreFD (Interval); formula leaves would reuse the set-mode leaf filters (XNeqY / XEqY /
- *       XLessY / LT3 / GT3 / EQ3 are offered over sets as plain units), the kernel that combines them (pcp_formula.hip) reads 8-byte
- *       interval cells only.  Refused rather than approximated: bounds-only leaves under a set-valued store would disagree with the
- *       reference on interior values.
+ *     Both also apply to the leaves of a formula unit.  The reified layer itself (Boolean / BooleanNeg / formula units) RUNS over sets: the
+ *     oracle's IntervalSet instantiation pins it, and a leaf's is_subsumed() is decided on the sets (XEqY is False iff they are disjoint).
+ *     The search forest over sets (pcp_dfs_forest_device_set*, pcp_dfs_forest_split_set) evaluates records, not formula trees: it returns
+ *     PCP_ERR_UNSUPPORTED for such a store.
  *   ENUMERATE (search/branching/enumerate.rs:33-60: children `x = v` and `x != v`) needs no engine support in set mode — both children are
  *   exact set operations the caller applies to `bits` before propagating (keep bit v / clear bit v), as pcp_branch_device_set does for
  *   BinarySplit.  In interval mode `x != v` with v inside (lb, ub) is not a domain operation: it stays a per-node propagator — a unit
@@ -169,7 +169,8 @@ int32_t pcp_model_push_sum(pcp_ctx* ctx, uint32_t n_members, const uint32_t* var
  * disjunction.rs:119-131), so a variable may occur in several leaves.  A pop of the unit runs Disjunction::propagate literally: a
  * child is propagated only when every other child is disentailed.  Where the reference would PANIC — Boolean::propagate on a domain
  * without 1 reached through a Conjunction (a non-monotonic update, variable/store.rs:153-156) — the node fails instead.
- * Interval mode only.  Models with formula units run the general formula kernel (pcp_formula.hip). */
+ * Both domain types: over Interval stores the unit runs in pcp_formula.hip, over IntervalSet stores (set mode) in pcp_setform.hip, where
+ * Boolean::propagate clears every other value of the set.  XEqYMulZ leaves and Sum operands stay interval mode only. */
 int32_t pcp_model_push_formula(pcp_ctx* ctx, uint32_t n_nodes, const pcp_fnode* nodes, uint32_t n_leaves, const pcp_prop* leaves);
 /* ≡ FrozenStore::restore's `propagators.truncate(label.0)` (propagation/store.rs:319-323); n_units counts
  * units, not elementary props. */
@@ -575,7 +576,8 @@ typedef struct {
                                1 = the assignment-driven kernel of all-XNeqY models over implicit nodes: the sweep is the adjacency
                                lists of the assigned variables (an XNeqY between two unassigned variables is a no-op, x_neq_y.rs:82-93);
                                2 = the 10-bit-cell kernel of binary models whose store does not fit LDS as pairs (implicit nodes, declared hull);
-                               3 = the formula kernel: a store with formula propagators (pcp_model_push_formula) or Boolean leaves;
+                               3 = the formula kernel: a store with formula propagators (pcp_model_push_formula) or Boolean leaves (set_mode = 1: its
+                                   IntervalSet form, pcp_setform.hip);
                                4 = the small-store kernel: at most 128 slots and 2048 elementary filters, one wavefront per node */
 } pcp_plan;
 int32_t pcp_last_plan(const pcp_ctx* ctx, pcp_plan* out);

@@ -196,12 +196,43 @@ int32_t finalize_model(pcp_ctx* c) {
   return PCP_OK;
 }
 
-// Set mode (IntervalSet<i32> domains): one workgroup per node, the sets in LDS (pcp_set.hip).
+// Set mode (IntervalSet<i32> domains): one workgroup per node, the sets in LDS (pcp_set.hip); a store with formula propagators: one wavefront
+// per node (pcp_setform.hip, plan.path 3).
 int32_t propagate_set_device(pcp_ctx* c, uint32_t n_nodes, const pcp_device_batch* bt, hipStream_t stream) {
   if (!c->hull_set) return fail(c, PCP_ERR_CONTRACT, "set mode needs the hull of the initial domains (pcp_model_set_hull): value v is bit v - lo");
   if ((int64_t)c->hull_hi - c->hull_lo >= (int64_t)c->set_words * 64) return fail(c, PCP_ERR_CONTRACT, "the declared hull does not fit set_words * 64 values");
   if (c->n_vars && (!bt->bits_in || !bt->bits_out || !bt->lb_out || !bt->ub_out)) return fail(c, PCP_ERR_ARG, "set mode: bits_in, bits_out, lb_out and ub_out must not be null");
   const uint32_t P = (uint32_t)c->props.size(), words = (P + 63) / 64, S = c->n_slots;
+  const bool implicit = bt->active_in == nullptr && c->opt_implicit;
+  if (c->has_formulas) {
+    // the reified layer over sets: every unit is evaluated as a tree, one lane per unit, one wavefront per node (pcp_setform.hip); `active`
+    // rows are unit-level there.  Four wavefronts per workgroup; a store too large for four slices runs with fewer.
+    uint32_t fwaves = 4;
+    while (fwaves > 1 && (!lds_bytes_setform(c->n_vars, c->set_words, c->n_units, fwaves) || lds_bytes_setform(c->n_vars, c->set_words, c->n_units, fwaves) > c->lds_max / 2))
+      fwaves /= 2;
+    const size_t flds = lds_bytes_setform(c->n_vars, c->set_words, c->n_units, fwaves);
+    if (!flds || flds > c->lds_max)
+      return fail(c, PCP_ERR_UNSUPPORTED, "a set-mode store with formula propagators must fit one CU's LDS (n_vars * (set_words + 1) * 8 bytes + the changed and unit masks)");
+    SetFormArgs a;
+    memset(&a, 0, sizeof(a));
+    a.m.recs = c->d_recs; a.m.const_val = c->d_const; a.m.n_recs = P; a.m.n_vars = c->n_vars; a.m.n_slots = S;
+    a.nodes = c->d_fnodes; a.unit_root = c->d_unit_root; a.n_units = c->n_units; a.n_nodes = n_nodes;
+    a.set_words = c->set_words; a.base = c->hull_lo;
+    a.bits_in = bt->bits_in; a.bits_out = bt->bits_out; a.lb_out = bt->lb_out; a.ub_out = bt->ub_out;
+    a.active_in = bt->active_in; a.active_out = bt->active_out; a.status = bt->status; a.stats = c->d_stats;
+    LaunchPlan plan;
+    plan.block = 64 * fwaves; plan.lds_bytes = flds;
+    {  // persistent workgroups: what the chip holds at once
+      const uint32_t per_cu = std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)(c->lds_max / flds), 2048u / plan.block));
+      plan.grid = std::min<uint32_t>((n_nodes + fwaves - 1) / fwaves, per_cu * (uint32_t)c->num_cu);
+    }
+    c->last_plan = pcp_plan{1u, 1u, 0u, 0u, 0u, 0u, implicit ? 1u : 0u, 1u, plan.grid, plan.block, (uint32_t)plan.lds_bytes, 0u, 3u};
+    if (c->opt_time_kernels) HIP_TRY(c, hipEventRecord(c->ev_start, stream));
+    HIP_TRY(c, launch_setformfix(a, implicit, plan, stream));
+    if (c->opt_time_kernels) HIP_TRY(c, hipEventRecord(c->ev_stop, stream));
+    c->ev_valid = c->opt_time_kernels != 0;
+    return PCP_OK;
+  }
   uint32_t cap = (uint32_t)std::min<int64_t>(c->opt_list_cap, 1024);
   while (cap > 64 && !lds_bytes_set(c->n_vars, S, c->set_words, cap)) cap /= 2;
   const size_t lds = lds_bytes_set(c->n_vars, S, c->set_words, cap);
@@ -210,7 +241,6 @@ int32_t propagate_set_device(pcp_ctx* c, uint32_t n_nodes, const pcp_device_batc
   memset(&m, 0, sizeof(m));
   m.recs = c->d_recs; m.adj_off = c->d_adj_off; m.adj = c->d_adj; m.adjp = c->have_adjp ? c->d_adjp : nullptr; m.const_val = c->d_const;
   m.n_recs = P; m.n_vars = c->n_vars; m.n_slots = S; m.has_ternary = c->has_ternary; m.uniform_kind = c->uniform_kind; m.max_deg = c->max_deg;
-  const bool implicit = bt->active_in == nullptr && c->opt_implicit;
   const uint32_t unit_words = (c->n_units + 63) / 64;
   const uint64_t* live_in = nullptr;
   uint64_t* live = nullptr;
@@ -361,6 +391,7 @@ int32_t pcp_ctx_create(int32_t hip_device, pcp_ctx** out) {
   if (hip_device < 0 || hip_device >= n) return PCP_ERR_ARG;
   if (hipSetDevice(hip_device) != hipSuccess) return PCP_ERR_HIP;
   pcp_ctx* c = new pcp_ctx();
+  c->set_formulas = true;  // this library has the set-mode formula kernel (pcp_setform.hip): the validators accept formula units over sets
   c->device = hip_device;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, hip_device) == hipSuccess) {
@@ -974,6 +1005,8 @@ static int32_t dfs_forest_set(pcp_ctx* c, const pcp_forest_state* st, const pcp_
   if (!c || !st) return PCP_ERR_ARG;
   if (enumerate && val > PCP_VAL_MIN) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_enum: val must be PCP_VAL_MIDDLE or PCP_VAL_MIN");
   if (!c->set_words) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set needs a set-mode model (pcp_model_reset with set_words > 0)");
+  if (c->has_formulas)
+    return fail(c, PCP_ERR_UNSUPPORTED, "the set-mode search forest evaluates records, not formula trees: stores with formula propagators (Boolean / pcp_model_push_formula) are not supported");
   if (obj) {
     if (obj->var >= c->n_vars) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_bnb: objective variable out of range");
     if (obj->mode > PCP_MAXIMIZE) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_bnb: mode must be PCP_MINIMIZE or PCP_MAXIMIZE");
@@ -1036,6 +1069,8 @@ int32_t pcp_dfs_forest_device_set_bnb(pcp_ctx* c, const pcp_forest_state* st, co
 int32_t pcp_dfs_forest_split_set(pcp_ctx* c, const pcp_forest_state* st, uint32_t n_pairs, const uint32_t* pairs, uint32_t* done, void* hip_stream) {
   if (!c || !st) return PCP_ERR_ARG;
   if (!c->set_words) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_split_set needs a set-mode model");
+  if (c->has_formulas)
+    return fail(c, PCP_ERR_UNSUPPORTED, "the set-mode search forest evaluates records, not formula trees: stores with formula propagators (Boolean / pcp_model_push_formula) are not supported");
   if (!st->n_trees || !st->bits || !st->tree || !st->levels || !st->trail || (n_pairs && (!pairs || !done))) return fail(c, PCP_ERR_ARG, "null buffer");
   HIP_TRY(c, hipSetDevice(c->device));
   SetDfsArgs a;

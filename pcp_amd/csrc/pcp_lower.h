@@ -22,7 +22,11 @@ struct HostModel {
   std::vector<std::vector<uint32_t>> sums;  // term::Sum views: member variables of each term (pcp_model_push_sum)
   uint32_t n_units = 0;
   bool has_groups = false;
-  bool has_formulas = false;            // a formula unit or a Boolean / BooleanNeg leaf: the store runs pcp_formula.hip
+  bool has_formulas = false;            // a formula unit or a Boolean / BooleanNeg leaf: the store runs pcp_formula.hip (set mode: pcp_setform.hip)
+  // The lowering is free of HIP and does not know which kernels its caller links.  Formula units and Boolean / BooleanNeg leaves over
+  // IntervalSet stores (set_words > 0) need the set-mode formula kernel (pcp_setform.hip): a caller that has it says so here — pcp_ctx does —
+  // and the validators then accept them; for any other caller they stay PCP_ERR_UNSUPPORTED, as before that kernel existed.
+  bool set_formulas = false;
 };
 
 // What the launch code asks about a lowered model.

@@ -183,7 +183,7 @@ int32_t lower_formulas(const HostModel& m, size_t P, Lowered& out, std::string& 
 
 int32_t validate_prop(const HostModel& m, const pcp_prop& p, std::string& err) {
   if (p.kind > PCP_NBOOL) return fail(err, PCP_ERR_ARG, "unknown propagator kind");
-  if (p.kind >= PCP_BOOL && m.set_words) return fail(err, PCP_ERR_UNSUPPORTED, "the reified layer (Boolean / formulas) is interval mode only");
+  if (p.kind >= PCP_BOOL && m.set_words && !m.set_formulas) return fail(err, PCP_ERR_UNSUPPORTED, "the reified layer (Boolean / formulas) is interval mode only");
   if (p.group_kind > 2 || p.reserved != 0) return fail(err, PCP_ERR_ARG, "bad group_kind/reserved");
   const int n = arity(p.kind);
   std::vector<uint32_t> seen;  // every variable the propagator subscribes to, Sum members included
@@ -211,7 +211,7 @@ int32_t validate_prop(const HostModel& m, const pcp_prop& p, std::string& err) {
 }
 
 int32_t validate_formula(const HostModel& m, uint32_t n_nodes, const pcp_fnode* nodes, uint32_t n_leaves, const pcp_prop* leaves, std::string& err) {
-  if (m.set_words) return fail(err, PCP_ERR_UNSUPPORTED, "formula propagators are interval mode only");
+  if (m.set_words && !m.set_formulas) return fail(err, PCP_ERR_UNSUPPORTED, "formula propagators are interval mode only");
   std::vector<uint32_t> depth(n_nodes, 0), uses(n_nodes, 0), leaf_uses(n_leaves, 0);
   depth[0] = 1; uses[0] = 1;
   for (uint32_t i = 0; i < n_nodes; ++i) {

@@ -107,6 +107,27 @@ struct FormArgs {
 size_t lds_bytes_formula(uint32_t n_slots, uint32_t n_units, uint32_t waves);  // one slice per wavefront (= per node in flight)
 hipError_t launch_formfix(const FormArgs& a, const LaunchPlan& p, hipStream_t stream);
 
+// The same stores over IntervalSet<i32> domains (set mode): the trees as above, the node's sets as bit words in LDS (pcp_setform.hip).
+struct SetFormArgs {
+  ModelDev m;                // needs recs, const_val, n_vars, n_slots
+  const FNode* nodes;
+  const uint32_t* unit_root;
+  uint32_t n_units;
+  uint32_t n_nodes;
+  uint32_t set_words;        // u64 words per variable
+  int32_t base;              // value v of a variable is bit v - base of its words (the hull's lower bound)
+  const uint64_t* bits_in;   // [n_nodes][n_vars][set_words]
+  uint64_t* bits_out;        // may be bits_in
+  int32_t* lb_out;           // [n_nodes][n_vars] the bounds of the final sets
+  int32_t* ub_out;
+  const uint64_t* active_in; // [n_nodes][ceil(n_units/64)] or null = every unit active
+  uint64_t* active_out;      // or null
+  uint8_t* status;
+  pcp_stats* stats;
+};
+size_t lds_bytes_setform(uint32_t n_vars, uint32_t set_words, uint32_t n_units, uint32_t waves);  // one slice per wavefront; 0 = beyond a CU's LDS
+hipError_t launch_setformfix(const SetFormArgs& a, bool implicit, const LaunchPlan& p, hipStream_t stream);
+
 // Small stores — a few dozen variables, up to a few thousand filters — over explicit `active` rows or implicit nodes: one wavefront per node
 // (pcp_small.hip).
 struct SmallArgs {
