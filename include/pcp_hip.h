@@ -147,8 +147,9 @@ uint32_t pcp_abi_version(void);
  *       (IntervalSet + IntervalSet); the reference's only Sum users (cumulative.rs) are tested over Interval stores.
  *     Both also apply to the leaves of a formula unit.  The reified layer itself (Boolean / BooleanNeg / formula units) RUNS over sets: the
  *     oracle's IntervalSet instantiation pins it, and a leaf's is_subsumed() is decided on the sets (XEqY is False iff they are disjoint).
- *     The search forest over sets (pcp_dfs_forest_device_set*, pcp_dfs_forest_split_set) evaluates records, not formula trees: it returns
- *     PCP_ERR_UNSUPPORTED for such a store.
+ *     The search forest over sets has one entry per kind of store: pcp_dfs_forest_device_set, _set_enum and _set_bnb evaluate records, not
+ *     formula trees, and return PCP_ERR_UNSUPPORTED for a store with formula propagators; pcp_dfs_forest_device_setform and _setform_bnb
+ *     search exactly those stores and return it for a store without one.  pcp_dfs_forest_split_set serves both.
  *   ENUMERATE (search/branching/enumerate.rs:33-60: children `x = v` and `x != v`) needs no engine support in set mode — both children are
  *   exact set operations the caller applies to `bits` before propagating (keep bit v / clear bit v), as pcp_branch_device_set does for
  *   BinarySplit.  In interval mode `x != v` with v inside (lb, ub) is not a domain operation: it stays a per-node propagator — a unit
@@ -526,7 +527,22 @@ typedef struct {
 } pcp_forest_objective;
 int32_t pcp_dfs_forest_device_set_bnb(pcp_ctx* ctx, const pcp_forest_state* st, const pcp_forest_objective* obj, uint32_t enumerate, uint32_t val,
                                       uint32_t n_steps, uint64_t node_limit, void* hip_stream);
-/* Between two calls of pcp_dfs_forest_device_set: finished trees take over work from trees that still have some.  pairs = n_pairs x
+/* The same forest for a store WITH formula propagators (Boolean / BooleanNeg / pcp_model_push_formula units): the loop above under either
+ * distributor (enumerate 0: BinarySplit on MiddleVal; 1: Enumerate on val, PCP_VAL_MIDDLE / PCP_VAL_MIN), every unit evaluated as a tree as
+ * pcp_propagate_device does for such a store.  These stores are small, so a tree is one WAVEFRONT with its node in a slice of a CU's LDS, up to
+ * four trees per 256-thread workgroup: pcp_last_plan reports block = 64 x trees per workgroup, grid = ceil(n_trees / those), lds_bytes, path 3.
+ * State, counters, errors, StopNode, first solution, levels and trail are those of pcp_dfs_forest_device_set, byte for byte, and
+ * pcp_dfs_forest_split_set hands work between the trees.  Unit liveness is derived, never stored: a descent keeps it, a backtrack and the
+ * start of a call set every unit live.  With n_trees = 1 the nodes are the reference's, one for one.
+ * Interval-mode model, enumerate > 1, val > PCP_VAL_MIN: PCP_ERR_ARG.  A store without formula propagators: PCP_ERR_UNSUPPORTED (it is
+ * searched by pcp_dfs_forest_device_set).  A node that does not fit one CU's LDS: PCP_ERR_UNSUPPORTED. */
+int32_t pcp_dfs_forest_device_setform(pcp_ctx* ctx, const pcp_forest_state* st, uint32_t enumerate, uint32_t val, uint32_t n_steps,
+                                      uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream);
+/* Branch and bound around it: pcp_dfs_forest_device_set_bnb for stores with formula propagators — the same objective struct, the same fold
+ * of *best on entering a node, no stop on a solution.  Also PCP_ERR_ARG: var >= n_vars, mode > PCP_MAXIMIZE, a null best / tree_best. */
+int32_t pcp_dfs_forest_device_setform_bnb(pcp_ctx* ctx, const pcp_forest_state* st, const pcp_forest_objective* obj, uint32_t enumerate,
+                                          uint32_t val, uint32_t n_steps, uint64_t node_limit, void* hip_stream);
+/* Between two calls of pcp_dfs_forest_device_set* / _setform*: finished trees take over work from trees that still have some.  pairs = n_pairs x
  * (donor, receiver) tree indices (device uint32).  For every pair whose receiver is finished and whose donor has an open right branch
  * left, the donor's OLDEST open right branch (the subtree nearest its root) becomes the receiver's new root — built from the donor's
  * current node and its trail — and done[pair] = 1; otherwise done[pair] = 0 and nothing changes.  The donor skips that branch when it

@@ -223,6 +223,10 @@ extern "C" {
                                           node_limit: u64, hip_stream: *mut c_void) -> i32; // the same loop under Enumerate (val: PCP_VAL_*)
     pub fn pcp_dfs_forest_device_set_bnb(ctx: *mut pcp_ctx, st: *const pcp_forest_state, obj: *const pcp_forest_objective, enumerate: u32, val: u32,
                                          n_steps: u32, node_limit: u64, hip_stream: *mut c_void) -> i32; // BranchAndBound around either loop
+    pub fn pcp_dfs_forest_device_setform(ctx: *mut pcp_ctx, st: *const pcp_forest_state, enumerate: u32, val: u32, n_steps: u32, stop_on_solution: u32,
+                                         node_limit: u64, hip_stream: *mut c_void) -> i32;
+    pub fn pcp_dfs_forest_device_setform_bnb(ctx: *mut pcp_ctx, st: *const pcp_forest_state, obj: *const pcp_forest_objective, enumerate: u32, val: u32,
+                                             n_steps: u32, node_limit: u64, hip_stream: *mut c_void) -> i32;
     pub fn pcp_dfs_forest_split_set(ctx: *mut pcp_ctx, st: *const pcp_forest_state, n_pairs: u32, pairs: *const u32, done: *mut u32,
                                     hip_stream: *mut c_void) -> i32; // pairs = n_pairs x (donor, receiver), device memory
     pub fn pcp_dfs_device(ctx: *mut pcp_ctx, st: *const pcp_dfs_state, n_steps: u32, stop_on_solution: u32, node_limit: u64,

@@ -1006,7 +1006,7 @@ static int32_t dfs_forest_set(pcp_ctx* c, const pcp_forest_state* st, const pcp_
   if (enumerate && val > PCP_VAL_MIN) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_enum: val must be PCP_VAL_MIDDLE or PCP_VAL_MIN");
   if (!c->set_words) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set needs a set-mode model (pcp_model_reset with set_words > 0)");
   if (c->has_formulas)
-    return fail(c, PCP_ERR_UNSUPPORTED, "the set-mode search forest evaluates records, not formula trees: stores with formula propagators (Boolean / pcp_model_push_formula) are not supported");
+    return fail(c, PCP_ERR_UNSUPPORTED, "pcp_dfs_forest_device_set evaluates records, not formula trees: a store with formula propagators (Boolean / pcp_model_push_formula) is searched by pcp_dfs_forest_device_setform");
   if (obj) {
     if (obj->var >= c->n_vars) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_bnb: objective variable out of range");
     if (obj->mode > PCP_MAXIMIZE) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_bnb: mode must be PCP_MINIMIZE or PCP_MAXIMIZE");
@@ -1066,11 +1066,80 @@ int32_t pcp_dfs_forest_device_set_bnb(pcp_ctx* c, const pcp_forest_state* st, co
   return dfs_forest_set(c, st, obj, enumerate != 0, val, n_steps, 0, node_limit, hip_stream);
 }
 
+// The same loop over a store with formula propagators: one tree per wavefront, the unit step of setformfix_kernel on a trailed node
+// (pcp_setformdfs.hip); obj != nullptr: under branch and bound.  The forest's state is that of dfs_forest_set, so pcp_dfs_forest_split_set
+// serves both.
+static int32_t dfs_forest_setform(pcp_ctx* c, const pcp_forest_state* st, const pcp_forest_objective* obj, uint32_t enumerate, uint32_t val, uint32_t n_steps,
+                                  uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
+  const char* const who = obj ? "pcp_dfs_forest_device_setform_bnb" : "pcp_dfs_forest_device_setform";
+  auto bad = [&](const char* what) { return fail(c, PCP_ERR_ARG, std::string(who) + ": " + what); };
+  if (enumerate > 1) return bad("enumerate must be 0 or 1");
+  if (val > PCP_VAL_MIN) return bad("val must be PCP_VAL_MIDDLE or PCP_VAL_MIN");
+  if (!c->set_words) return bad("needs a set-mode model (pcp_model_reset with set_words > 0)");
+  if (obj) {
+    if (obj->var >= c->n_vars) return bad("objective variable out of range");
+    if (obj->mode > PCP_MAXIMIZE) return bad("mode must be PCP_MINIMIZE or PCP_MAXIMIZE");
+    if (!obj->best || !obj->tree_best) return bad("best and tree_best are required");
+  }
+  if (!c->has_formulas)
+    return fail(c, PCP_ERR_UNSUPPORTED, std::string(who) + " searches stores with formula propagators (Boolean / pcp_model_push_formula): a store of records alone is searched by pcp_dfs_forest_device_set");
+  if (!c->hull_set) return fail(c, PCP_ERR_CONTRACT, "set mode needs the hull of the initial domains (pcp_model_set_hull)");
+  if ((int64_t)c->hull_hi - c->hull_lo >= (int64_t)c->set_words * 64) return fail(c, PCP_ERR_CONTRACT, "the declared hull does not fit set_words * 64 values");
+  if (!st->n_trees || !st->bits || !st->tree || !st->levels || !st->trail || !st->counters || !st->total_nodes || !st->stop || !st->level_capacity || !st->trail_capacity)
+    return bad("null buffer / zero capacity");
+  if (!obj && (st->first_solution == nullptr) != (st->solution_flag == nullptr)) return bad("first_solution and solution_flag go together");
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  HIP_TRY(c, hipSetDevice(c->device));
+  { const int32_t rcf = finalize_model(c); if (rcf) return rcf; }
+  // up to four trees per 256-thread workgroup; a store whose four slices exceed half a CU's LDS runs with two or one
+  uint32_t waves = 4;
+  while (waves > 1 && (!lds_bytes_setformdfs(c->n_vars, c->set_words, c->n_units, waves) || lds_bytes_setformdfs(c->n_vars, c->set_words, c->n_units, waves) > c->lds_max / 2))
+    waves /= 2;
+  const size_t lds = lds_bytes_setformdfs(c->n_vars, c->set_words, c->n_units, waves);
+  if (!lds || lds > c->lds_max)
+    return fail(c, PCP_ERR_UNSUPPORTED, std::string(who) + ": a tree's node must fit one CU's LDS (n_vars * (set_words + 1) * 8 bytes + the changed, touched and unit masks)");
+  SetFormDfsArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  SetDfsArgs& a = fa.d;
+  a.m.recs = c->d_recs; a.m.const_val = c->d_const; a.m.n_recs = (uint32_t)c->props.size(); a.m.n_vars = c->n_vars; a.m.n_slots = c->n_slots;
+  fa.nodes = c->d_fnodes; fa.unit_root = c->d_unit_root; fa.n_units = c->n_units;
+  a.set_words = c->set_words; a.base = c->hull_lo;
+  a.n_trees = st->n_trees; a.level_cap = st->level_capacity; a.trail_cap = st->trail_capacity; a.n_steps = n_steps; a.stop_on_solution = stop_on_solution;
+  a.node_limit = node_limit;
+  a.bits = st->bits; a.tree = st->tree; a.levels = reinterpret_cast<uint4*>(st->levels); a.trail = reinterpret_cast<uint4*>(st->trail);
+  a.counters = reinterpret_cast<unsigned long long*>(st->counters); a.total_nodes = reinterpret_cast<unsigned long long*>(st->total_nodes);
+  a.stop = st->stop; a.first_solution = st->first_solution; a.solution_flag = st->solution_flag; a.stats = c->d_stats;
+  a.val_mode = val;
+  if (obj) {  // branch and bound runs to the end and keeps a row per tree instead of the forest's first solution
+    a.stop_on_solution = 0; a.first_solution = nullptr; a.solution_flag = nullptr;
+    a.obj_var = obj->var; a.obj_mode = obj->mode; a.obj_best = obj->best; a.tree_best = obj->tree_best; a.tree_row = obj->tree_row;
+  }
+  if (!n_steps) return PCP_OK;
+  LaunchPlan plan;
+  plan.block = 64 * waves; plan.lds_bytes = lds; plan.grid = (st->n_trees + waves - 1) / waves;
+  c->last_plan = pcp_plan{waves, 1u, 0u, 0u, 0u, 0u, 1u, 1u, plan.grid, plan.block, (uint32_t)lds, 0u, 3u};
+  if (c->opt_time_kernels) HIP_TRY(c, hipEventRecord(c->ev_start, stream));
+  HIP_TRY(c, launch_setformdfs(fa, enumerate != 0, obj != nullptr, plan, stream));
+  if (c->opt_time_kernels) HIP_TRY(c, hipEventRecord(c->ev_stop, stream));
+  c->ev_valid = c->opt_time_kernels != 0;
+  return PCP_OK;
+}
+
+int32_t pcp_dfs_forest_device_setform(pcp_ctx* c, const pcp_forest_state* st, uint32_t enumerate, uint32_t val, uint32_t n_steps, uint32_t stop_on_solution,
+                                      uint64_t node_limit, void* hip_stream) {
+  if (!c || !st) return c ? fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_setform: null state") : PCP_ERR_ARG;
+  return dfs_forest_setform(c, st, nullptr, enumerate, val, n_steps, stop_on_solution, node_limit, hip_stream);
+}
+
+int32_t pcp_dfs_forest_device_setform_bnb(pcp_ctx* c, const pcp_forest_state* st, const pcp_forest_objective* obj, uint32_t enumerate, uint32_t val, uint32_t n_steps,
+                                          uint64_t node_limit, void* hip_stream) {
+  if (!c || !st || !obj) return c ? fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_setform_bnb: null state / objective") : PCP_ERR_ARG;
+  return dfs_forest_setform(c, st, obj, enumerate, val, n_steps, 0, node_limit, hip_stream);
+}
+
 int32_t pcp_dfs_forest_split_set(pcp_ctx* c, const pcp_forest_state* st, uint32_t n_pairs, const uint32_t* pairs, uint32_t* done, void* hip_stream) {
   if (!c || !st) return PCP_ERR_ARG;
   if (!c->set_words) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_split_set needs a set-mode model");
-  if (c->has_formulas)
-    return fail(c, PCP_ERR_UNSUPPORTED, "the set-mode search forest evaluates records, not formula trees: stores with formula propagators (Boolean / pcp_model_push_formula) are not supported");
   if (!st->n_trees || !st->bits || !st->tree || !st->levels || !st->trail || (n_pairs && (!pairs || !done))) return fail(c, PCP_ERR_ARG, "null buffer");
   HIP_TRY(c, hipSetDevice(c->device));
   SetDfsArgs a;

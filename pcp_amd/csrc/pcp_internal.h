@@ -140,6 +140,8 @@ struct SetDfsArgs {
 // a level's flags (levels[..].w): its right branch went to another tree (setdfs_split_kernel); its distributor is Enumerate (x = v, then
 // x != v) instead of BinarySplit (x <= v, then x > v)
 constexpr uint32_t kLevelGiven = 1u, kLevelEnum = 2u;
+constexpr uint32_t kDfsFull = 0xFFFFFFFFu;  // tree[..][2]: the current node has not been propagated at all (PCP_DFS_FULL)
+constexpr uint32_t kDfsChunk = 8;            // nodes a tree reserves from the forest's counter at a time
 size_t lds_bytes_set_dfs(uint32_t n_vars, uint32_t n_slots, uint32_t set_words, uint32_t list_cap);
 hipError_t launch_setdfs(const SetDfsArgs& a, bool enumerate, bool bnb, hipStream_t stream);
 hipError_t launch_setdfs_split(const SetDfsArgs& a, uint32_t n_pairs, const uint32_t* pairs, uint32_t* done, hipStream_t stream);

@@ -128,6 +128,18 @@ struct SetFormArgs {
 size_t lds_bytes_setform(uint32_t n_vars, uint32_t set_words, uint32_t n_units, uint32_t waves);  // one slice per wavefront; 0 = beyond a CU's LDS
 hipError_t launch_setformfix(const SetFormArgs& a, bool implicit, const LaunchPlan& p, hipStream_t stream);
 
+// The search loop over such a store on the device: one tree per WAVEFRONT, the current node in its LDS slice, an undo trail in HBM
+// (pcp_setformdfs.hip).  The forest's state, levels, trail and objective are setdfs_kernel's (SetDfsArgs `d`; of d.m: recs, const_val,
+// n_recs, n_vars, n_slots), so setdfs_split_kernel serves this forest as it is.
+struct SetFormDfsArgs {
+  SetDfsArgs d;
+  const FNode* nodes;
+  const uint32_t* unit_root;
+  uint32_t n_units;
+};
+size_t lds_bytes_setformdfs(uint32_t n_vars, uint32_t set_words, uint32_t n_units, uint32_t waves);  // one slice per tree; 0 = beyond a CU's LDS
+hipError_t launch_setformdfs(const SetFormDfsArgs& a, bool enumerate, bool bnb, const LaunchPlan& p, hipStream_t stream);
+
 // Small stores — a few dozen variables, up to a few thousand filters — over explicit `active` rows or implicit nodes: one wavefront per node
 // (pcp_small.hip).
 struct SmallArgs {

@@ -412,28 +412,8 @@ __global__ void __launch_bounds__(kSetThreads) set_derive_active_kernel(const Se
 // every other propagator is a no-op until one of its variables changes); a root (pending == kDfsFull) runs the sweep of setfix_kernel.
 // Exactly the reference's left-first order within a tree; several trees = the subtrees of an open-node frontier, each on its CU.
 // ------------------------------------------------------------------------------------------------
-constexpr uint32_t kDfsFull = 0xFFFFFFFFu;
-constexpr uint32_t kDfsChunk = 8;  // nodes a tree reserves from the forest's counter at a time
-
 struct SetDfsCarve { SetCarve c; size_t touched, adjo, total; };
 
-// The member of one variable's set (words w[0 .. sw), value = base + bit index) nearest to m, m - d before m + d, as a key for a minimum:
-// 2 d for the nearest member <= m, 2 d + 1 for the nearest >= m (m itself: 0).  A word is reduced at once — the highest member <= m and the
-// lowest member >= m of the masked word —, never value by value; the caller takes the minimum over the words.  ~0: no member in this word.
-__device__ __forceinline__ unsigned long long nearest_member_key(unsigned long long w, long long word_lo, long long m) {
-  const long long t = m - word_lo;  // m's bit in this word, if 0 <= t < 64
-  const unsigned long long le = t < 0 ? 0ull : (t >= 63 ? ~0ull : ((2ull << t) - 1ull));  // the values <= m
-  const unsigned long long ge = t <= 0 ? ~0ull : (t >= 64 ? 0ull : (~0ull << t));         // the values >= m
-  unsigned long long key = ~0ull;
-  const unsigned long long below = w & le, above = w & ge;
-  if (below) key = 2ull * (unsigned long long)(m - (word_lo + 63 - __clzll((long long)below)));
-  if (above) key = min(key, 2ull * (unsigned long long)(word_lo + (__ffsll((long long)above) - 1) - m) + 1ull);
-  return key;
-}
-__device__ __forceinline__ long long nearest_member_value(unsigned long long key, long long m) {
-  const long long d = (long long)(key >> 1);
-  return (key & 1ull) ? m + d : m - d;
-}
 __host__ __device__ inline SetDfsCarve set_dfs_carve(uint32_t V, uint32_t S, uint32_t sw, uint32_t cap) {
   SetDfsCarve d;
   d.c = set_carve(V, S, sw, cap);

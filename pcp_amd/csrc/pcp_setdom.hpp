@@ -1,6 +1,7 @@
 // pcp_setdom.hpp — IntervalSet<i32> domains as bitsets in LDS: the domain object the set-mode kernels narrow (SetDomT), the elementary
-// filters on it (eval_set) and the bounds of a set from its words (scan_bounds).  Shared by the kernels of pcp_set.hip (one workgroup per
-// node, plain stores) and pcp_setform.hip (one wavefront per node, stores with formula propagators).  Device code only.
+// filters on it (eval_set), the bounds of a set from its words (scan_bounds) and the member of a set nearest to a value (Enumerate's
+// value rule).  Shared by the kernels of pcp_set.hip (one workgroup per node, plain stores) and of pcp_setform.hip / pcp_setformdfs.hip
+// (one wavefront per node or per tree, stores with formula propagators).  Device code only.
 #pragma once
 #include "pcp_internal.h"
 
@@ -201,6 +202,24 @@ __device__ __forceinline__ int2 scan_bounds(const unsigned long long* w, uint32_
   for (uint32_t k = sw; k-- > 0;)
     if (w[k]) { hi = base + (int)k * 64 + 63 - (int)__builtin_clzll(w[k]); break; }
   return make_int2(lo, hi);
+}
+
+// The member of one variable's set (words w[0 .. sw), value = base + bit index) nearest to m, m - d before m + d, as a key for a minimum:
+// 2 d for the nearest member <= m, 2 d + 1 for the nearest >= m (m itself: 0).  A word is reduced at once — the highest member <= m and the
+// lowest member >= m of the masked word —, never value by value; the caller takes the minimum over the words.  ~0: no member in this word.
+__device__ __forceinline__ unsigned long long nearest_member_key(unsigned long long w, long long word_lo, long long m) {
+  const long long t = m - word_lo;  // m's bit in this word, if 0 <= t < 64
+  const unsigned long long le = t < 0 ? 0ull : (t >= 63 ? ~0ull : ((2ull << t) - 1ull));  // the values <= m
+  const unsigned long long ge = t <= 0 ? ~0ull : (t >= 64 ? 0ull : (~0ull << t));         // the values >= m
+  unsigned long long key = ~0ull;
+  const unsigned long long below = w & le, above = w & ge;
+  if (below) key = 2ull * (unsigned long long)(m - (word_lo + 63 - __clzll((long long)below)));
+  if (above) key = min(key, 2ull * (unsigned long long)(word_lo + (__ffsll((long long)above) - 1) - m) + 1ull);
+  return key;
+}
+__device__ __forceinline__ long long nearest_member_value(unsigned long long key, long long m) {
+  const long long d = (long long)(key >> 1);
+  return (key & 1ull) ? m + d : m - d;
 }
 
 }  // namespace

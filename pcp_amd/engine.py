@@ -25,7 +25,7 @@ ERRORS = {-1: "PCP_ERR_ARG", -2: "PCP_ERR_CONTRACT", -3: "PCP_ERR_HIP", -4: "PCP
 ABI_SYMBOLS = [
     "pcp_ctx_create", "pcp_ctx_destroy", "pcp_last_error", "pcp_strerror", "pcp_abi_version",
     "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull",
-    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
+    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
 ]
 
 
@@ -153,6 +153,8 @@ def load_library():
     L.pcp_dfs_forest_device_set.argtypes = [vp, C.POINTER(ForestState), u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_set_enum.argtypes = [vp, C.POINTER(ForestState), u32, u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_set_bnb.argtypes = [vp, C.POINTER(ForestState), C.POINTER(ForestObjective), u32, u32, u32, C.c_uint64, vp]
+    L.pcp_dfs_forest_device_setform.argtypes = [vp, C.POINTER(ForestState), u32, u32, u32, u32, C.c_uint64, vp]
+    L.pcp_dfs_forest_device_setform_bnb.argtypes = [vp, C.POINTER(ForestState), C.POINTER(ForestObjective), u32, u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_split_set.argtypes = [vp, C.POINTER(ForestState), u32, vp, vp, vp]
     L.pcp_dfs_forest_device.argtypes = [vp, C.POINTER(DfsState), u32, u32, u32, C.c_uint64, vp]
     L.pcp_stats_reset.argtypes = [vp, vp]
@@ -162,7 +164,7 @@ def load_library():
     L.pcp_last_plan.argtypes = [vp, C.POINTER(PcpPlan)]
     L.pcp_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
     for f in ("pcp_ctx_create", "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull", "pcp_model_set_hull",
-              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
+              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
         getattr(L, f).restype = i32
     _lib = L
     return L
@@ -525,6 +527,21 @@ class Context:
         return self._run_forest_set(root_bits, launch, node_limit=node_limit, steps_per_launch=steps_per_launch, level_capacity=level_capacity,
                                     trail_capacity=trail_capacity, max_launches=max_launches, want_solution=want_solution, info=info, rebalance=rebalance)
 
+    def dfs_forest_setform(self, root_bits, stop_on_solution: bool = False, node_limit: int = 0, steps_per_launch: int = 256,
+                           level_capacity: int = 0, trail_capacity: int = 0, max_launches: int = 1 << 30, want_solution: bool = True,
+                           info: dict | None = None, rebalance: bool = True, brancher: str = "split", val: str = "middle"):
+        """pcp_dfs_forest_device_setform: dfs_forest_set for a store WITH formula propagators (Boolean / formula units) — the same loop, state
+        and result dict, one tree per wavefront with its node in a slice of a CU's LDS (last_plan: block = 64 x trees per workgroup, path 3).
+        A store without formula propagators raises PCP_ERR_UNSUPPORTED (dfs_forest_set searches it), as dfs_forest_set does for one with."""
+        _check_brancher(brancher, val)
+
+        def launch(st, steps, stream):
+            return self._L.pcp_dfs_forest_device_setform(self._h, C.byref(st), 1 if brancher == "enumerate" else 0, VAL_MODES.get(val, VAL_MIDDLE), steps,
+                                                         int(bool(stop_on_solution)), int(node_limit), C.c_void_p(stream))
+
+        return self._run_forest_set(root_bits, launch, node_limit=node_limit, steps_per_launch=steps_per_launch, level_capacity=level_capacity,
+                                    trail_capacity=trail_capacity, max_launches=max_launches, want_solution=want_solution, info=info, rebalance=rebalance)
+
     def _run_forest_set(self, root_bits, launch, node_limit: int = 0, steps_per_launch: int = 256, level_capacity: int = 0, trail_capacity: int = 0,
                         max_launches: int = 1 << 30, want_solution: bool = False, info: dict | None = None, rebalance: bool = True, live=None,
                         ramp_steps: int = 0):
@@ -592,7 +609,7 @@ class Context:
 
     def dfs_forest_set_bnb(self, root_bits, objective, live=None, best0=None, brancher: str = "split", val: str = "middle", steps_per_launch: int = 256,
                            node_limit: int = 0, level_capacity: int = 0, trail_capacity: int = 0, rebalance: bool = True, info: dict | None = None,
-                           ramp_steps: int = 0, max_launches: int = 1 << 30):
+                           ramp_steps: int = 0, max_launches: int = 1 << 30, _entry: str = "pcp_dfs_forest_device_set_bnb"):
         """pcp_dfs_forest_device_set_bnb: branch and bound (branch_and_bound.rs:64-84) in the set-mode forest — the loop of dfs_forest_set under
         either ``brancher``, every node entered with the forest's incumbent (one device word) folded into the set of the objective variable.
         ``objective`` = (var, "min" | "max").  ``live``: which trees start with a root ([n_trees] bool; None: all); the others start finished
@@ -616,8 +633,8 @@ class Context:
         obj = ForestObjective(int(var), OBJ_MODES[mode], d_best.data_ptr(), tree_best.data_ptr(), tree_row.data_ptr())
 
         def launch(st, steps, stream):
-            return self._L.pcp_dfs_forest_device_set_bnb(self._h, C.byref(st), C.byref(obj), 1 if brancher == "enumerate" else 0, VAL_MODES.get(val, VAL_MIDDLE), steps,
-                                                         int(node_limit), C.c_void_p(stream))
+            return getattr(self._L, _entry)(self._h, C.byref(st), C.byref(obj), 1 if brancher == "enumerate" else 0, VAL_MODES.get(val, VAL_MIDDLE), steps,
+                                            int(node_limit), C.c_void_p(stream))
 
         out = self._run_forest_set(root_bits, launch, node_limit=node_limit, steps_per_launch=steps_per_launch, level_capacity=level_capacity,
                                    trail_capacity=trail_capacity, max_launches=max_launches, info=info, rebalance=rebalance, live=live, ramp_steps=ramp_steps)
@@ -628,6 +645,11 @@ class Context:
         out["best"] = None if best == none else best  # (a seeded incumbent nothing beat stays the best known value)
         out["best_solution"] = tree_row[int(winners[0])].cpu().numpy() if len(winners) else None
         return out
+
+    def dfs_forest_setform_bnb(self, root_bits, objective, **kw):
+        """pcp_dfs_forest_device_setform_bnb: dfs_forest_set_bnb for a store WITH formula propagators (see dfs_forest_setform) — the same
+        arguments and result dict."""
+        return self.dfs_forest_set_bnb(root_bits, objective, _entry="pcp_dfs_forest_device_setform_bnb", **kw)
 
     def stats_reset(self, stream_ptr: int = 0):
         self._check(self._L.pcp_stats_reset(self._h, C.c_void_p(stream_ptr)))

@@ -42,20 +42,24 @@ def trail_bound(ctx) -> int:
 
 
 def forest_search_set(ctx, lb0, ub0, base: int = 0, node_limit: int = 0, n_trees: int = 512, steps_per_launch: int = 2048, rank: int = 0, world: int = 1,
-                      trail_capacity: int = 0, level_capacity: int = 0, info: dict | None = None, brancher: str = "split", val: str = "middle") -> dict:
+                      trail_capacity: int = 0, level_capacity: int = 0, info: dict | None = None, brancher: str = "split", val: str = "middle",
+                      formulas: bool = False, rebalance: bool = True) -> dict:
     """All solutions of the space below (lb0, ub0) — or the first `node_limit` nodes of this rank's share of it.
     brancher / val: the distributor of the expansion AND of the trees ("enumerate": Enumerate on MiddleVal or MinVal), so that their union is
     one tree of that distributor.
+    formulas: the store holds formula propagators (Boolean / formula units): the trees run in Context.dfs_forest_setform, one per wavefront,
+    instead of dfs_forest_set (the expansion runs such stores as it is).
     trail_capacity / level_capacity 0 = derived from the model (trail_bound): every trail entry takes at least one value out of one
     set and is popped before that value can come back, so a tree's trail never holds more entries than the root has values —
     n_vars * set_words * 64 at most.  (N-queens-1000: 1 024 000 entries = 16 MB per tree; a 100-variable model: 100 KB.)
-    Returns dict(nodes, solutions, failed, error, seeded_nodes, trees, launches); with world > 1 the expansion's counters are
+    rebalance: between launches finished trees take work from the others (pcp_dfs_forest_split_set).
+    Returns dict(nodes, solutions, failed, error, seeded_nodes, trees, launches, finished_trees, splits); with world > 1 the expansion's counters are
     reported by rank 0 only, so that a sum over the ranks counts every node once."""
     roots, st = seed_roots(ctx, lb0, ub0, base, n_trees * world, brancher=brancher, val=val)
     mine = roots[rank::world].contiguous()
     out = {"seeded_nodes": st.num_nodes if rank == 0 else 0, "trees": int(mine.shape[0]), "launches": 0,
            "nodes": st.num_nodes if rank == 0 else 0, "solutions": st.num_solution if rank == 0 else 0, "failed": st.num_failed_node if rank == 0 else 0,
-           "error": 0}
+           "error": 0, "finished_trees": 0, "splits": 0}
     budget = 0
     if node_limit:
         budget = share_of_budget(node_limit, st.num_nodes, rank, world)
@@ -64,21 +68,23 @@ def forest_search_set(ctx, lb0, ub0, base: int = 0, node_limit: int = 0, n_trees
     if mine.shape[0] == 0:
         return out
     bound = trail_bound(ctx)
-    r = ctx.dfs_forest_set(mine, node_limit=budget, steps_per_launch=steps_per_launch, trail_capacity=trail_capacity or bound,
-                           level_capacity=level_capacity or min(bound, 1 << 14),
-                           want_solution=False, info=info, brancher=brancher, val=val)
+    run = ctx.dfs_forest_setform if formulas else ctx.dfs_forest_set
+    r = run(mine, node_limit=budget, steps_per_launch=steps_per_launch, trail_capacity=trail_capacity or bound, level_capacity=level_capacity or min(bound, 1 << 14),
+            want_solution=False, info=info, brancher=brancher, val=val, rebalance=rebalance)
     out["nodes"] += r["nodes"]; out["solutions"] += r["solutions"]; out["failed"] += r["failed"]
-    out["error"] = r["error"]; out["launches"] = r["launches"]
+    out["error"] = r["error"]; out["launches"] = r["launches"]; out["finished_trees"] = r["finished_trees"]; out["splits"] = r["splits"]
     return out
 
 
 def forest_bnb_set(ctx, lb0, ub0, base: int, objective, n_trees: int = 256, ramp_steps: int = 16, steps_per_launch: int = 2048, brancher: str = "split",
-                   val: str = "middle", best0=None, node_limit: int = 0, trail_capacity: int = 0, level_capacity: int = 0, info: dict | None = None) -> dict:
+                   val: str = "middle", best0=None, node_limit: int = 0, trail_capacity: int = 0, level_capacity: int = 0, info: dict | None = None,
+                   formulas: bool = False) -> dict:
     """Branch and bound over FDSpace in the forest (branch_and_bound.rs:64-84 around the loop of forest_search_set): minimize / maximize
     ``objective`` = (var, "min" | "max") below (lb0, ub0).  There is no expansion by DeviceSearch: the single root goes to tree 0, the
     other trees start idle, and the incumbent is ONE device word from the root to the end (pcp_dfs_forest_device_set_bnb), so both
     distributors work.  While trees are idle the launches are short (``ramp_steps`` nodes each) and the splits between them hand the
     oldest open right branches to the idle trees; after that the launches are ``steps_per_launch`` nodes.
+    formulas: the store holds formula propagators: Context.dfs_forest_setform_bnb instead of dfs_forest_set_bnb.
     Returns the dict of Context.dfs_forest_set_bnb: counters, ``best``, ``best_solution``, ``tree_best``."""
     from .model import interval_bits
     V, sw = int(ctx.n_vars), int(ctx.set_words)
@@ -87,9 +93,10 @@ def forest_bnb_set(ctx, lb0, ub0, base: int, objective, n_trees: int = 256, ramp
     live = np.zeros(int(n_trees), bool)
     live[0] = True
     bound = trail_bound(ctx)
-    return ctx.dfs_forest_set_bnb(roots, objective, live=live, best0=best0, brancher=brancher, val=val, steps_per_launch=steps_per_launch, node_limit=node_limit,
-                                  trail_capacity=trail_capacity or bound, level_capacity=level_capacity or min(bound, 1 << 14), info=info,
-                                  ramp_steps=ramp_steps if n_trees > 1 else 0)
+    run = ctx.dfs_forest_setform_bnb if formulas else ctx.dfs_forest_set_bnb
+    return run(roots, objective, live=live, best0=best0, brancher=brancher, val=val, steps_per_launch=steps_per_launch, node_limit=node_limit,
+               trail_capacity=trail_capacity or bound, level_capacity=level_capacity or min(bound, 1 << 14), info=info,
+               ramp_steps=ramp_steps if n_trees > 1 else 0)
 
 
 def plan_refill(idle, donors):
