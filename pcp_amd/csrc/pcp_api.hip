@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -998,55 +999,82 @@ static int32_t dfs_enqueue_steps(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n
   return rc;
 }
 
+// The state half of SetDfsArgs: the store's shape and the forest's buffers (all that setdfs_split_kernel reads).
+static void fill_forest_state(SetDfsArgs& a, const pcp_ctx* c, const pcp_forest_state* st) {
+  memset(&a, 0, sizeof(a));
+  a.m.n_vars = c->n_vars; a.m.n_slots = c->n_slots;
+  a.set_words = c->set_words; a.base = c->hull_lo;
+  a.n_trees = st->n_trees; a.level_cap = st->level_capacity; a.trail_cap = st->trail_capacity;
+  a.bits = st->bits; a.tree = st->tree; a.levels = reinterpret_cast<uint4*>(st->levels); a.trail = reinterpret_cast<uint4*>(st->trail);
+  a.counters = reinterpret_cast<unsigned long long*>(st->counters); a.total_nodes = reinterpret_cast<unsigned long long*>(st->total_nodes);
+  a.stop = st->stop; a.first_solution = st->first_solution; a.solution_flag = st->solution_flag;
+}
+
+// What a launch of either set-mode search forest checks and fills, `who` being the entry point: the selector, the set-mode model, the
+// objective, the store (`wrong_store`: this entry's refusal of the store at hand, or null), the hull and the state's buffers; then the
+// model is finalised and `a` gets everything but the model's tables and list_cap.  obj != nullptr: under branch and bound, which runs to
+// the end and keeps a row per tree instead of the forest's first solution.
+static int32_t forest_set_args(pcp_ctx* c, const char* who, const pcp_forest_state* st, const pcp_forest_objective* obj, uint32_t val, const char* wrong_store,
+                               uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, SetDfsArgs& a) {
+  auto bad = [&](const char* what) { return fail(c, PCP_ERR_ARG, std::string(who) + ": " + what); };
+  if (val > PCP_VAL_MIN) return bad("val must be PCP_VAL_MIDDLE or PCP_VAL_MIN");
+  if (!c->set_words) return bad("needs a set-mode model (pcp_model_reset with set_words > 0)");
+  if (obj) {
+    if (obj->var >= c->n_vars) return bad("objective variable out of range");
+    if (obj->mode > PCP_MAXIMIZE) return bad("mode must be PCP_MINIMIZE or PCP_MAXIMIZE");
+    if (!obj->best || !obj->tree_best) return bad("best and tree_best are required");
+  }
+  if (wrong_store) return fail(c, PCP_ERR_UNSUPPORTED, std::string(who) + wrong_store);
+  if (!c->hull_set) return fail(c, PCP_ERR_CONTRACT, "set mode needs the hull of the initial domains (pcp_model_set_hull)");
+  if ((int64_t)c->hull_hi - c->hull_lo >= (int64_t)c->set_words * 64) return fail(c, PCP_ERR_CONTRACT, "the declared hull does not fit set_words * 64 values");
+  if (!st->n_trees || !st->bits || !st->tree || !st->levels || !st->trail || !st->counters || !st->total_nodes || !st->stop || !st->level_capacity || !st->trail_capacity)
+    return bad("null buffer / zero capacity");
+  if (!obj && (st->first_solution == nullptr) != (st->solution_flag == nullptr)) return bad("first_solution and solution_flag go together");
+  HIP_TRY(c, hipSetDevice(c->device));
+  { const int32_t rcf = finalize_model(c); if (rcf) return rcf; }
+  fill_forest_state(a, c, st);
+  a.m.recs = c->d_recs; a.m.const_val = c->d_const; a.m.n_recs = (uint32_t)c->props.size();
+  a.n_steps = n_steps; a.stop_on_solution = stop_on_solution; a.node_limit = node_limit;
+  a.stats = c->d_stats;
+  a.val_mode = val;
+  if (obj) {
+    a.stop_on_solution = 0; a.first_solution = nullptr; a.solution_flag = nullptr;
+    a.obj_var = obj->var; a.obj_mode = obj->mode; a.obj_best = obj->best; a.tree_best = obj->tree_best; a.tree_row = obj->tree_row;
+  }
+  return PCP_OK;
+}
+
+// One launch between the context's timing events.
+static int32_t forest_launch(pcp_ctx* c, hipStream_t stream, const std::function<hipError_t()>& launch) {
+  if (c->opt_time_kernels) HIP_TRY(c, hipEventRecord(c->ev_start, stream));
+  HIP_TRY(c, launch());
+  if (c->opt_time_kernels) HIP_TRY(c, hipEventRecord(c->ev_stop, stream));
+  c->ev_valid = c->opt_time_kernels != 0;
+  return PCP_OK;
+}
+
 // The search loop over FDSpace under either distributor: BinarySplit on MiddleVal (pcp_dfs_forest_device_set) or Enumerate on `val`;
 // obj != nullptr: under branch and bound (pcp_dfs_forest_device_set_bnb).
 static int32_t dfs_forest_set(pcp_ctx* c, const pcp_forest_state* st, const pcp_forest_objective* obj, bool enumerate, uint32_t val, uint32_t n_steps,
                               uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
   if (!c || !st) return PCP_ERR_ARG;
-  if (enumerate && val > PCP_VAL_MIN) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_enum: val must be PCP_VAL_MIDDLE or PCP_VAL_MIN");
-  if (!c->set_words) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set needs a set-mode model (pcp_model_reset with set_words > 0)");
-  if (c->has_formulas)
-    return fail(c, PCP_ERR_UNSUPPORTED, "pcp_dfs_forest_device_set evaluates records, not formula trees: a store with formula propagators (Boolean / pcp_model_push_formula) is searched by pcp_dfs_forest_device_setform");
-  if (obj) {
-    if (obj->var >= c->n_vars) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_bnb: objective variable out of range");
-    if (obj->mode > PCP_MAXIMIZE) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_bnb: mode must be PCP_MINIMIZE or PCP_MAXIMIZE");
-    if (!obj->best || !obj->tree_best) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_set_bnb: best and tree_best are required");
-  }
-  if (!c->hull_set) return fail(c, PCP_ERR_CONTRACT, "set mode needs the hull of the initial domains (pcp_model_set_hull)");
-  if ((int64_t)c->hull_hi - c->hull_lo >= (int64_t)c->set_words * 64) return fail(c, PCP_ERR_CONTRACT, "the declared hull does not fit set_words * 64 values");
-  if (!st->n_trees || !st->bits || !st->tree || !st->levels || !st->trail || !st->counters || !st->total_nodes || !st->stop || !st->level_capacity || !st->trail_capacity)
-    return fail(c, PCP_ERR_ARG, "null buffer / zero capacity");
-  if (!obj && (st->first_solution == nullptr) != (st->solution_flag == nullptr)) return fail(c, PCP_ERR_ARG, "first_solution and solution_flag go together");
-  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
-  HIP_TRY(c, hipSetDevice(c->device));
-  { const int32_t rcf = finalize_model(c); if (rcf) return rcf; }
-  const uint32_t P = (uint32_t)c->props.size(), S = c->n_slots;
-  uint32_t cap = (uint32_t)std::min<int64_t>(c->opt_list_cap, 1024);
-  while (cap > 64 && !lds_bytes_set_dfs(c->n_vars, S, c->set_words, cap)) cap /= 2;
-  const size_t lds = lds_bytes_set_dfs(c->n_vars, S, c->set_words, cap);
-  if (!lds || lds > c->lds_max) return fail(c, PCP_ERR_UNSUPPORTED, "set-mode variable store does not fit one CU's LDS (n_vars * (set_words + 1) * 8 bytes)");
+  const char* const who = obj ? "pcp_dfs_forest_device_set_bnb" : (enumerate ? "pcp_dfs_forest_device_set_enum" : "pcp_dfs_forest_device_set");
   SetDfsArgs a;
-  memset(&a, 0, sizeof(a));
-  a.m.recs = c->d_recs; a.m.adj_off = c->d_adj_off; a.m.adj = c->d_adj; a.m.adjp = c->have_adjp ? c->d_adjp : nullptr; a.m.const_val = c->d_const;
-  a.m.n_recs = P; a.m.n_vars = c->n_vars; a.m.n_slots = S; a.m.has_ternary = c->has_ternary; a.m.uniform_kind = c->uniform_kind; a.m.max_deg = c->max_deg;
-  a.set_words = c->set_words; a.list_cap = cap; a.base = c->hull_lo;
-  a.n_trees = st->n_trees; a.level_cap = st->level_capacity; a.trail_cap = st->trail_capacity; a.n_steps = n_steps; a.stop_on_solution = stop_on_solution;
-  a.node_limit = node_limit;
-  a.bits = st->bits; a.tree = st->tree; a.levels = reinterpret_cast<uint4*>(st->levels); a.trail = reinterpret_cast<uint4*>(st->trail);
-  a.counters = reinterpret_cast<unsigned long long*>(st->counters); a.total_nodes = reinterpret_cast<unsigned long long*>(st->total_nodes);
-  a.stop = st->stop; a.first_solution = st->first_solution; a.solution_flag = st->solution_flag; a.stats = c->d_stats;
-  a.val_mode = val;
-  if (obj) {  // branch and bound runs to the end and keeps a row per tree instead of the forest's first solution
-    a.stop_on_solution = 0; a.first_solution = nullptr; a.solution_flag = nullptr;
-    a.obj_var = obj->var; a.obj_mode = obj->mode; a.obj_best = obj->best; a.tree_best = obj->tree_best; a.tree_row = obj->tree_row;
-  }
+  const int32_t rc = forest_set_args(c, who, st, obj, val,
+                                     c->has_formulas ? ": pcp_dfs_forest_device_set evaluates records, not formula trees: a store with formula propagators (Boolean / pcp_model_push_formula) is searched by pcp_dfs_forest_device_setform" : nullptr,
+                                     n_steps, stop_on_solution, node_limit, a);
+  if (rc) return rc;
+  uint32_t cap = (uint32_t)std::min<int64_t>(c->opt_list_cap, 1024);
+  while (cap > 64 && !lds_bytes_set_dfs(c->n_vars, c->n_slots, c->set_words, cap)) cap /= 2;
+  const size_t lds = lds_bytes_set_dfs(c->n_vars, c->n_slots, c->set_words, cap);
+  if (!lds || lds > c->lds_max) return fail(c, PCP_ERR_UNSUPPORTED, "set-mode variable store does not fit one CU's LDS (n_vars * (set_words + 1) * 8 bytes)");
+  a.m.adj_off = c->d_adj_off; a.m.adj = c->d_adj; a.m.adjp = c->have_adjp ? c->d_adjp : nullptr;
+  a.m.has_ternary = c->has_ternary; a.m.uniform_kind = c->uniform_kind; a.m.max_deg = c->max_deg;
+  a.list_cap = cap;
   if (!n_steps) return PCP_OK;
   c->last_plan = pcp_plan{1u, 1u, 0u, 0u, 0u, 0u, 1u, 1u, st->n_trees, 1024u, (uint32_t)lds, cap, 0u};
-  if (c->opt_time_kernels) HIP_TRY(c, hipEventRecord(c->ev_start, stream));
-  HIP_TRY(c, launch_setdfs(a, enumerate, obj != nullptr, stream));
-  if (c->opt_time_kernels) HIP_TRY(c, hipEventRecord(c->ev_stop, stream));
-  c->ev_valid = c->opt_time_kernels != 0;
-  return PCP_OK;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  return forest_launch(c, stream, [&] { return launch_setdfs(a, enumerate, obj != nullptr, stream); });
 }
 
 int32_t pcp_dfs_forest_device_set(pcp_ctx* c, const pcp_forest_state* st, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
@@ -1072,25 +1100,13 @@ int32_t pcp_dfs_forest_device_set_bnb(pcp_ctx* c, const pcp_forest_state* st, co
 static int32_t dfs_forest_setform(pcp_ctx* c, const pcp_forest_state* st, const pcp_forest_objective* obj, uint32_t enumerate, uint32_t val, uint32_t n_steps,
                                   uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
   const char* const who = obj ? "pcp_dfs_forest_device_setform_bnb" : "pcp_dfs_forest_device_setform";
-  auto bad = [&](const char* what) { return fail(c, PCP_ERR_ARG, std::string(who) + ": " + what); };
-  if (enumerate > 1) return bad("enumerate must be 0 or 1");
-  if (val > PCP_VAL_MIN) return bad("val must be PCP_VAL_MIDDLE or PCP_VAL_MIN");
-  if (!c->set_words) return bad("needs a set-mode model (pcp_model_reset with set_words > 0)");
-  if (obj) {
-    if (obj->var >= c->n_vars) return bad("objective variable out of range");
-    if (obj->mode > PCP_MAXIMIZE) return bad("mode must be PCP_MINIMIZE or PCP_MAXIMIZE");
-    if (!obj->best || !obj->tree_best) return bad("best and tree_best are required");
-  }
-  if (!c->has_formulas)
-    return fail(c, PCP_ERR_UNSUPPORTED, std::string(who) + " searches stores with formula propagators (Boolean / pcp_model_push_formula): a store of records alone is searched by pcp_dfs_forest_device_set");
-  if (!c->hull_set) return fail(c, PCP_ERR_CONTRACT, "set mode needs the hull of the initial domains (pcp_model_set_hull)");
-  if ((int64_t)c->hull_hi - c->hull_lo >= (int64_t)c->set_words * 64) return fail(c, PCP_ERR_CONTRACT, "the declared hull does not fit set_words * 64 values");
-  if (!st->n_trees || !st->bits || !st->tree || !st->levels || !st->trail || !st->counters || !st->total_nodes || !st->stop || !st->level_capacity || !st->trail_capacity)
-    return bad("null buffer / zero capacity");
-  if (!obj && (st->first_solution == nullptr) != (st->solution_flag == nullptr)) return bad("first_solution and solution_flag go together");
-  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
-  HIP_TRY(c, hipSetDevice(c->device));
-  { const int32_t rcf = finalize_model(c); if (rcf) return rcf; }
+  if (enumerate > 1) return fail(c, PCP_ERR_ARG, std::string(who) + ": enumerate must be 0 or 1");
+  SetFormDfsArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  const int32_t rc = forest_set_args(c, who, st, obj, val,
+                                     c->has_formulas ? nullptr : " searches stores with formula propagators (Boolean / pcp_model_push_formula): a store of records alone is searched by pcp_dfs_forest_device_set",
+                                     n_steps, stop_on_solution, node_limit, fa.d);
+  if (rc) return rc;
   // up to four trees per 256-thread workgroup; a store whose four slices exceed half a CU's LDS runs with two or one
   uint32_t waves = 4;
   while (waves > 1 && (!lds_bytes_setformdfs(c->n_vars, c->set_words, c->n_units, waves) || lds_bytes_setformdfs(c->n_vars, c->set_words, c->n_units, waves) > c->lds_max / 2))
@@ -1098,31 +1114,13 @@ static int32_t dfs_forest_setform(pcp_ctx* c, const pcp_forest_state* st, const 
   const size_t lds = lds_bytes_setformdfs(c->n_vars, c->set_words, c->n_units, waves);
   if (!lds || lds > c->lds_max)
     return fail(c, PCP_ERR_UNSUPPORTED, std::string(who) + ": a tree's node must fit one CU's LDS (n_vars * (set_words + 1) * 8 bytes + the changed, touched and unit masks)");
-  SetFormDfsArgs fa;
-  memset(&fa, 0, sizeof(fa));
-  SetDfsArgs& a = fa.d;
-  a.m.recs = c->d_recs; a.m.const_val = c->d_const; a.m.n_recs = (uint32_t)c->props.size(); a.m.n_vars = c->n_vars; a.m.n_slots = c->n_slots;
   fa.nodes = c->d_fnodes; fa.unit_root = c->d_unit_root; fa.n_units = c->n_units;
-  a.set_words = c->set_words; a.base = c->hull_lo;
-  a.n_trees = st->n_trees; a.level_cap = st->level_capacity; a.trail_cap = st->trail_capacity; a.n_steps = n_steps; a.stop_on_solution = stop_on_solution;
-  a.node_limit = node_limit;
-  a.bits = st->bits; a.tree = st->tree; a.levels = reinterpret_cast<uint4*>(st->levels); a.trail = reinterpret_cast<uint4*>(st->trail);
-  a.counters = reinterpret_cast<unsigned long long*>(st->counters); a.total_nodes = reinterpret_cast<unsigned long long*>(st->total_nodes);
-  a.stop = st->stop; a.first_solution = st->first_solution; a.solution_flag = st->solution_flag; a.stats = c->d_stats;
-  a.val_mode = val;
-  if (obj) {  // branch and bound runs to the end and keeps a row per tree instead of the forest's first solution
-    a.stop_on_solution = 0; a.first_solution = nullptr; a.solution_flag = nullptr;
-    a.obj_var = obj->var; a.obj_mode = obj->mode; a.obj_best = obj->best; a.tree_best = obj->tree_best; a.tree_row = obj->tree_row;
-  }
   if (!n_steps) return PCP_OK;
   LaunchPlan plan;
   plan.block = 64 * waves; plan.lds_bytes = lds; plan.grid = (st->n_trees + waves - 1) / waves;
   c->last_plan = pcp_plan{waves, 1u, 0u, 0u, 0u, 0u, 1u, 1u, plan.grid, plan.block, (uint32_t)lds, 0u, 3u};
-  if (c->opt_time_kernels) HIP_TRY(c, hipEventRecord(c->ev_start, stream));
-  HIP_TRY(c, launch_setformdfs(fa, enumerate != 0, obj != nullptr, plan, stream));
-  if (c->opt_time_kernels) HIP_TRY(c, hipEventRecord(c->ev_stop, stream));
-  c->ev_valid = c->opt_time_kernels != 0;
-  return PCP_OK;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  return forest_launch(c, stream, [&] { return launch_setformdfs(fa, enumerate != 0, obj != nullptr, plan, stream); });
 }
 
 int32_t pcp_dfs_forest_device_setform(pcp_ctx* c, const pcp_forest_state* st, uint32_t enumerate, uint32_t val, uint32_t n_steps, uint32_t stop_on_solution,
@@ -1143,11 +1141,7 @@ int32_t pcp_dfs_forest_split_set(pcp_ctx* c, const pcp_forest_state* st, uint32_
   if (!st->n_trees || !st->bits || !st->tree || !st->levels || !st->trail || (n_pairs && (!pairs || !done))) return fail(c, PCP_ERR_ARG, "null buffer");
   HIP_TRY(c, hipSetDevice(c->device));
   SetDfsArgs a;
-  memset(&a, 0, sizeof(a));
-  a.m.n_vars = c->n_vars; a.m.n_slots = c->n_slots;
-  a.set_words = c->set_words; a.base = c->hull_lo;
-  a.n_trees = st->n_trees; a.level_cap = st->level_capacity; a.trail_cap = st->trail_capacity;
-  a.bits = st->bits; a.tree = st->tree; a.levels = reinterpret_cast<uint4*>(st->levels); a.trail = reinterpret_cast<uint4*>(st->trail);
+  fill_forest_state(a, c, st);
   HIP_TRY(c, launch_setdfs_split(a, n_pairs, pairs, done, reinterpret_cast<hipStream_t>(hip_stream)));
   return PCP_OK;
 }

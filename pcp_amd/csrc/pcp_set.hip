@@ -22,6 +22,7 @@
 
 #include "pcp_internal.h"
 #include "pcp_setdom.hpp"  // SetDomT, eval_set, scan_bounds and the S_* words of `misc`
+#include "pcp_setdfs.hpp"  // trail_dfs: the search loop of setdfs_kernel
 #ifndef PCP_ABLATE
 #define PCP_ABLATE 0  // profiling builds (tools/build_variant.py): bit 2048 = phase timers of setfix_kernel in the counters
 #endif
@@ -401,16 +402,10 @@ __global__ void __launch_bounds__(kSetThreads) set_derive_active_kernel(const Se
 }
 
 // ------------------------------------------------------------------------------------------------
-// The reference's search loop over FDSpace on the device, ONE TREE PER WORKGROUP (pcp_dfs_forest_device_set):
-// OneSolution / AllSolution<Propagation<Brancher<FirstSmallestVar, MiddleVal, BinarySplit>>> (search/mod.rs:45-52) over
-// VStoreSet = VStoreTrail<IntervalSet<i32>> (variable/mod.rs:38).  The reference restores a node by undoing a TRAIL
-// (variable/memory/trail_memory.rs:100-104); so does this kernel: the current node never leaves LDS, every narrowing appends
-// (variable, word, removed bits) to the tree's trail in HBM, a backtrack ORs the bits back down to the level's mark and applies the
-// right branch.  Per node the HBM traffic is the trail (a few KB after an assignment, a few bytes otherwise) instead of the
-// 125 KB-per-node rows of the batched search (pcp_propagate_device + pcp_branch_device_set).
-// A child differs from its parent's fixpoint in the branched variable only, so only that variable is marked changed (at a fixpoint
-// every other propagator is a no-op until one of its variables changes); a root (pending == kDfsFull) runs the sweep of setfix_kernel.
-// Exactly the reference's left-first order within a tree; several trees = the subtrees of an open-node frontier, each on its CU.
+// The search loop over FDSpace for stores of records, ONE TREE PER WORKGROUP (pcp_dfs_forest_device_set / _set_enum / _set_bnb): trail_dfs
+// (pcp_setdfs.hpp: the loop, the trail, Enumerate and branch and bound) run by a WorkgroupTeam over a RecordNode.  Per node the HBM traffic
+// is the trail (a few KB after an assignment, a few bytes otherwise) instead of the 125 KB-per-node rows of the batched search
+// (pcp_propagate_device + pcp_branch_device_set).  Several trees = the subtrees of an open-node frontier, each on its CU.
 // ------------------------------------------------------------------------------------------------
 struct SetDfsCarve { SetCarve c; size_t touched, adjo, total; };
 
@@ -423,96 +418,39 @@ __host__ __device__ inline SetDfsCarve set_dfs_carve(uint32_t V, uint32_t S, uin
   return d;
 }
 
-// ENUM: the loop under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate> (enumerate.rs:47-60) — a level is `x = v, then x != v`,
-// v the member of the set nearest to the selector's value (a.val_mode).  A template parameter, not a scalar branch: the BinarySplit
-// instantiation is the code it was before the parameter existed.
-//
-// BNB: BranchAndBound<..> around either loop (branch_and_bound.rs:64-84; pcp_dfs_forest_device_set_bnb).  The forest shares ONE incumbent,
-// a device int32 (a.obj_best).  On entering a node — before its propagation — the bound  var < best  (minimize) /  var > best  (maximize) is
-// folded into the objective variable's set through restrict_var: XLessY(var, Constant(best)) narrows once and is then entailed (pcp_bnb.hip),
-// the removal is trailed and marks the variable changed, and a fold that empties the set fails the node on the round loop's first
-// scan_bounds like any other empty set (a node and a failure, as the reference counts it).  Before any solution the incumbent is the "no
-// solution yet" value of pcp_hip.h, which lies outside every set: the fold is a no-op.  The fold stands where a barrier already follows the
-// branch restriction (descend, backtrack) and once at launch start, for the node the tree enters first: a root, a node persisted by the
-// launch before, or one handed over by setdfs_split_kernel.  Its trail entries come after the level's mark, so a backtrack undoes them and
-// the right child folds again against the incumbent of that moment; the incumbent only improves, so nothing a fold removed could have
-// stayed.  The trail bound of the plain loop holds: a fold entry, like every other, takes at least one value out of a set and is popped
-// before that value can return.  On a solution v = lower(var) beats every earlier value of this tree (the node passed the fold): the tree
-// keeps v and the node's lower bounds (a.tree_best, a.tree_row) and then lowers / raises the incumbent atomically — another tree may hold a
-// better one already, so the winner's row is chosen on the host among the trees whose value equals the final incumbent.  There is no
-// stop-on-solution and no first solution: branch and bound runs to the end (or to the node limit).  The two BNB = false instantiations are
-// the code they were before the parameter existed.
-template <bool ENUM, bool BNB>
-__global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const uint32_t tid = threadIdx.x, nth = blockDim.x, lane = tid & 63;
-  const uint32_t wv = __builtin_amdgcn_readfirstlane(tid >> 6), nwv = nth >> 6;
-  const uint32_t V = a.m.n_vars, S = a.m.n_slots, sw = a.set_words, C = a.list_cap, P = a.m.n_recs, words = (P + 63) >> 6;
-  const uint32_t Wv = (S + 31) >> 5;
-  const SetDfsCarve dcv = set_dfs_carve(V, S, sw, C);
-  const SetCarve& cv = dcv.c;
-  unsigned long long* bits = reinterpret_cast<unsigned long long*>(smem + cv.bits);
-  int2* bnd = reinterpret_cast<int2*>(smem + cv.bnd);
-  uint32_t* cur = reinterpret_cast<uint32_t*>(smem + cv.chg_a);
-  uint32_t* nxt = reinterpret_cast<uint32_t*>(smem + cv.chg_b);
-  uint32_t* list_id = reinterpret_cast<uint32_t*>(smem + cv.list_id);
-  uint32_t* list_off = reinterpret_cast<uint32_t*>(smem + cv.list_off);
-  uint32_t* list_deg = reinterpret_cast<uint32_t*>(smem + cv.list_deg);
-  uint32_t* misc = reinterpret_cast<uint32_t*>(smem + cv.misc);
-  uint32_t* touched = reinterpret_cast<uint32_t*>(smem + dcv.touched);
-  uint32_t* adjo = reinterpret_cast<uint32_t*>(smem + dcv.adjo);
-  const uint32_t t = blockIdx.x;
-  pcp_stats* const st_slot = a.stats + (blockIdx.x & (kStatSlots - 1));
-  uint32_t* const tree = a.tree + (size_t)t * 4;
-  uint32_t n_levels = tree[0], pending = tree[2];
-  if (tree[3] & 1u) return;  // this tree is finished
-  const uint32_t given0 = tree[3] >> 8;  // its oldest levels whose right branch went to another tree (setdfs_split_kernel)
-  uint4* const trail = a.trail + (size_t)t * a.trail_cap;
-  uint4* const levels = a.levels + (size_t)t * a.level_cap;
-  unsigned long long* const gbits = reinterpret_cast<unsigned long long*>(a.bits) + (size_t)t * V * sw;
-
-  // ---- the tree's current node into LDS, its bounds ------------------------------------------------------------------------
-  if (tid < 32) misc[tid] = 0;
-  for (uint32_t i = tid; i < Wv; i += nth) { cur[i] = 0; nxt[i] = 0; touched[i] = 0; }
-  for (uint32_t v = tid; v <= V; v += nth) adjo[v] = a.m.adj_off[v];
-  {
-    const uint32_t nwords = V * sw;
-    if (!(nwords & 1u) && !((size_t)gbits & 15)) {
-      const uint4* s4 = reinterpret_cast<const uint4*>(gbits);
-      uint4* d4 = reinterpret_cast<uint4*>(bits);
-      for (uint32_t i = tid; i < nwords / 2; i += nth) d4[i] = s4[i];
-    } else {
-      for (uint32_t i = tid; i < nwords; i += nth) bits[i] = gbits[i];
-    }
-  }
-  __syncthreads();
-  if (tid == 0) misc[S_TRAILLEN] = tree[1];
-  for (uint32_t v = tid; v < V; v += nth) {
-    const int2 b = scan_bounds(bits + (size_t)v * sw, sw, a.base);
-    bnd[v] = b;
-    if (b.x > b.y) atomicOr(&misc[S_FAIL], 1u);
-  }
-  if (pending != kDfsFull && tid == 0) cur[pending >> 5] = 1u << (pending & 31u);  // (a node persisted by the launch before)
-  if constexpr (BNB) {
-    // a persisted node was folded when it was entered, and that fold's mark went with the launch: the objective is marked again
-    // (a variable marked without need only runs records that are no-ops at a fixpoint)
-    if (pending != kDfsFull && tid == 0) cur[a.obj_var >> 5] |= 1u << (a.obj_var & 31u);
-  }
-  __syncthreads();
-
+// A node of the records forest: setfix_kernel's propagation on a trailed node.  At a fixpoint every propagator is a no-op until one of its
+// variables changes, so a child runs the changed-variable lists from its branched variable alone (two changed masks, cur and nxt, swapped
+// every round); a root (pending == kDfsFull) runs the sweep of setfix_kernel first.
+template <bool BNB>
+struct RecordNode {
+  using DM = SetDomT<true>;
+  const SetDfsArgs& a;
+  const WorkgroupTeam& team;
+  unsigned long long* bits;
+  int2* bnd;
+  uint32_t *cur, *nxt, *list_id, *list_off, *list_deg, *misc, *touched, *adjo;
+  uint4* trail;
+  uint32_t mask_words;
+  bool neq_only, use_pay;
   uint32_t narrow = 0;
   uint64_t ev = 0;
-  unsigned long long c_nodes = 0, c_sols = 0, c_fail = 0;
-  uint32_t c_err = 0;
-  bool finished = false;
-  uint32_t reserved = 0;       // nodes this tree may still run before it asks the forest's counter again
-  bool res_has_last = false;   // ... the last of which is the node that reaches the limit
-  const bool neq_only = a.m.uniform_kind == PCP_NEQ && S == V;
-  using DM = SetDomT<true>;
+  unsigned long long key = ~0ull;
+
+  __device__ __forceinline__ RecordNode(const SetDfsArgs& a_, const WorkgroupTeam& team_, unsigned char* smem, const SetDfsCarve& dcv, uint32_t t)
+      : a(a_), team(team_),
+        bits(reinterpret_cast<unsigned long long*>(smem + dcv.c.bits)), bnd(reinterpret_cast<int2*>(smem + dcv.c.bnd)),
+        cur(reinterpret_cast<uint32_t*>(smem + dcv.c.chg_a)), nxt(reinterpret_cast<uint32_t*>(smem + dcv.c.chg_b)),
+        list_id(reinterpret_cast<uint32_t*>(smem + dcv.c.list_id)), list_off(reinterpret_cast<uint32_t*>(smem + dcv.c.list_off)),
+        list_deg(reinterpret_cast<uint32_t*>(smem + dcv.c.list_deg)), misc(reinterpret_cast<uint32_t*>(smem + dcv.c.misc)),
+        touched(reinterpret_cast<uint32_t*>(smem + dcv.touched)), adjo(reinterpret_cast<uint32_t*>(smem + dcv.adjo)),
+        trail(a_.trail + (size_t)t * a_.trail_cap), mask_words((a_.m.n_slots + 31) >> 5),
+        neq_only(a_.m.uniform_kind == PCP_NEQ && a_.m.n_slots == a_.m.n_vars), use_pay(a_.m.adjp != nullptr && !a_.m.has_ternary) {}
+
+  __device__ __forceinline__ uint32_t* mark_mask() const { return cur; }
+  __device__ __forceinline__ DM dom(uint32_t* chg) { return DM{bits, bnd, a.m.const_val, a.m.n_vars, a.set_words, a.base, chg, misc, &narrow, trail, &misc[S_TRAILLEN], a.trail_cap}; }
   // a record as seen from variable v's list, entry idx: binary models rebuild it from the 8-byte adjacency payload (one coalesced load
   // instead of an index load and the gather that depends on it)
-  const bool use_pay = a.m.adjp != nullptr && !a.m.has_ternary;
-  auto rec_at = [&](uint32_t v, uint32_t idx) -> Rec {
+  __device__ __forceinline__ Rec rec_at(uint32_t v, uint32_t idx) const {
     if (use_pay) {
       const uint2 q = a.m.adjp[idx];
       const uint32_t other = q.x & kSlotMask, kind = (q.x >> 28) & 7u;
@@ -522,92 +460,58 @@ __global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a)
       return rc;
     }
     return a.m.recs[a.m.adj[idx]];
-  };
-
-  // a branch constraint folded into the variable's set: the values lo..hi leave it — one lane per word (one thread doing the up
-  // to set_words atomics and trail entries in turn was a quarter of a cheap node)
-  auto restrict_var = [&](uint32_t var, long long lo, long long hi) {
-    if (wv != 0) return;
-    long long b0 = lo - a.base, b1 = hi - a.base;
-    if (b0 < 0) b0 = 0;
-    if (b1 >= (long long)sw * 64) b1 = (long long)sw * 64 - 1;
-    bool changed = false;
-    for (long long k = (b0 >> 6) + lane; b0 <= b1 && k <= (b1 >> 6); k += 64) {
-      unsigned long long m = ~0ull;
-      if (k == (b0 >> 6)) m &= ~0ull << (b0 & 63);
-      if (k == (b1 >> 6)) m &= ~0ull >> (63 - (b1 & 63));
-      unsigned long long* w = &bits[(size_t)var * sw + k];
-      const unsigned long long gone = atomicAnd(w, ~m) & m;
-      if (gone) {
-        changed = true;
-        const uint32_t pos = atomicAdd(&misc[S_TRAILLEN], 1u);
-        if (pos < a.trail_cap) trail[pos] = make_uint4(var * sw + (uint32_t)k, var, (uint32_t)gone, (uint32_t)(gone >> 32));
-        else atomicOr(&misc[S_TRAILOVF], 1u);
-      }
-    }
-    if (__ballot(changed) != 0 && lane == 0) { atomicOr(&cur[var >> 5], 1u << (var & 31u)); ++narrow; }
-  };
-  // BNB: the bound folded into the objective's set — the values >= best (minimize) / <= best (maximize) leave it.  Wavefront 0, as restrict_var.
-  auto fold_bound = [&]() {
-    if (wv != 0) return;
-    const long long best = (long long)__hip_atomic_load(a.obj_best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (a.obj_mode == PCP_MINIMIZE) restrict_var(a.obj_var, best, 1ll << 40);
-    else restrict_var(a.obj_var, -(1ll << 40), best);
-  };
-  if constexpr (BNB) {
-    // the node this launch enters first, against the incumbent of now.  The sweep of a root reads bnd before the round loop scans
-    // anything, so the objective's bounds are taken again here.
-    fold_bound();
-    __syncthreads();
-    if (tid == 0) {
-      const int2 b = scan_bounds(bits + (size_t)a.obj_var * sw, sw, a.base);
-      bnd[a.obj_var] = b;
-      if (b.x > b.y) misc[S_FAIL] = 1u;
-    }
-    __syncthreads();
   }
 
-  for (uint32_t step = 0; step < a.n_steps; ++step) {
-    // ---- may this node run?  (stop flag of the forest, the node limit of all trees together: StopNode, stop_node.rs:57-62) ----
-    // Nodes are reserved kDfsChunk at a time from the forest's counter (two device-scope atomics and a barrier per node were a fifth
-    // of a cheap node); what a tree does not use goes back when the launch ends.  The node that reaches the limit is explored and
-    // counted, but StopNode replaces its status by EndOfSearch (stop_node.rs:55-62): it is neither a solution nor a failure.
-    if (reserved == 0) {
-      if (tid == 0) {
-        uint32_t got = 0, has_last = 0;
-        if (!__hip_atomic_load(a.stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-          const unsigned long long want = min((unsigned long long)kDfsChunk, (unsigned long long)(a.n_steps - step));
-          const unsigned long long old = atomicAdd(a.total_nodes, want);
-          if (!a.node_limit) got = (uint32_t)want;
-          else if (old >= a.node_limit) atomicAdd(a.total_nodes, 0ull - want);
-          else {
-            got = (uint32_t)min(want, a.node_limit - old);
-            if (got < want) atomicAdd(a.total_nodes, 0ull - (want - got));
-            has_last = old + got >= a.node_limit ? 1u : 0u;
-          }
-        }
-        misc[S_CTL] = got; misc[S_CTL + 2] = has_last;
-      }
-      __syncthreads();
-      reserved = misc[S_CTL];
-      res_has_last = misc[S_CTL + 2] != 0;
-      if (!reserved) break;
+  __device__ __forceinline__ void load(const unsigned long long* gbits) {
+    const uint32_t tid = team.rank, nth = team.size, V = a.m.n_vars;
+    if (tid < 32) misc[tid] = 0;
+    for (uint32_t i = tid; i < mask_words; i += nth) { cur[i] = 0; nxt[i] = 0; touched[i] = 0; }
+    for (uint32_t v = tid; v <= V; v += nth) adjo[v] = a.m.adj_off[v];
+    copy_node(team, bits, gbits, V * a.set_words);
+    team.sync();
+  }
+  // launch start: the bounds of every variable; a node persisted by the launch before marks its pending variable again
+  __device__ __forceinline__ void begin(uint32_t pending) {
+    const uint32_t tid = team.rank, V = a.m.n_vars, sw = a.set_words;
+    for (uint32_t v = tid; v < V; v += team.size) {
+      const int2 b = scan_bounds(bits + (size_t)v * sw, sw, a.base);
+      bnd[v] = b;
+      if (b.x > b.y) atomicOr(&misc[S_FAIL], 1u);
     }
-    --reserved;
-    const bool last = res_has_last && reserved == 0;
+    if (pending != kDfsFull && tid == 0) cur[pending >> 5] = 1u << (pending & 31u);
+    if constexpr (BNB) {
+      // a persisted node was folded when it was entered, and that fold's mark went with the launch: the objective is marked again
+      // (a variable marked without need only runs records that are no-ops at a fixpoint)
+      if (pending != kDfsFull && tid == 0) cur[a.obj_var >> 5] |= 1u << (a.obj_var & 31u);
+    }
+    team.sync();
+  }
+  // after the fold of launch start: the sweep of a root reads bnd before the round loop scans anything, so the objective's bounds are
+  // taken again here
+  __device__ __forceinline__ void begun() {
+    if constexpr (BNB) {
+      if (team.leader()) {
+        const int2 b = scan_bounds(bits + (size_t)a.obj_var * a.set_words, a.set_words, a.base);
+        bnd[a.obj_var] = b;
+        if (b.x > b.y) misc[S_FAIL] = 1u;
+      }
+      team.sync();
+    }
+  }
 
-    // ---- propagate ---------------------------------------------------------------------------------------------------------
+  __device__ __forceinline__ bool propagate(uint32_t pending) {
+    const uint32_t tid = team.rank, nth = team.size, V = a.m.n_vars, sw = a.set_words, C = a.list_cap, P = a.m.n_recs;
     if (pending == kDfsFull && !misc[S_FAIL]) {
-      const DM dm{bits, bnd, a.m.const_val, V, sw, a.base, cur, misc, &narrow, trail, &misc[S_TRAILLEN], a.trail_cap};
+      const DM dm = dom(cur);
       bool bulk = false;
       if (neq_only) {  // the lists of the assigned variables stand for the whole sweep (see setfix_kernel)
         if (tid == 0) misc[S_NSING] = 0;
-        __syncthreads();
+        team.sync();
         for (uint32_t v = tid; v < V; v += nth) {
           const int2 b = bnd[v];
           if (b.x == b.y) { const uint32_t pos = atomicAdd(&misc[S_NSING], 1u); if (pos < C) list_id[pos] = v; }
         }
-        __syncthreads();
+        team.sync();
         const uint32_t ns = misc[S_NSING];
         bulk = ns <= C;
         if (bulk)
@@ -618,7 +522,7 @@ __global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a)
       }
       if (!bulk)
         for (uint32_t r = tid; r < P; r += nth) { (void)eval_set(a.m.recs[r], dm, false); ++ev; }
-      __syncthreads();
+      team.sync();
     }
     bool runaway = false;
     for (uint32_t round = 0;; ++round) {
@@ -630,8 +534,8 @@ __global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a)
         bnd[v] = b;
         if (b.x > b.y) atomicOr(&misc[S_FAIL], 1u);
       }
-      __syncthreads();
-      for (uint32_t w = tid; w < Wv; w += nth) {
+      team.sync();
+      for (uint32_t w = tid; w < mask_words; w += nth) {
         if (round) nxt[w] = 0;
         uint32_t bitsw = cur[w];
         if (!bitsw) continue;
@@ -648,11 +552,11 @@ __global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a)
         }
         if (dropped) cur[w] &= ~dropped;
       }
-      __syncthreads();
+      team.sync();
       const uint32_t total = misc[m_total];
       if (total == 0 || misc[S_FAIL]) break;
       if (tid == 0) misc[(round & 1u) ? S_TOTAL : S_TOTAL2] = 0;
-      const DM dm{bits, bnd, a.m.const_val, V, sw, a.base, nxt, misc, &narrow, trail, &misc[S_TRAILLEN], a.trail_cap};
+      const DM dm = dom(nxt);
       auto run = [&](uint32_t v, const Rec rec) {  // FIFO dedup as in setfix_kernel: the lowest changed variable of a record runs it
         const uint32_t x = rec.xk & kSlotMask;
         const bool tern = (rec.xk >> 28) > PCP_LT;
@@ -679,42 +583,36 @@ __global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a)
           if (vmin != 0xFFFFFFFFu) run(vmin, rec);
         }
       }
-      __syncthreads();
+      team.sync();
       uint32_t* sw_ = cur; cur = nxt; nxt = sw_;
     }
-    __syncthreads();
-    // ---- status (store.rs:250-256): failed / every propagator entailed / open -------------------------------------------------
-    // The candidate for branching first — the variable of minimal CARDINALITY > 1, first index (first_smallest_var.rs:30-39 on
-    // Domain::size()): an open node almost always has an open record in that variable's list, while the table's first records
-    // belong to the variables a dive assigned first and are all entailed.  Only when the list holds no open record is the whole
-    // table scanned (exact either way).
+    team.sync();
+    return runaway;
+  }
+
+  // status (store.rs:250-256): failed / every propagator entailed / open.  The candidate for branching first (first_smallest_var): an open
+  // node almost always has an open record in that variable's list, while the table's first records belong to the variables a dive
+  // assigned first and are all entailed.  Only when the list holds no open record is the whole table scanned (exact either way).  The
+  // minimum across wavefronts goes through list_off, idle between rounds (16 x 8 bytes).
+  __device__ __forceinline__ NodeStatus status() {
+    const uint32_t lane = team.lane, wv = team.wave, P = a.m.n_recs, words = (P + 63) >> 6;
     const bool failed = misc[S_FAIL] != 0;
-    unsigned long long key = ~0ull;
+    key = ~0ull;
     if (!failed) {
-      for (uint32_t v = tid; v < V; v += nth) {
-        unsigned long long size = 0;
-        for (uint32_t k = 0; k < sw; ++k) size += (unsigned long long)__popcll(bits[(size_t)v * sw + k]);
-        if (size > 1) key = min(key, (size << 32) | v);
-      }
-      for (int o = 32; o > 0; o >>= 1) key = min(key, (unsigned long long)__shfl_down(key, o));
-      unsigned long long* best = reinterpret_cast<unsigned long long*>(list_off);  // (idle between rounds; 16 x 8 bytes)
-      if (lane == 0) best[wv] = key;
-      __syncthreads();
-      key = best[0];
-      for (uint32_t w = 1; w < nwv; ++w) key = min(key, best[w]);
-      const DM dm{bits, bnd, a.m.const_val, V, sw, a.base, nxt, misc, &narrow, trail, &misc[S_TRAILLEN], a.trail_cap};
+      key = first_smallest_var(team, bits, a.m.n_vars, a.set_words);
+      const DM dm = dom(nxt);
       if (key != ~0ull) {
         const uint32_t u = (uint32_t)key, o0 = adjo[u], o1 = adjo[u + 1];
-        for (uint32_t i0 = o0 + wv * 64; i0 < o1; i0 += nth) {
+        for (uint32_t i0 = o0 + wv * 64; i0 < o1; i0 += team.size) {
           if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&misc[S_OPEN], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))) break;
           bool open_rec = false;
           if (i0 + lane < o1) open_rec = !eval_set(rec_at(u, i0 + lane), dm, true);
           if (__ballot(open_rec) != 0 && lane == 0) atomicOr(&misc[S_OPEN], 1u);
         }
       }
-      __syncthreads();
+      team.sync();
       if (!misc[S_OPEN]) {
-        for (uint32_t w = wv; w < words; w += nwv) {
+        for (uint32_t w = wv; w < words; w += team.n_waves) {
           if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&misc[S_OPEN], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))) break;
           const uint32_t r = (w << 6) + lane;
           bool open_rec = false;
@@ -723,133 +621,36 @@ __global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a)
         }
       }
     }
-    __syncthreads();
+    team.sync();
     if (failed)  // (only a failed node leaves marks behind; its backtrack has barriers before anything is marked again)
-      for (uint32_t i = tid; i < Wv; i += nth) { cur[i] = 0; nxt[i] = 0; }
-    const bool open = misc[S_OPEN] != 0;
-    const uint32_t tlen = misc[S_TRAILLEN];
-    if (misc[S_TRAILOVF]) { c_err = 4; break; }  // the trail is full: the tree cannot be restored any more (terminal)
-    if (runaway) { c_err = 5; break; }
-    ++c_nodes;
-    bool descend = false;
-    if (failed) {
-      if (!last) ++c_fail;
-    } else if (!open && last) {
-    } else if (!open) {  // a solution (monitor.rs:19-68); the first one of the forest is kept
-      ++c_sols;
-      if constexpr (BNB) {
-        const int v = bnd[a.obj_var].x;  // the incumbent is var.lower() in both modes (branch_and_bound.rs:73-77)
-        if (a.tree_row)
-          for (uint32_t u = tid; u < V; u += nth) a.tree_row[(size_t)t * V + u] = bnd[u].x;
-        if (tid == 0) {
-          a.tree_best[t] = v;
-          // (the old value is used, so the atomic has been performed before the backtrack below reads the incumbent for its fold)
-          const int old = a.obj_mode == PCP_MINIMIZE ? __hip_atomic_fetch_min(a.obj_best, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                                     : __hip_atomic_fetch_max(a.obj_best, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          misc[S_CTL + 1] = (uint32_t)old;
-        }
-      } else if (a.first_solution) {
-        if (tid == 0) misc[S_CTL + 1] = atomicCAS(a.solution_flag, 0u, 1u) == 0u ? 1u : 0u;
-        __syncthreads();
-        if (misc[S_CTL + 1])
-          for (uint32_t v = tid; v < V; v += nth) a.first_solution[v] = bnd[v].x;
-      }
-      if (a.stop_on_solution && tid == 0) atomicExch(a.stop, 1u);
-    } else {
-      // Brancher<FirstSmallestVar, MiddleVal, BinarySplit>::enter on sets: the candidate found above
-      if (key == ~0ull) { c_err = 3; --c_nodes; if (tid == 0) atomicAdd(a.total_nodes, ~0ull); break; }  // Unknown, yet nothing to branch on: the reference panics
-      if (n_levels >= a.level_cap) { c_err = 1; --c_nodes; pending = kDfsFull; if (tid == 0) atomicAdd(a.total_nodes, ~0ull); break; }
-      const uint32_t var = (uint32_t)key;
-      const int2 d = bnd[var];
-      if constexpr (ENUM) {
-        // MinVal: lower() (min_val.rs:25-27), a member; MiddleVal: (lower + upper) / 2 (middle_val.rs:25-27) or, when that is a hole of the
-        // set, the member nearest to it, the lower one first.  Wavefront 0 alone needs the value: one lane per word, a minimum across lanes.
-        if (wv == 0) {
-          long long v = d.x;
-          if (a.val_mode != PCP_VAL_MIN) {
-            const long long m = ((long long)d.x + (long long)d.y) / 2;
-            unsigned long long nk = ~0ull;
-            for (uint32_t k = lane; k < sw; k += 64) nk = min(nk, nearest_member_key(bits[(size_t)var * sw + k], (long long)a.base + 64ll * (long long)k, m));
-            for (int o = 32; o > 0; o >>= 1) nk = min(nk, (unsigned long long)__shfl_xor(nk, o));
-            v = nearest_member_value(nk, m);
-          }
-          if (tid == 0) levels[n_levels] = make_uint4(var, (uint32_t)(int)v, tlen, kLevelEnum);
-          // the left child x = v (enumerate.rs:47-53): everything below v and everything above it leaves the set
-          restrict_var(var, d.x, v - 1);
-          restrict_var(var, v + 1, d.y);
-        }
-      } else {
-        const int val = (int)(((long long)d.x + (long long)d.y) / 2);  // MiddleVal (middle_val.rs:25-27)
-        if (tid == 0) levels[n_levels] = make_uint4(var, (uint32_t)val, tlen, 0u);
-        restrict_var(var, (long long)val + 1, d.y);  // the left child x <= val (binary_split.rs:46-57)
-      }
-      if constexpr (BNB) fold_bound();
-      ++n_levels;
-      pending = var;
-      descend = true;
-    }
-    if (!descend) {
-      // ---- backtrack: the deepest level whose right branch is still open (a level whose right branch was given to another tree
-      // is undone like any other and skipped) ------------------------------------------------------------------------------
-      uint4 lv = make_uint4(0u, 0u, 0u, kLevelGiven);
-      uint32_t from = tlen;
-      while (n_levels) {
-        --n_levels;
-        lv = levels[n_levels];
-        for (uint32_t i = lv.z + tid; i < from; i += nth) {
-          const uint4 e = trail[i];
-          atomicOr(&bits[e.x], ((unsigned long long)e.w << 32) | e.z);
-          atomicOr(&touched[e.y >> 5], 1u << (e.y & 31u));
-        }
-        from = lv.z;
-        if (!(lv.w & kLevelGiven)) break;
-      }
-      if (lv.w & kLevelGiven) { finished = true; break; }  // nothing left that is this tree's
-      __syncthreads();
-      if (tid == 0) { misc[S_TRAILLEN] = from; misc[S_FAIL] = 0; }
-      for (uint32_t v = tid; v < V; v += nth)
-        if ((touched[v >> 5] >> (v & 31u)) & 1u) bnd[v] = scan_bounds(bits + (size_t)v * sw, sw, a.base);
-      __syncthreads();
-      for (uint32_t i = tid; i < Wv; i += nth) touched[i] = 0;
-      // the right child, by the level's own distributor: x > val (binary_split.rs:52-57) or x != val (enumerate.rs:54-59)
-      restrict_var(lv.x, (lv.w & kLevelEnum) ? (long long)(int)lv.y : (long long)bnd[lv.x].x, (long long)(int)lv.y);
-      if constexpr (BNB) fold_bound();
-      pending = lv.x;
-    }
-    if (tid == 0) { misc[S_OPEN] = 0; misc[S_TOTAL] = 0; misc[S_TOTAL2] = 0; if (last) atomicExch(a.stop, 1u); }  // (a node's last round leaves its count behind)
-    if (last || (a.stop_on_solution && c_sols)) { __syncthreads(); break; }
-    __syncthreads();
+      for (uint32_t i = team.rank; i < mask_words; i += team.size) { cur[i] = 0; nxt[i] = 0; }
+    return NodeStatus{failed, misc[S_OPEN] != 0};
   }
-  if (reserved && tid == 0) atomicAdd(a.total_nodes, 0ull - (unsigned long long)reserved);  // what this tree reserved and did not run
-
-  // ---- persist the tree: its current node, its stacks' lengths, its counters --------------------------------------------------
-  __syncthreads();
-  {
-    const uint32_t nwords = V * sw;
-    if (!(nwords & 1u) && !((size_t)gbits & 15)) {
-      const uint4* s4 = reinterpret_cast<const uint4*>(bits);
-      uint4* d4 = reinterpret_cast<uint4*>(gbits);
-      for (uint32_t i = tid; i < nwords / 2; i += nth) d4[i] = s4[i];
-    } else {
-      for (uint32_t i = tid; i < nwords; i += nth) gbits[i] = bits[i];
+  __device__ __forceinline__ unsigned long long branch_key() const { return key; }  // (status() needed it to probe the node)
+  __device__ __forceinline__ void backtracking() {}  // (the levels and the trail were synchronised by the barriers of propagate() and status())
+  __device__ __forceinline__ void backtracked() {}
+  __device__ __forceinline__ void end_node() {
+    if (team.leader()) { misc[S_OPEN] = 0; misc[S_TOTAL] = 0; misc[S_TOTAL2] = 0; }  // (a node's last round leaves its count behind)
+  }
+  __device__ __forceinline__ void flush_stats(pcp_stats* st_slot, unsigned long long c_nodes) {
+    for (int o = 32; o > 0; o >>= 1) { narrow += __shfl_down(narrow, o); ev += __shfl_down(ev, o); }
+    if (team.lane == 0) {
+      if (narrow) atomicAdd((unsigned long long*)&st_slot->narrowings, (unsigned long long)narrow);
+      if (ev) { atomicAdd((unsigned long long*)&st_slot->evaluated, (unsigned long long)ev); atomicAdd((unsigned long long*)&st_slot->full_evals, (unsigned long long)ev); }
     }
-  }
-  for (int o = 32; o > 0; o >>= 1) { narrow += __shfl_down(narrow, o); ev += __shfl_down(ev, o); }
-  if (lane == 0) {
-    if (narrow) atomicAdd((unsigned long long*)&st_slot->narrowings, (unsigned long long)narrow);
-    if (ev) { atomicAdd((unsigned long long*)&st_slot->evaluated, (unsigned long long)ev); atomicAdd((unsigned long long*)&st_slot->full_evals, (unsigned long long)ev); }
-  }
-  if (tid == 0) {
-    tree[0] = n_levels; tree[1] = misc[S_TRAILLEN]; tree[2] = pending; tree[3] = (finished ? 1u : 0u) | (min(given0, n_levels) << 8);
-    unsigned long long* cn = a.counters + (size_t)t * 4;
-    cn[0] += c_nodes; cn[1] += c_sols; cn[2] += c_fail;
-    if (c_err) cn[3] = c_err;
     // reference-equivalent steps: every propagator of every node once (init_scheduler) — the wake-ups are in `evaluated`
-    atomicAdd((unsigned long long*)&st_slot->steps, c_nodes * (unsigned long long)P);
-    atomicAdd((unsigned long long*)&st_slot->nodes, c_nodes);
-    if (c_fail) atomicAdd((unsigned long long*)&st_slot->failed_nodes, c_fail);
-    if (c_err) atomicExch(a.stop, 1u);
+    if (team.leader()) atomicAdd((unsigned long long*)&st_slot->steps, c_nodes * (unsigned long long)a.m.n_recs);
   }
+};
+
+// ENUM, BNB: see trail_dfs.  The BNB = false instantiations carry no branch-and-bound code, the ENUM = false ones no value selector.
+template <bool ENUM, bool BNB>
+__global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const SetDfsCarve dcv = set_dfs_carve(a.m.n_vars, a.m.n_slots, a.set_words, a.list_cap);
+  const WorkgroupTeam team(reinterpret_cast<uint32_t*>(smem + dcv.c.misc), reinterpret_cast<unsigned long long*>(smem + dcv.c.list_off));
+  RecordNode<BNB> node(a, team, smem, dcv, blockIdx.x);
+  trail_dfs<ENUM, BNB>(a, blockIdx.x, team, node);
 }
 
 // A finished tree takes over the OLDEST open right branch of a tree that still has some (the subtree nearest the donor's root: the
