@@ -150,6 +150,12 @@ uint32_t pcp_abi_version(void);
  *     The search forest over sets has one entry per kind of store: pcp_dfs_forest_device_set, _set_enum and _set_bnb evaluate records, not
  *     formula trees, and return PCP_ERR_UNSUPPORTED for a store with formula propagators; pcp_dfs_forest_device_setform and _setform_bnb
  *     search exactly those stores and return it for a store without one.  pcp_dfs_forest_split_set serves both.
+ *   THE SEARCH FORESTS, one row per kind of store:
+ *     all-XNeqY, Interval            pcp_dfs_forest_device
+ *     formula units, Interval        pcp_dfs_forest_device_form, _form_bnb   (what Cumulative::join builds: XEqYMulZ and Sum keep it here)
+ *     records, IntervalSet           pcp_dfs_forest_device_set, _set_enum, _set_bnb
+ *     formula units, IntervalSet     pcp_dfs_forest_device_setform, _setform_bnb
+ *     any other Interval store has no forest: pcp_dfs_device searches it, one tree.
  *   ENUMERATE (search/branching/enumerate.rs:33-60: children `x = v` and `x != v`) needs no engine support in set mode — both children are
  *   exact set operations the caller applies to `bits` before propagating (keep bit v / clear bit v), as pcp_branch_device_set does for
  *   BinarySplit.  In interval mode `x != v` with v inside (lb, ub) is not a domain operation: it stays a per-node propagator — a unit
@@ -457,6 +463,20 @@ int32_t pcp_dfs_device(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_steps, 
  * up the counters and decides when to stop launching (all sp == 0, any stop != 0, its node budget).  All-XNeqY models over implicit
  * nodes only (PCP_ERR_UNSUPPORTED otherwise: pcp_dfs_device runs any interval model, one tree). */
 int32_t pcp_dfs_forest_device(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream);
+/* The same forest for an Interval store WITH formula propagators (Boolean / BooleanNeg / pcp_model_push_formula units) — the stores
+ * propagators::Cumulative::join builds (propagators/cumulative.rs:59-114: equivalences over Boolean, XEqYMulZ and Sum views, which set mode
+ * refuses).  ≡ the engine of pcp_dfs_device (search/mod.rs:45-52, search/engine/one_solution.rs:92-105, under StopNode,
+ * search/stop_node.rs:47-62) on n_trees stacks at once: tree t is exactly a pcp_dfs_device instance on slice t of the state, laid out as for
+ * pcp_dfs_forest_device; `dirty` is ignored and may be NULL, `status` is scratch.  These stores are small, so a tree is one WAVEFRONT with
+ * the node it runs in a slice of a CU's LDS, up to four trees per 256-thread workgroup: pcp_last_plan reports path 3, block = 64 x trees per
+ * workgroup, grid = ceil(n_trees / those), lds_bytes.  Between two calls sp, the rows [0, sp), the counters and stop are what pcp_dfs_device
+ * leaves after the same number of steps, node for node, so a caller may move bottom rows between stacks.  Unit liveness is derived, never
+ * stored: the descent to a left child keeps it, every other pop sets every unit live.
+ * Set-mode model, a null required buffer, n_trees == 0, capacity < 2: PCP_ERR_ARG.  A store without formula propagators:
+ * PCP_ERR_UNSUPPORTED (all-XNeqY: pcp_dfs_forest_device; any other: pcp_dfs_device, one tree).  A node that does not fit one CU's LDS:
+ * PCP_ERR_UNSUPPORTED.  n_steps == 0: PCP_OK, nothing is launched. */
+int32_t pcp_dfs_forest_device_form(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, uint32_t n_steps, uint32_t stop_on_solution,
+                                   uint64_t node_limit, void* hip_stream);
 
 /* ---- the same loop over FDSpace (set mode), a FOREST of trees, one per workgroup (ABI v5) --------------------------------------
  * ≡ the engine above over VStoreSet = VStoreTrail<IntervalSet<i32>> (variable/mod.rs:38): like the reference, a node is restored
@@ -542,6 +562,16 @@ int32_t pcp_dfs_forest_device_setform(pcp_ctx* ctx, const pcp_forest_state* st, 
  * of *best on entering a node, no stop on a solution.  Also PCP_ERR_ARG: var >= n_vars, mode > PCP_MAXIMIZE, a null best / tree_best. */
 int32_t pcp_dfs_forest_device_setform_bnb(pcp_ctx* ctx, const pcp_forest_state* st, const pcp_forest_objective* obj, uint32_t enumerate,
                                           uint32_t val, uint32_t n_steps, uint64_t node_limit, void* hip_stream);
+/* Branch and bound around pcp_dfs_forest_device_form, the forest over Interval stores with formula propagators (above) —
+ * BranchAndBound<Propagation<Brancher<..>>> (search/branch_and_bound.rs:64-84) — with the objective struct of the set forests.  The forest shares ONE incumbent, the device word *best.  Every row a tree pops first gets the bound
+ * folded into the objective's domain, *best read at that moment: ub[var] = min(ub[var], best - 1) (minimize) or lb[var] = max(lb[var],
+ * best + 1) (maximize); "no solution yet" as for pcp_objective: the fold is then a no-op.  A node the fold empties is a node and a failed
+ * node.  The fold is written back with the node, so the right child inherits it and folds again when it is popped.  On a solution
+ * tree_best[t] = lb[var], tree_row[t] = the node's lower bounds, then *best is lowered / raised atomically.  There is no stop on a solution,
+ * and st->first_solution is ignored.  With n_trees = 1 the nodes are the reference's, one for one.
+ * Also PCP_ERR_ARG: var >= n_vars, mode > PCP_MAXIMIZE, a null best / tree_best. */
+int32_t pcp_dfs_forest_device_form_bnb(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_objective* obj,
+                                       uint32_t n_steps, uint64_t node_limit, void* hip_stream);
 /* Between two calls of pcp_dfs_forest_device_set* / _setform*: finished trees take over work from trees that still have some.  pairs = n_pairs x
  * (donor, receiver) tree indices (device uint32).  For every pair whose receiver is finished and whose donor has an open right branch
  * left, the donor's OLDEST open right branch (the subtree nearest its root) becomes the receiver's new root — built from the donor's

@@ -107,6 +107,32 @@ struct FormArgs {
 size_t lds_bytes_formula(uint32_t n_slots, uint32_t n_units, uint32_t waves);  // one slice per wavefront (= per node in flight)
 hipError_t launch_formfix(const FormArgs& a, const LaunchPlan& p, hipStream_t stream);
 
+// The search loop over such a store on the device: one tree per WAVEFRONT on its own stack of (lb, ub) rows, the node being run in that
+// wavefront's LDS slice (pcp_formdfs.hip).  The stacks are a pcp_dfs_state laid out as for pcp_dfs_forest_device.
+struct FormDfsArgs {
+  ModelDev m;                    // needs recs, const_val, sums, n_vars, n_slots
+  const FNode* nodes;
+  const uint32_t* unit_root;
+  uint32_t n_units;
+  uint32_t n_trees, capacity, n_steps, stop_on_solution;
+  unsigned long long node_limit; // per tree
+  int32_t* lb;                   // [n_trees][capacity][n_vars]
+  int32_t* ub;
+  uint32_t* sp;                  // [n_trees]
+  uint32_t* stop;                // [n_trees]
+  unsigned long long* counters;  // [n_trees][5]: nodes, solutions, failed nodes, error, first-solution flag
+  int32_t* first_solution;       // [n_trees][n_vars] or null
+  uint32_t* violation;
+  pcp_stats* stats;
+  // branch and bound only (formdfs_kernel<true>, pcp_dfs_forest_device_form_bnb)
+  uint32_t obj_var, obj_mode;    // the objective variable, PCP_MINIMIZE / PCP_MAXIMIZE
+  int32_t* obj_best;             // device int32[1]: the forest's incumbent
+  int32_t* tree_best;            // [n_trees]: the value of each tree's last solution
+  int32_t* tree_row;             // [n_trees][n_vars] or null: its lower bounds
+};
+size_t lds_bytes_formdfs(uint32_t n_slots, uint32_t n_units, uint32_t waves);  // one slice per tree; 0 = beyond a CU's LDS
+hipError_t launch_formdfs(const FormDfsArgs& a, bool bnb, const LaunchPlan& p, hipStream_t stream);
+
 // The same stores over IntervalSet<i32> domains (set mode): the trees as above, the node's sets as bit words in LDS (pcp_setform.hip).
 struct SetFormArgs {
   ModelDev m;                // needs recs, const_val, n_vars, n_slots

@@ -25,7 +25,7 @@ ERRORS = {-1: "PCP_ERR_ARG", -2: "PCP_ERR_CONTRACT", -3: "PCP_ERR_HIP", -4: "PCP
 ABI_SYMBOLS = [
     "pcp_ctx_create", "pcp_ctx_destroy", "pcp_last_error", "pcp_strerror", "pcp_abi_version",
     "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull",
-    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
+    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
 ]
 
 
@@ -157,6 +157,8 @@ def load_library():
     L.pcp_dfs_forest_device_setform_bnb.argtypes = [vp, C.POINTER(ForestState), C.POINTER(ForestObjective), u32, u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_split_set.argtypes = [vp, C.POINTER(ForestState), u32, vp, vp, vp]
     L.pcp_dfs_forest_device.argtypes = [vp, C.POINTER(DfsState), u32, u32, u32, C.c_uint64, vp]
+    L.pcp_dfs_forest_device_form.argtypes = [vp, C.POINTER(DfsState), u32, u32, u32, C.c_uint64, vp]
+    L.pcp_dfs_forest_device_form_bnb.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestObjective), u32, C.c_uint64, vp]
     L.pcp_stats_reset.argtypes = [vp, vp]
     L.pcp_stats_read.argtypes = [vp, C.POINTER(PcpStats), vp]
     L.pcp_debug_counters.argtypes = [vp, C.POINTER(C.c_uint64), u32, vp]
@@ -164,7 +166,7 @@ def load_library():
     L.pcp_last_plan.argtypes = [vp, C.POINTER(PcpPlan)]
     L.pcp_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
     for f in ("pcp_ctx_create", "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull", "pcp_model_set_hull",
-              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
+              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
         getattr(L, f).restype = i32
     _lib = L
     return L
@@ -423,10 +425,11 @@ class Context:
                                                    _ptr(child_ub), _ptr(child_dirty), _ptr(child_excl_off), _ptr(child_excl), int(child_excl_capacity), _ptr(counts),
                                                    C.c_void_p(stream_ptr)))
 
-    def dfs_device(self, lb0, ub0, n_steps: int, capacity: int = 4096, stop_on_solution: bool = True, node_limit: int = 0, chunk: int = 256):
+    def dfs_device(self, lb0, ub0, n_steps: int, capacity: int = 4096, stop_on_solution: bool = True, node_limit: int = 0, chunk: int = 256, info: dict | None = None):
         """pcp_dfs_device: the reference's one-node-per-step DFS entirely on the device.  Runs until the stack is empty, a stop
         condition holds or n_steps steps were enqueued (in chunks of `chunk` steps between two reads of the 8-byte state).
-        Returns dict(nodes, solutions, failed, error, open, steps_enqueued, first_solution)."""
+        Returns dict(nodes, solutions, failed, error, open, steps_enqueued, first_solution).  ``info`` (a dict) receives ``rows``: the open
+        nodes the search left on its stack, (lb, ub) numpy arrays [open, n_vars], bottom row first."""
         import torch
         dev = torch.device("cuda", self.device)
         V = self.n_vars
@@ -451,12 +454,14 @@ class Context:
                 break
         cn = counters.cpu().tolist()
         sp, stop = state.cpu().tolist()
+        if info is not None:
+            info["rows"] = (lb[:sp].cpu().numpy(), ub[:sp].cpu().numpy())
         return {"nodes": cn[0], "solutions": cn[1], "failed": cn[2], "error": cn[3], "open": sp, "stopped": bool(stop), "steps_enqueued": done,
                 "first_solution": sol.cpu().numpy() if cn[1] else None}
 
     def dfs_forest(self, root_lb, root_ub, stop_on_solution: bool = False, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
                    max_launches: int = 1 << 30, node_budget: int = 0, want_solution: bool = False, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
-                   sp0=None, hints: bool = True):
+                   sp0=None, hints: bool = True, formulas: bool = False, _call=None):
         """pcp_dfs_forest_device: the reference's search loop (interval mode, all-XNeqY models) on many subtrees at once, one workgroup per
         tree, each exactly a pcp_dfs_device instance.  root_lb / root_ub: [n_trees, n_vars] int32 (numpy or CUDA tensors): the roots, not yet
         propagated.  Launches of steps_per_launch nodes per tree are repeated until every stack is empty, a tree stopped (solution with
@@ -465,7 +470,10 @@ class Context:
         rank, node_budget and the end of the search are GLOBAL (one small all_reduce per launch), and a rank whose trees ran dry takes open
         nodes from the other ranks (search_forest.refill_across_ranks).  ``capacity`` rows per tree are allocated up front and doubled, up to
         ``max_capacity``, whenever a tree fills its stack (error 1 is only reported beyond that).  Returns dict(nodes, solutions, failed, error, open, launches,
-        per_tree=[n_trees, 5], first_solutions) — this rank's counters."""
+        per_tree=[n_trees, 5], first_solutions) — this rank's counters.
+        ``formulas``: the store holds formula propagators (Boolean / formula units — what Cumulative.join builds): the trees run in
+        pcp_dfs_forest_device_form, one per wavefront (last_plan: path 3, block = 64 x trees per workgroup); it keeps no ``dirty`` rows.
+        Stacks, growth, refill, ``dist`` and the result dict are the same."""
         import torch
         dev = torch.device("cuda", self.device)
         V = self.n_vars
@@ -482,7 +490,7 @@ class Context:
         status = torch.zeros((T, capacity), dtype=torch.uint8, device=dev)
         counters = torch.zeros((T, 5), dtype=torch.int64, device=dev)
         sol = torch.zeros((T, V), dtype=torch.int32, device=dev) if want_solution else None
-        dirty = torch.full((T, capacity), -1, dtype=torch.int32, device=dev) if hints else None  # pcp_dfs_state.dirty: one word per stack row
+        dirty = torch.full((T, capacity), -1, dtype=torch.int32, device=dev) if (hints and not formulas) else None  # pcp_dfs_state.dirty: one word per stack row
         from .search_forest import ForestStacks, run_forest_loop
         stream = torch.cuda.current_stream(dev).cuda_stream
         box = {}
@@ -495,18 +503,59 @@ class Context:
         del lb, ub, status, dirty
         point(fs)
 
+        entry = self._L.pcp_dfs_forest_device_form if formulas else self._L.pcp_dfs_forest_device
+
         def launch():
-            self._check(self._L.pcp_dfs_forest_device(self._h, C.byref(box["st"]), T, int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit_per_tree), C.c_void_p(stream)))
+            if _call is not None:  # (dfs_forest_bnb: the same loop over another entry point)
+                self._check(_call(box["st"], T, stream))
+            else:
+                self._check(entry(self._h, C.byref(box["st"]), T, int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit_per_tree), C.c_void_p(stream)))
 
         loop = run_forest_loop(launch, fs, stop_on_solution=stop_on_solution, node_budget=node_budget,
                                rebalance=rebalance and not node_limit_per_tree, max_launches=max_launches, dist=dist)
         launches, steals = loop["launches"], loop["steals"]
         if info is not None:
             info.update(loop)
+            spc = sp.cpu().tolist()  # the open nodes each tree left on its stack, bottom row first
+            info["rows"] = [(fs.lb[t, :spc[t]].cpu().numpy(), fs.ub[t, :spc[t]].cpu().numpy()) for t in range(T)] if T <= 64 else None
         cn = counters.cpu().numpy()
         return {"nodes": int(cn[:, 0].sum()), "solutions": int(cn[:, 1].sum()), "failed": int(cn[:, 2].sum()), "error": int(cn[:, 3].max()),
                 "open": int(sp.sum().item()), "launches": launches, "per_tree": cn, "trees": T, "steals": steals,
                 "first_solutions": sol.cpu().numpy() if want_solution else None}
+
+    def dfs_forest_bnb(self, root_lb, root_ub, objective, best0=None, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
+                       max_launches: int = 1 << 30, node_budget: int = 0, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
+                       sp0=None):
+        """pcp_dfs_forest_device_form_bnb: branch and bound (branch_and_bound.rs:64-84) in the forest over an Interval store with formula
+        propagators — the loop, stacks, growth and refill of dfs_forest(formulas=True), every popped row entered with the forest's incumbent
+        (one device word) folded into the objective's bounds.  ``objective`` = (var, "min" | "max").  ``best0``: a known bound to start from
+        (only solutions that beat it are found).  Returns the dict of dfs_forest plus ``best`` (None: no tree found a solution),
+        ``best_solution`` (the row of the lowest tree whose value is ``best``) and ``tree_best`` ([n_trees]; a tree without a solution: the
+        "no solution yet" value)."""
+        import torch
+        var, mode = objective
+        if mode not in OBJ_MODES:
+            raise ValueError(f"objective mode must be 'min' or 'max', not {mode!r}")
+        none = no_incumbent(mode)
+        dev = torch.device("cuda", self.device)
+        T = int(np.prod(root_lb.shape)) // max(self.n_vars, 1)
+        d_best = torch.full((1,), none if best0 is None else int(best0), dtype=torch.int32, device=dev)
+        tree_best = torch.full((T,), none, dtype=torch.int32, device=dev)
+        tree_row = torch.zeros((T, self.n_vars), dtype=torch.int32, device=dev)
+        obj = ForestObjective(int(var) & 0xFFFFFFFF, OBJ_MODES[mode], d_best.data_ptr(), tree_best.data_ptr(), tree_row.data_ptr())
+
+        def call(st, n_trees, stream):
+            return self._L.pcp_dfs_forest_device_form_bnb(self._h, C.byref(st), n_trees, C.byref(obj), int(steps_per_launch), int(node_limit_per_tree), C.c_void_p(stream))
+
+        out = self.dfs_forest(root_lb, root_ub, node_limit_per_tree=node_limit_per_tree, steps_per_launch=steps_per_launch, capacity=capacity, max_launches=max_launches,
+                              node_budget=node_budget, rebalance=rebalance, info=info, dist=dist, max_capacity=max_capacity, sp0=sp0, formulas=True, _call=call)
+        tb = tree_best.cpu().numpy()
+        found = tb != none
+        out["tree_best"] = tb
+        out["best"] = int(d_best.item()) if found.any() else None
+        winners = np.nonzero(found & (tb == int(d_best.item())))[0]
+        out["best_solution"] = tree_row[int(winners[0])].cpu().numpy() if len(winners) else None
+        return out
 
     def dfs_forest_set(self, root_bits, stop_on_solution: bool = False, node_limit: int = 0, steps_per_launch: int = 256,
                        level_capacity: int = 0, trail_capacity: int = 0, max_launches: int = 1 << 30, want_solution: bool = True,

@@ -295,10 +295,11 @@ def run_forest_loop(launch, fs: ForestStacks, stop_on_solution: bool = False, no
             "grown": fs.grown, "capacity": fs.capacity}
 
 
-def seed_roots_interval(ctx, lb0, ub0, want: int):
-    """Interval mode: breadth-first expansion of the root to at least `want` open nodes.  Returns (lb rows, ub rows, stats)."""
+def seed_roots_interval(ctx, lb0, ub0, want: int, objective=None):
+    """Interval mode: breadth-first expansion of the root to at least `want` open nodes.  ``objective``: the expansion runs under branch and
+    bound (DeviceSearch(objective=)), its stats carry the incumbent (``best``, ``best_solution``).  Returns (lb rows, ub rows, stats)."""
     from .search_device import DeviceSearch
-    ds = DeviceSearch(ctx, batch=max(want, 1), capacity=4 * max(want, 1) + 64, implicit=True)
+    ds = DeviceSearch(ctx, batch=max(want, 1), capacity=4 * max(want, 1) + 64, implicit=True, objective=objective)
     ds.reset(lb0, ub0)
     while 0 < ds.size < want:
         if ds.advance(all_solutions=True, max_rounds=1, keep_solutions=0):
@@ -312,8 +313,9 @@ STACK_BYTES_CAP = 64 << 30  # default ceiling of the forest's stack rows per GPU
 
 
 def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_per_launch: int = 512, rank: int = 0, world: int = 1, capacity: int = 0,
-                  dist=None, info: dict | None = None, stack_bytes: int = STACK_BYTES_CAP) -> dict:
-    """Interval mode, all-XNeqY models: expansion + one in-kernel DFS per open node (pcp_dfs_forest_device).  The node limit is checked
+                  dist=None, info: dict | None = None, stack_bytes: int = STACK_BYTES_CAP, formulas: bool = False) -> dict:
+    """Interval mode, all-XNeqY models: expansion + one in-kernel DFS per open node (pcp_dfs_forest_device).  formulas: the store holds
+    formula propagators (what Cumulative.join builds): the trees run in pcp_dfs_forest_device_form, one per wavefront.  The node limit is checked
     between launches, so `nodes` can exceed it by less than one launch; it is the exact count.  Without ``dist`` every tree also stops at
     its share of the limit; with ``dist`` (torch.distributed, world ranks) the limit is global, finished trees are refilled (also across
     ranks) and the returned counters are still this rank's.  A tree's stack holds its OPEN nodes (one right branch per level of
@@ -354,7 +356,38 @@ def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_
             upfront = max(upfront, torch.cuda.mem_get_info(ml.device)[0] // 8)
         capacity = ceiling if (per_tree and not multi and ceiling * row_bytes <= upfront) else min(128, ceiling)
     r = ctx.dfs_forest(ml, mu, node_limit_per_tree=0 if multi else per_tree, steps_per_launch=steps_per_launch, capacity=capacity, max_capacity=max(ceiling, capacity),
-                       node_budget=max(node_limit - st.num_nodes, 1) if multi else budget, dist=dist if multi else None, info=info, sp0=sp0)
+                       node_budget=max(node_limit - st.num_nodes, 1) if multi else budget, dist=dist if multi else None, info=info, sp0=sp0, formulas=formulas)
     out["nodes"] += r["nodes"]; out["solutions"] += r["solutions"]; out["failed"] += r["failed"]
     out["error"] = r["error"]; out["launches"] = r["launches"]
+    return out
+
+
+def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: int = 512, best0=None, capacity: int = 128, max_capacity: int = 1 << 16,
+               info: dict | None = None, formulas: bool = True) -> dict:
+    """Branch and bound over an Interval store with formula propagators (branch_and_bound.rs:64-84 around the loop of forest_search):
+    minimize / maximize ``objective`` = (var, "min" | "max") below (lb0, ub0).  The root is expanded breadth-first under branch and bound
+    (seed_roots_interval with DeviceSearch(objective=)) to at least ``n_trees`` open nodes; each becomes a tree of
+    Context.dfs_forest_bnb, and the expansion's incumbent — or ``best0``, whichever is better — is the forest's first one, so the
+    expansion's solutions take part.  Returns the dict of Context.dfs_forest_bnb (``nodes`` / ``solutions`` / ``failed`` include the
+    expansion's, ``seeded_nodes`` names them); ``best`` is None when neither the expansion nor a tree found a solution beating ``best0``."""
+    if not formulas:
+        raise ValueError("forest_bnb searches stores with formula propagators (all-XNeqY stores have no objective to bound)")
+    var, mode = objective
+    rl, ru, st = seed_roots_interval(ctx, lb0, ub0, n_trees, objective=(int(var), mode))
+    better = min if mode == "min" else max
+    known = [b for b in (best0, st.best) if b is not None]
+    start = better(known) if known else None
+    seeded = {"best": st.best, "best_solution": st.best_solution}
+    if rl.shape[0] == 0:  # the expansion finished the tree
+        out = {"nodes": 0, "solutions": 0, "failed": 0, "error": 0, "open": 0, "launches": 0, "trees": 0, "steals": 0, "tree_best": np.zeros(0, np.int32),
+               "best": None, "best_solution": None}
+    else:
+        out = ctx.dfs_forest_bnb(rl, ru, (int(var), mode), best0=start, steps_per_launch=steps_per_launch, capacity=capacity,
+                                 max_capacity=max(max_capacity, capacity), info=info)
+    out["seeded_nodes"] = st.num_nodes
+    out["nodes"] += st.num_nodes; out["solutions"] += st.num_solution; out["failed"] += st.num_failed_node
+    # no tree beat the expansion's incumbent: it is the optimum, unless the caller's bound was already as good
+    beats = lambda a, b: b is None or (a < b if mode == "min" else a > b)
+    if out["best"] is None and seeded["best"] is not None and beats(seeded["best"], best0):
+        out["best"], out["best_solution"] = seeded["best"], seeded["best_solution"]
     return out
