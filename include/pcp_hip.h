@@ -177,7 +177,10 @@ int32_t pcp_model_push_sum(pcp_ctx* ctx, uint32_t n_members, const uint32_t* var
  * child is propagated only when every other child is disentailed.  Where the reference would PANIC — Boolean::propagate on a domain
  * without 1 reached through a Conjunction (a non-monotonic update, variable/store.rs:153-156) — the node fails instead.
  * Both domain types: over Interval stores the unit runs in pcp_formula.hip, over IntervalSet stores (set mode) in pcp_setform.hip, where
- * Boolean::propagate clears every other value of the set.  XEqYMulZ leaves and Sum operands stay interval mode only. */
+ * Boolean::propagate clears every other value of the set.  XEqYMulZ leaves and Sum operands stay interval mode only.
+ * A tree of more than 64 nodes must be a flat Conjunction of leaves (the kernels keep a tree's statuses in 64-bit masks and walk a wider
+ * unit as a loop over its members): this call takes any other one, and the first propagation or search call on the store — the lowering
+ * runs there, before any launch — returns PCP_ERR_UNSUPPORTED until the unit is truncated away. */
 int32_t pcp_model_push_formula(pcp_ctx* ctx, uint32_t n_nodes, const pcp_fnode* nodes, uint32_t n_leaves, const pcp_prop* leaves);
 /* ≡ FrozenStore::restore's `propagators.truncate(label.0)` (propagation/store.rs:319-323); n_units counts
  * units, not elementary props. */
