@@ -155,6 +155,7 @@ uint32_t pcp_abi_version(void);
  *     formula units, Interval        pcp_dfs_forest_device_form, _form_bnb   (what Cumulative::join builds: XEqYMulZ and Sum keep it here)
  *     records, IntervalSet           pcp_dfs_forest_device_set, _set_enum, _set_bnb
  *     formula units, IntervalSet     pcp_dfs_forest_device_setform, _setform_bnb
+ *     small stores, Interval         pcp_dfs_forest_device_small, _small_bnb (plain propagators of any kind, <= 128 slots, <= 2048 filters: Golomb)
  *     any other Interval store has no forest: pcp_dfs_device searches it, one tree.
  *   ENUMERATE (search/branching/enumerate.rs:33-60: children `x = v` and `x != v`) needs no engine support in set mode — both children are
  *   exact set operations the caller applies to `bits` before propagating (keep bit v / clear bit v), as pcp_branch_device_set does for
@@ -575,6 +576,24 @@ int32_t pcp_dfs_forest_device_setform_bnb(pcp_ctx* ctx, const pcp_forest_state* 
  * Also PCP_ERR_ARG: var >= n_vars, mode > PCP_MAXIMIZE, a null best / tree_best. */
 int32_t pcp_dfs_forest_device_form_bnb(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_objective* obj,
                                        uint32_t n_steps, uint64_t node_limit, void* hip_stream);
+/* The same forest for a SMALL Interval store of plain propagators — no formula units, at most 128 slots (variables and interned constants)
+ * and 2048 elementary filters: Distinct, XLessY, XEqY, XEqYPlusZ, XLessYPlusZ, XGreaterYPlusZ, XEqYMulZ and Sum views in any mixture, the
+ * stores the one-wavefront-per-node fixpoint kernel propagates (plan.path 4; the Golomb-ruler network is one).  State, counters, error
+ * codes, StopNode and first solutions are those of pcp_dfs_forest_device_form: tree t is exactly a pcp_dfs_device instance on slice t of
+ * the state, `dirty` is ignored and may be NULL, `status` is scratch, unit liveness is derived.  A tree is one WAVEFRONT, up to four trees
+ * per 256-thread workgroup, which share one LDS copy of the records: pcp_last_plan reports path 4, block = 64 x trees per workgroup,
+ * grid = ceil(n_trees / those), lds_bytes.  Option "small_alldiff" is honoured (0: a Distinct runs pair by pair — the same tree).  An
+ * all-XNeqY store within the limits is accepted too.
+ * Set-mode model, a null required buffer, n_trees == 0, capacity < 2: PCP_ERR_ARG.  A store with formula propagators: PCP_ERR_UNSUPPORTED
+ * (pcp_dfs_forest_device_form).  A store over the limits, or whose records and one node do not fit one CU's LDS: PCP_ERR_UNSUPPORTED
+ * (pcp_dfs_device searches it, one tree).  n_steps == 0: PCP_OK, nothing is launched. */
+int32_t pcp_dfs_forest_device_small(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, uint32_t n_steps, uint32_t stop_on_solution,
+                                    uint64_t node_limit, void* hip_stream);
+/* Branch and bound around it, exactly as pcp_dfs_forest_device_form_bnb is around pcp_dfs_forest_device_form: one incumbent word *best for
+ * the forest, folded into every popped row; tree_best / tree_row on a solution, then *best lowered / raised atomically; no stop on a
+ * solution.  Also PCP_ERR_ARG: var >= n_vars, mode > PCP_MAXIMIZE, a null best / tree_best. */
+int32_t pcp_dfs_forest_device_small_bnb(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_objective* obj,
+                                        uint32_t n_steps, uint64_t node_limit, void* hip_stream);
 /* Between two calls of pcp_dfs_forest_device_set* / _setform*: finished trees take over work from trees that still have some.  pairs = n_pairs x
  * (donor, receiver) tree indices (device uint32).  For every pair whose receiver is finished and whose donor has an open right branch
  * left, the donor's OLDEST open right branch (the subtree nearest its root) becomes the receiver's new root — built from the donor's

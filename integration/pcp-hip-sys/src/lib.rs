@@ -221,6 +221,10 @@ extern "C" {
                                       hip_stream: *mut c_void) -> i32; // the same forest for Interval stores with formula propagators (Cumulative::join)
     pub fn pcp_dfs_forest_device_form_bnb(ctx: *mut pcp_ctx, st: *const pcp_dfs_state, n_trees: u32, obj: *const pcp_forest_objective, n_steps: u32,
                                           node_limit: u64, hip_stream: *mut c_void) -> i32; // BranchAndBound around it
+    pub fn pcp_dfs_forest_device_small(ctx: *mut pcp_ctx, st: *const pcp_dfs_state, n_trees: u32, n_steps: u32, stop_on_solution: u32, node_limit: u64,
+                                       hip_stream: *mut c_void) -> i32; // the same forest for small Interval stores of plain propagators (Golomb)
+    pub fn pcp_dfs_forest_device_small_bnb(ctx: *mut pcp_ctx, st: *const pcp_dfs_state, n_trees: u32, obj: *const pcp_forest_objective, n_steps: u32,
+                                           node_limit: u64, hip_stream: *mut c_void) -> i32; // BranchAndBound around it
     pub fn pcp_dfs_forest_device_set(ctx: *mut pcp_ctx, st: *const pcp_forest_state, n_steps: u32, stop_on_solution: u32, node_limit: u64,
                                      hip_stream: *mut c_void) -> i32;
     pub fn pcp_dfs_forest_device_set_enum(ctx: *mut pcp_ctx, st: *const pcp_forest_state, val: u32, n_steps: u32, stop_on_solution: u32,

@@ -1250,6 +1250,63 @@ int32_t pcp_dfs_forest_device_form_bnb(pcp_ctx* c, const pcp_dfs_state* st, uint
   return dfs_forest_form(c, st, n_trees, obj, n_steps, 0, node_limit, hip_stream);
 }
 
+// The same loop over a SMALL Interval store of plain propagators — what smallfix_kernel propagates (plan.path 4): one tree per wavefront,
+// that kernel's round inside the loop (pcp_smalldfs.hip); obj != nullptr: under branch and bound.  The stacks are those of
+// pcp_dfs_forest_device.
+static int32_t dfs_forest_small(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_objective* obj, uint32_t n_steps, uint32_t stop_on_solution,
+                                uint64_t node_limit, void* hip_stream) {
+  const std::string who = obj ? "pcp_dfs_forest_device_small_bnb" : "pcp_dfs_forest_device_small";
+  if (c->set_words) return fail(c, PCP_ERR_ARG, who + " runs interval-mode models (sets: pcp_dfs_forest_device_set)");
+  if (!n_trees || !st->lb || !st->ub || !st->sp || !st->stop || !st->status || !st->counters || st->capacity < 2)
+    return fail(c, PCP_ERR_ARG, who + ": null buffer / no tree / capacity < 2");
+  if (obj) {
+    if (obj->var >= c->n_vars) return fail(c, PCP_ERR_ARG, who + ": objective variable out of range");
+    if (obj->mode > PCP_MAXIMIZE) return fail(c, PCP_ERR_ARG, who + ": mode must be PCP_MINIMIZE or PCP_MAXIMIZE");
+    if (!obj->best || !obj->tree_best) return fail(c, PCP_ERR_ARG, who + ": best and tree_best are required");
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  { const int32_t rcf = finalize_model(c); if (rcf) return rcf; }
+  if (c->has_formulas)
+    return fail(c, PCP_ERR_UNSUPPORTED, who + " searches stores of plain propagators: a store with formula propagators (Boolean / pcp_model_push_formula) is searched by pcp_dfs_forest_device_form");
+  const uint32_t S = c->n_slots, P = (uint32_t)c->props.size();
+  const char* const too_large = " searches small stores — at most 128 variables (incl. interned constants) and 2048 elementary filters, a workgroup's records and nodes in one CU's LDS: a larger store is searched by pcp_dfs_device, one tree";
+  if (S > 128u || P > 2048u) return fail(c, PCP_ERR_UNSUPPORTED, who + too_large);
+  // up to four trees per 256-thread workgroup; a store whose records and four slices exceed half a CU's LDS runs with two or one
+  uint32_t waves = 4;
+  while (waves > 1 && (!lds_bytes_smalldfs(S, c->n_units, P, waves) || lds_bytes_smalldfs(S, c->n_units, P, waves) > c->lds_max / 2)) waves /= 2;
+  const size_t lds = lds_bytes_smalldfs(S, c->n_units, P, waves);
+  if (!lds || lds > c->lds_max) return fail(c, PCP_ERR_UNSUPPORTED, who + too_large);
+  if (!n_steps) return PCP_OK;
+  SmallDfsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.m.recs = c->d_recs; a.m.const_val = c->d_const; a.m.n_recs = P; a.m.n_vars = c->n_vars; a.m.n_slots = S; a.m.has_ternary = c->has_ternary;
+  a.m.sums = SumTab{c->d_sum_off, c->d_sum_mem, c->n_vars, c->n_sum_slots, c->d_mul_off};
+  a.rec_unit = c->has_groups ? c->d_rec_unit : nullptr; a.n_units = c->n_units;
+  if (c->n_alldiff && c->opt_small_alldiff) { a.ad_tab = c->d_ad_tab; a.ad_vars = c->d_ad_vars; }
+  a.n_trees = n_trees; a.capacity = st->capacity; a.n_steps = n_steps; a.stop_on_solution = obj ? 0u : stop_on_solution; a.node_limit = node_limit;
+  a.lb = st->lb; a.ub = st->ub; a.sp = st->sp; a.stop = st->stop; a.counters = reinterpret_cast<unsigned long long*>(st->counters);
+  a.first_solution = obj ? nullptr : st->first_solution;
+  a.violation = c->d_retry + 1; a.stats = c->d_stats;
+  if (obj) { a.obj_var = obj->var; a.obj_mode = obj->mode; a.obj_best = obj->best; a.tree_best = obj->tree_best; a.tree_row = obj->tree_row; }
+  LaunchPlan plan;
+  plan.block = 64 * waves; plan.lds_bytes = lds; plan.grid = (n_trees + waves - 1) / waves;
+  c->last_plan = pcp_plan{waves, 1u, 0u, 0u, 0u, 0u, 1u, 0u, plan.grid, plan.block, (uint32_t)lds, 0u, 4u};
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  return forest_launch(c, stream, [&] { return launch_smalldfs(a, obj != nullptr, plan, stream); });
+}
+
+int32_t pcp_dfs_forest_device_small(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
+                                    void* hip_stream) {
+  if (!c || !st) return c ? fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_small: null state") : PCP_ERR_ARG;
+  return dfs_forest_small(c, st, n_trees, nullptr, n_steps, stop_on_solution, node_limit, hip_stream);
+}
+
+int32_t pcp_dfs_forest_device_small_bnb(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_objective* obj, uint32_t n_steps, uint64_t node_limit,
+                                        void* hip_stream) {
+  if (!c || !st || !obj) return c ? fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_small_bnb: null state / objective") : PCP_ERR_ARG;
+  return dfs_forest_small(c, st, n_trees, obj, n_steps, 0, node_limit, hip_stream);
+}
+
 int32_t pcp_dfs_device(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
   if (!c || !st) return PCP_ERR_ARG;
   if (c->set_words) return fail(c, PCP_ERR_UNSUPPORTED, "pcp_dfs_device runs interval-mode models only");

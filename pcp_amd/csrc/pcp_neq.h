@@ -194,4 +194,32 @@ struct SmallArgs {
 size_t lds_bytes_small(uint32_t n_slots, uint32_t n_units, uint32_t n_recs, uint32_t waves);
 hipError_t launch_smallfix(const SmallArgs& a, const LaunchPlan& p, hipStream_t stream);
 
+// The search loop over such a store on the device: one tree per WAVEFRONT on its own stack of (lb, ub) rows, the node being run in that
+// wavefront's LDS slice, the records in the copy its workgroup shares (pcp_smalldfs.hip).  The stacks are a pcp_dfs_state laid out as for
+// pcp_dfs_forest_device.
+struct SmallDfsArgs {
+  ModelDev m;                    // needs recs, const_val, sums, n_recs, n_vars, n_slots
+  const uint32_t* rec_unit;      // [n_recs] unit of each record, or null: every record is its own unit
+  uint32_t n_units;
+  const uint32_t* ad_tab;        // all-different units, or null (SmallArgs)
+  const uint32_t* ad_vars;
+  uint32_t n_trees, capacity, n_steps, stop_on_solution;
+  unsigned long long node_limit; // per tree
+  int32_t* lb;                   // [n_trees][capacity][n_vars]
+  int32_t* ub;
+  uint32_t* sp;                  // [n_trees]
+  uint32_t* stop;                // [n_trees]
+  unsigned long long* counters;  // [n_trees][5]: nodes, solutions, failed nodes, error, first-solution flag
+  int32_t* first_solution;       // [n_trees][n_vars] or null
+  uint32_t* violation;
+  pcp_stats* stats;
+  // branch and bound only (smalldfs_kernel<true>, pcp_dfs_forest_device_small_bnb)
+  uint32_t obj_var, obj_mode;    // the objective variable, PCP_MINIMIZE / PCP_MAXIMIZE
+  int32_t* obj_best;             // device int32[1]: the forest's incumbent
+  int32_t* tree_best;            // [n_trees]: the value of each tree's last solution
+  int32_t* tree_row;             // [n_trees][n_vars] or null: its lower bounds
+};
+size_t lds_bytes_smalldfs(uint32_t n_slots, uint32_t n_units, uint32_t n_recs, uint32_t waves);  // the records' copy + one slice per tree; 0 = beyond a CU's LDS
+hipError_t launch_smalldfs(const SmallDfsArgs& a, bool bnb, const LaunchPlan& p, hipStream_t stream);
+
 }  // namespace pcp

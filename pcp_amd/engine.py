@@ -25,7 +25,7 @@ ERRORS = {-1: "PCP_ERR_ARG", -2: "PCP_ERR_CONTRACT", -3: "PCP_ERR_HIP", -4: "PCP
 ABI_SYMBOLS = [
     "pcp_ctx_create", "pcp_ctx_destroy", "pcp_last_error", "pcp_strerror", "pcp_abi_version",
     "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull",
-    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
+    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
 ]
 
 
@@ -159,6 +159,8 @@ def load_library():
     L.pcp_dfs_forest_device.argtypes = [vp, C.POINTER(DfsState), u32, u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_form.argtypes = [vp, C.POINTER(DfsState), u32, u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_form_bnb.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestObjective), u32, C.c_uint64, vp]
+    L.pcp_dfs_forest_device_small.argtypes = [vp, C.POINTER(DfsState), u32, u32, u32, C.c_uint64, vp]
+    L.pcp_dfs_forest_device_small_bnb.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestObjective), u32, C.c_uint64, vp]
     L.pcp_stats_reset.argtypes = [vp, vp]
     L.pcp_stats_read.argtypes = [vp, C.POINTER(PcpStats), vp]
     L.pcp_debug_counters.argtypes = [vp, C.POINTER(C.c_uint64), u32, vp]
@@ -166,7 +168,7 @@ def load_library():
     L.pcp_last_plan.argtypes = [vp, C.POINTER(PcpPlan)]
     L.pcp_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
     for f in ("pcp_ctx_create", "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull", "pcp_model_set_hull",
-              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
+              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
         getattr(L, f).restype = i32
     _lib = L
     return L
@@ -461,7 +463,7 @@ class Context:
 
     def dfs_forest(self, root_lb, root_ub, stop_on_solution: bool = False, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
                    max_launches: int = 1 << 30, node_budget: int = 0, want_solution: bool = False, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
-                   sp0=None, hints: bool = True, formulas: bool = False, _call=None):
+                   sp0=None, hints: bool = True, formulas: bool = False, small: bool = False, _call=None):
         """pcp_dfs_forest_device: the reference's search loop (interval mode, all-XNeqY models) on many subtrees at once, one workgroup per
         tree, each exactly a pcp_dfs_device instance.  root_lb / root_ub: [n_trees, n_vars] int32 (numpy or CUDA tensors): the roots, not yet
         propagated.  Launches of steps_per_launch nodes per tree are repeated until every stack is empty, a tree stopped (solution with
@@ -473,8 +475,13 @@ class Context:
         per_tree=[n_trees, 5], first_solutions) — this rank's counters.
         ``formulas``: the store holds formula propagators (Boolean / formula units — what Cumulative.join builds): the trees run in
         pcp_dfs_forest_device_form, one per wavefront (last_plan: path 3, block = 64 x trees per workgroup); it keeps no ``dirty`` rows.
-        Stacks, growth, refill, ``dist`` and the result dict are the same."""
+        Stacks, growth, refill, ``dist`` and the result dict are the same.
+        ``small``: a small store of plain propagators of any kind (at most 128 slots and 2048 elementary filters, no formula units — the
+        Golomb network): the trees run in pcp_dfs_forest_device_small, one per wavefront (last_plan: path 4); no ``dirty`` rows either.
+        Together with ``formulas`` it is a ValueError: a store is one or the other."""
         import torch
+        if small and formulas:
+            raise ValueError("dfs_forest: small=True and formulas=True name two different forests (a store has formula units or it has none)")
         dev = torch.device("cuda", self.device)
         V = self.n_vars
         to_dev = lambda x: (torch.from_numpy(np.ascontiguousarray(x, np.int32)) if isinstance(x, np.ndarray) else x).to(dev).reshape(-1, V)
@@ -490,7 +497,7 @@ class Context:
         status = torch.zeros((T, capacity), dtype=torch.uint8, device=dev)
         counters = torch.zeros((T, 5), dtype=torch.int64, device=dev)
         sol = torch.zeros((T, V), dtype=torch.int32, device=dev) if want_solution else None
-        dirty = torch.full((T, capacity), -1, dtype=torch.int32, device=dev) if (hints and not formulas) else None  # pcp_dfs_state.dirty: one word per stack row
+        dirty = torch.full((T, capacity), -1, dtype=torch.int32, device=dev) if (hints and not formulas and not small) else None  # pcp_dfs_state.dirty: one word per stack row
         from .search_forest import ForestStacks, run_forest_loop
         stream = torch.cuda.current_stream(dev).cuda_stream
         box = {}
@@ -503,7 +510,7 @@ class Context:
         del lb, ub, status, dirty
         point(fs)
 
-        entry = self._L.pcp_dfs_forest_device_form if formulas else self._L.pcp_dfs_forest_device
+        entry = self._L.pcp_dfs_forest_device_small if small else (self._L.pcp_dfs_forest_device_form if formulas else self._L.pcp_dfs_forest_device)
 
         def launch():
             if _call is not None:  # (dfs_forest_bnb: the same loop over another entry point)
@@ -525,13 +532,15 @@ class Context:
 
     def dfs_forest_bnb(self, root_lb, root_ub, objective, best0=None, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
                        max_launches: int = 1 << 30, node_budget: int = 0, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
-                       sp0=None):
+                       sp0=None, small: bool = False):
         """pcp_dfs_forest_device_form_bnb: branch and bound (branch_and_bound.rs:64-84) in the forest over an Interval store with formula
         propagators — the loop, stacks, growth and refill of dfs_forest(formulas=True), every popped row entered with the forest's incumbent
         (one device word) folded into the objective's bounds.  ``objective`` = (var, "min" | "max").  ``best0``: a known bound to start from
         (only solutions that beat it are found).  Returns the dict of dfs_forest plus ``best`` (None: no tree found a solution),
         ``best_solution`` (the row of the lowest tree whose value is ``best``) and ``tree_best`` ([n_trees]; a tree without a solution: the
-        "no solution yet" value)."""
+        "no solution yet" value).
+        ``small``: the store is a small one of plain propagators (dfs_forest(small=True)): the same loop and result over
+        pcp_dfs_forest_device_small_bnb."""
         import torch
         var, mode = objective
         if mode not in OBJ_MODES:
@@ -545,10 +554,11 @@ class Context:
         obj = ForestObjective(int(var) & 0xFFFFFFFF, OBJ_MODES[mode], d_best.data_ptr(), tree_best.data_ptr(), tree_row.data_ptr())
 
         def call(st, n_trees, stream):
-            return self._L.pcp_dfs_forest_device_form_bnb(self._h, C.byref(st), n_trees, C.byref(obj), int(steps_per_launch), int(node_limit_per_tree), C.c_void_p(stream))
+            entry = self._L.pcp_dfs_forest_device_small_bnb if small else self._L.pcp_dfs_forest_device_form_bnb
+            return entry(self._h, C.byref(st), n_trees, C.byref(obj), int(steps_per_launch), int(node_limit_per_tree), C.c_void_p(stream))
 
         out = self.dfs_forest(root_lb, root_ub, node_limit_per_tree=node_limit_per_tree, steps_per_launch=steps_per_launch, capacity=capacity, max_launches=max_launches,
-                              node_budget=node_budget, rebalance=rebalance, info=info, dist=dist, max_capacity=max_capacity, sp0=sp0, formulas=True, _call=call)
+                              node_budget=node_budget, rebalance=rebalance, info=info, dist=dist, max_capacity=max_capacity, sp0=sp0, formulas=not small, small=small, _call=call)
         tb = tree_best.cpu().numpy()
         found = tb != none
         out["tree_best"] = tb

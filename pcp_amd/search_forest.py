@@ -313,14 +313,17 @@ STACK_BYTES_CAP = 64 << 30  # default ceiling of the forest's stack rows per GPU
 
 
 def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_per_launch: int = 512, rank: int = 0, world: int = 1, capacity: int = 0,
-                  dist=None, info: dict | None = None, stack_bytes: int = STACK_BYTES_CAP, formulas: bool = False) -> dict:
+                  dist=None, info: dict | None = None, stack_bytes: int = STACK_BYTES_CAP, formulas: bool = False, small: bool = False) -> dict:
     """Interval mode, all-XNeqY models: expansion + one in-kernel DFS per open node (pcp_dfs_forest_device).  formulas: the store holds
-    formula propagators (what Cumulative.join builds): the trees run in pcp_dfs_forest_device_form, one per wavefront.  The node limit is checked
+    formula propagators (what Cumulative.join builds): the trees run in pcp_dfs_forest_device_form, one per wavefront.  small: a small store of
+    plain propagators of any kind (the Golomb network): pcp_dfs_forest_device_small, one tree per wavefront; with formulas=True a ValueError.  The node limit is checked
     between launches, so `nodes` can exceed it by less than one launch; it is the exact count.  Without ``dist`` every tree also stops at
     its share of the limit; with ``dist`` (torch.distributed, world ranks) the limit is global, finished trees are refilled (also across
     ranks) and the returned counters are still this rank's.  A tree's stack holds its OPEN nodes (one right branch per level of
     its current path); the rows are allocated on demand (ForestStacks.grow) up to ``stack_bytes`` for the whole forest — a tree
     that needs more reports error 1."""
+    if small and formulas:
+        raise ValueError("forest_search: small=True and formulas=True name two different forests (a store has formula units or it has none)")
     rl, ru, st = seed_roots_interval(ctx, lb0, ub0, n_trees * world)
     ml, mu = rl[rank::world].contiguous(), ru[rank::world].contiguous()
     out = {"seeded_nodes": st.num_nodes if rank == 0 else 0, "trees": int(ml.shape[0]), "launches": 0,
@@ -356,21 +359,23 @@ def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_
             upfront = max(upfront, torch.cuda.mem_get_info(ml.device)[0] // 8)
         capacity = ceiling if (per_tree and not multi and ceiling * row_bytes <= upfront) else min(128, ceiling)
     r = ctx.dfs_forest(ml, mu, node_limit_per_tree=0 if multi else per_tree, steps_per_launch=steps_per_launch, capacity=capacity, max_capacity=max(ceiling, capacity),
-                       node_budget=max(node_limit - st.num_nodes, 1) if multi else budget, dist=dist if multi else None, info=info, sp0=sp0, formulas=formulas)
+                       node_budget=max(node_limit - st.num_nodes, 1) if multi else budget, dist=dist if multi else None, info=info, sp0=sp0, formulas=formulas, small=small)
     out["nodes"] += r["nodes"]; out["solutions"] += r["solutions"]; out["failed"] += r["failed"]
     out["error"] = r["error"]; out["launches"] = r["launches"]
     return out
 
 
 def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: int = 512, best0=None, capacity: int = 128, max_capacity: int = 1 << 16,
-               info: dict | None = None, formulas: bool = True) -> dict:
+               info: dict | None = None, formulas: bool = True, small: bool = False) -> dict:
     """Branch and bound over an Interval store with formula propagators (branch_and_bound.rs:64-84 around the loop of forest_search):
     minimize / maximize ``objective`` = (var, "min" | "max") below (lb0, ub0).  The root is expanded breadth-first under branch and bound
     (seed_roots_interval with DeviceSearch(objective=)) to at least ``n_trees`` open nodes; each becomes a tree of
     Context.dfs_forest_bnb, and the expansion's incumbent — or ``best0``, whichever is better — is the forest's first one, so the
     expansion's solutions take part.  Returns the dict of Context.dfs_forest_bnb (``nodes`` / ``solutions`` / ``failed`` include the
-    expansion's, ``seeded_nodes`` names them); ``best`` is None when neither the expansion nor a tree found a solution beating ``best0``."""
-    if not formulas:
+    expansion's, ``seeded_nodes`` names them); ``best`` is None when neither the expansion nor a tree found a solution beating ``best0``.
+    ``small``: a small store of plain propagators instead (Context.dfs_forest_bnb(small=True) — model.golomb_ruler); it wins over
+    ``formulas``, whose default is True."""
+    if not formulas and not small:
         raise ValueError("forest_bnb searches stores with formula propagators (all-XNeqY stores have no objective to bound)")
     var, mode = objective
     rl, ru, st = seed_roots_interval(ctx, lb0, ub0, n_trees, objective=(int(var), mode))
@@ -383,7 +388,7 @@ def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: i
                "best": None, "best_solution": None}
     else:
         out = ctx.dfs_forest_bnb(rl, ru, (int(var), mode), best0=start, steps_per_launch=steps_per_launch, capacity=capacity,
-                                 max_capacity=max(max_capacity, capacity), info=info)
+                                 max_capacity=max(max_capacity, capacity), info=info, small=small)
     out["seeded_nodes"] = st.num_nodes
     out["nodes"] += st.num_nodes; out["solutions"] += st.num_solution; out["failed"] += st.num_failed_node
     # no tree beat the expansion's incumbent: it is the optimum, unless the caller's bound was already as good
