@@ -352,6 +352,9 @@ int32_t pcp_propagate_device_bnb(pcp_ctx* ctx, uint32_t n_nodes, const pcp_devic
  *   child_lb/child_ub : [2*n_nodes][n_vars] (capacity);  child_active : [2*n_nodes][ceil(n_units/64)]
  *   counts            : device uint32[5] out = { n_children, n_true, n_false, n_unknown, n_other } — n_other counts nodes whose
  *                       status is none of the three (PCP_STATUS_HULL: a node the engine refused); a driver should stop on it
+ * Rows at or past n_children are not written.  A PCP_UNKNOWN node in which every variable is assigned has nothing to split (the
+ * reference panics, first_smallest_var.rs:36; a propagated node is never one): its two children are plain copies of it, and
+ * child_dirty holds 0xFFFFFFFF for both.
  * Nothing is synchronised; read `counts` after synchronising hip_stream. */
 int32_t pcp_branch_device(pcp_ctx* ctx, uint32_t n_nodes, const int32_t* lb, const int32_t* ub, const uint64_t* active,
                           const uint8_t* status, int32_t* child_lb, int32_t* child_ub, uint64_t* child_active,
