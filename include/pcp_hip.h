@@ -334,6 +334,27 @@ typedef struct {
   uint32_t reserved;
 } pcp_objective;
 int32_t pcp_propagate_device_bnb(pcp_ctx* ctx, uint32_t n_nodes, const pcp_device_batch* batch, const pcp_objective* obj, void* hip_stream);
+/* Node exclusions on SMALL stores of ANY plain model, optionally under branch and bound — Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>
+ * (search/branching/enumerate.rs:33-60) over the stores pcp_propagate_device_units serves, on the lists pcp_branch_device_excl writes, with or
+ * without BranchAndBound around it (search/branch_and_bound.rs:64-84).  (Added without a new ABI number: no layout changed.)
+ *   excl_off, excl : as for pcp_propagate_device_excl — node i is propagated as if  XNeqY(Identity(var), Constant(value))  had been allocated behind
+ *                    the model's propagators once for each entry of  excl[excl_off[i] .. excl_off[i + 1])  (search/branching/branch.rs:36-55): a value
+ *                    is removed only at a bound, x assigned to it gives PCP_FALSE (x_neq_y.rs:82-93); an exclusion is entailed iff its value lies
+ *                    outside [lb, ub] (x_neq_y.rs:71-73), and one that is not keeps the node PCP_UNKNOWN.  excl_off[0] need not be 0 (a slice of a
+ *                    larger CSR); excl_off == NULL: no node has any.  Any number per node, duplicates and any order are allowed.  An entry with
+ *                    var >= n_vars refuses that node only (PCP_STATUS_HULL, outputs untouched, sticky flag).  pcp_stats: every test of an entry is
+ *                    one step.
+ *   obj            : NULL: no branch and bound.  Otherwise the pcp_objective of pcp_propagate_device_bnb (best_bits unused), with its FOLD / EMPTY /
+ *                    REDUCE contract, the fold done while each node is staged (no launch in front of the fixpoint): Minimize  ub = min(ub, best - 1),
+ *                    Maximize  lb = max(lb, best + 1);  a node the fold would empty comes out PCP_FALSE with its *_out row equal to its *_in row,
+ *                    in place or not.  var >= n_vars, an unknown mode, a null best, reserved != 0: PCP_ERR_ARG.
+ * Accepted: interval mode, int32 rows, implicit nodes (active_in == NULL; active_out on request), a store without formula propagators of at most
+ * 128 variables (interned constants included) and 2048 elementary filters that fits LDS — the one-wavefront-per-node kernel, plan.path 4; an
+ * all-XNeqY model within those limits too.  dirty_var is ignored (every node is swept as a whole).  Anything else returns PCP_ERR_UNSUPPORTED
+ * with a message: set mode, formula propagators, a larger store, cell_format != 0, active_in, the device DFS stack.
+ * Enqueued on hip_stream, not synchronised, no host read-back. */
+int32_t pcp_propagate_device_small_excl(pcp_ctx* ctx, uint32_t n_nodes, const pcp_device_batch* batch, const uint32_t* excl_off, const pcp_excl* excl,
+                                        const pcp_objective* obj, void* hip_stream);
 /* One context = one queue of launches: the device-side scratch behind a launch (counters, team words, `active` scratch, the tile tickets of the
  * persistent kernels) belongs to the context, so the launches of one context must not overlap on the device — enqueue them on one stream, or order
  * the streams; concurrent launches take one context each (the model is uploaded per context).  The tile tickets are guarded at run time as well:

@@ -164,6 +164,20 @@ pub struct pcp_forest_objective {
     pub tree_row: *mut i32,   // [n_trees][n_vars] or null
 }
 
+/// The objective of `pcp_propagate_device_small_excl` (and of the header's `pcp_propagate_device_bnb`): branch and bound around a batch.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct pcp_objective {
+    pub var: u32,
+    pub mode: u32,            // PCP_MINIMIZE / PCP_MAXIMIZE
+    pub best: *mut i32,       // device int32[1], in/out: the incumbent
+    pub best_lb: *mut i32,    // device [n_vars] or null: the row of the node that set it
+    pub best_ub: *mut i32,
+    pub best_bits: *mut u64,  // set mode only
+    pub improved: *mut u32,   // device u32[1] or null: +1 per call that improved the incumbent
+    pub reserved: u32,        // 0
+}
+
 /// `pcp_debug_counters` slots (ABI v6): which code paths ran since the last `pcp_stats_reset`.
 pub const PCP_DBG_BIG_DENSE: usize = 0;
 pub const PCP_DBG_BIG_SPARSE: usize = 1;
@@ -195,6 +209,10 @@ extern "C" {
     pub fn pcp_propagate_device_units(ctx: *mut pcp_ctx, n_nodes: u32, batch: *const pcp_device_batch, node_unit_off: *const u32,
                                       node_units: *const pcp_prop, hip_stream: *mut c_void) -> i32;
     pub fn pcp_propagate_device_excl(ctx: *mut pcp_ctx, n_nodes: u32, batch: *const pcp_device_batch, excl_off: *const u32, excl: *const pcp_excl, hip_stream: *mut c_void) -> i32; // Enumerate's x != v on the all-XNeqY kernel
+    /// The same on small stores of any plain model (one wavefront per node), `obj` null or the objective of a branch and bound whose
+    /// incumbent is folded into every node as it is staged (search/branching/enumerate.rs:33-60 under search/branch_and_bound.rs:64-84).
+    pub fn pcp_propagate_device_small_excl(ctx: *mut pcp_ctx, n_nodes: u32, batch: *const pcp_device_batch, excl_off: *const u32, excl: *const pcp_excl,
+                                           obj: *const pcp_objective, hip_stream: *mut c_void) -> i32;
     pub fn pcp_branch_device(ctx: *mut pcp_ctx, n_nodes: u32, lb: *const i32, ub: *const i32, active: *const u64, status: *const u8,
                              child_lb: *mut i32, child_ub: *mut i32, child_active: *mut u64, counts: *mut u32,
                              hip_stream: *mut c_void) -> i32; // Brancher<FirstSmallestVar, MiddleVal, BinarySplit>::enter

@@ -14,7 +14,8 @@
 //                     PCP_STATUS_HULL), takes the best lb_out[var] of the PCP_TRUE nodes as a (key, index) minimum, and when it beats the
 //                     incumbent writes the incumbent, copies the winning row(s) and bumps `improved`.
 // Both are a few microseconds at any batch size the drivers use; the fixpoint between them is untouched (fusing the fold into each kernel
-// family's staging is left for later).  Vector memory operations only.
+// family's staging is left for later; smallexcl_kernel<true>, pcp_smallexcl.hip, does fold while it stages and leaves the marks for the reduce).
+// Vector memory operations only.
 #include "pcp_internal.h"
 
 namespace pcp {

@@ -140,18 +140,23 @@ def bfs_frontier(ctx, lb0: np.ndarray, ub0: np.ndarray, n_open: int, max_rounds:
     return L[ok][:n_open], U[ok][:n_open], (None if A is None else A[ok][:n_open]), st
 
 
-def _search(kind, root, all_solutions: bool, node_limit: int, batch: int, obj=None) -> SearchStats:
+def _search(kind, root, all_solutions: bool, node_limit: int, batch: int, obj=None, rows_up: bool = False) -> SearchStats:
     """The depth-first loop of dfs / dfs_set / dfs_enumerate over a LIFO stack of open nodes.  ``kind`` says what a node is:
     ``kind.propagate(st, take, obj)`` stacks the popped nodes, propagates them (counting launches and filter steps in ``st``) and returns
-    (lb rows, status, the propagated batch); ``kind.branch(batch, unk)`` returns the children of its rows ``unk``: two nodes per row, left then right."""
+    (lb rows, status, the propagated batch); ``kind.branch(batch, unk)`` returns the children of its rows ``unk``: two nodes per row, left then right.
+    ``rows_up``: a batch is the top ``batch`` nodes in the order of their rows on DeviceSearch's stack, the lowest first — the children of the
+    LOWEST Unknown node end on top, a tie between solutions goes to the lowest, the node that reaches a limit is the lowest.  Under branch and
+    bound the order in which the nodes of a batch are entered decides what the next batch is bounded by, so a host specification of
+    DeviceSearch(objective=) has to take them as it does; with batch = 1 both orders are the reference's."""
     st = SearchStats()
     all_solutions = all_solutions or obj is not None
     stack = [root]
     while stack:
-        take = stack[-batch:][::-1]  # top of the stack first
+        take = stack[-batch:] if rows_up else stack[-batch:][::-1]  # top of the stack first (rows_up: last)
         del stack[-batch:]
         if node_limit:
-            take = take[: max(0, node_limit - st.num_nodes)]
+            left = max(0, node_limit - st.num_nodes)
+            take = take[len(take) - min(left, len(take)):] if rows_up else take[:left]  # the `left` nodes nearest the top
             if not take:
                 break
         lb, status, done_batch = kind.propagate(st, take, obj)
@@ -160,7 +165,7 @@ def _search(kind, root, all_solutions: bool, node_limit: int, batch: int, obj=No
         if at_limit:
             # StopNode hands EndOfSearch to the monitor for the node that reaches the limit (stop_node.rs:57-62 under Monitor,
             # stop_node.rs:90-97): it is counted as a node, never as a solution or a failure
-            status[-1] = UNKNOWN
+            status[0 if rows_up else -1] = UNKNOWN
         st.num_failed_node += int((status == FALSE).sum())
         true = np.nonzero(status == TRUE)[0]
         st.num_solution += len(true)
@@ -281,18 +286,34 @@ def branch_enumerate(lb: np.ndarray, ub: np.ndarray, excl_off=None, excl=None, v
 
 
 class _ExclRows:
-    """A node is (lb, ub, exclusions [k, 2], dirty variable), propagated on torch tensors through ``ctx.propagate_device_excl``.  There is no
-    objective and no emptiness check: the children of branch_enumerate are never empty."""
+    """A node is (lb, ub, exclusions [k, 2], dirty variable), propagated on torch tensors through ``ctx.propagate_device_excl`` (an all-XNeqY
+    model without an objective) or ``ctx.propagate_device_small_excl`` (``small``: any other small store, and every search with an objective).
+    The children of branch_enumerate are never empty; with an objective the incumbent is folded into the bounds here, as _IntervalRows does,
+    and a node the fold empties is failed without a launch."""
 
-    def __init__(self, ctx, val, record, hints):
+    def __init__(self, ctx, val, record, hints, small=False):
         import torch
-        self.torch, self.ctx, self.val, self.record, self.hints = torch, ctx, val, record, hints
-        self.dev = torch.device("cuda", ctx.device)
-        self.stream = torch.cuda.current_stream(self.dev).cuda_stream
+        self.torch, self.ctx, self.val, self.record, self.hints, self.small = torch, ctx, val, record, hints, small
+        on_gpu = getattr(ctx, "device", 0) != "cpu"  # (the CPU tests drive this class with an oracle-backed stand-in context)
+        self.dev = torch.device("cuda", ctx.device) if on_gpu else torch.device("cpu")
+        self.stream = torch.cuda.current_stream(self.dev).cuda_stream if on_gpu else 0
 
     def propagate(self, st, take, obj):
-        torch, dev = self.torch, self.dev
         L, U = (np.stack([t[i] for t in take]) for i in (0, 1))
+        if obj is None or st.best is None:
+            return self._launch(st, take, L, U)
+        if obj[1]:  # the bound propagator, folded
+            U[:, obj[0]] = np.minimum(U[:, obj[0]], st.best - 1)
+        else:
+            L[:, obj[0]] = np.maximum(L[:, obj[0]], st.best + 1)
+        ok = np.nonzero((L <= U).all(axis=1))[0]
+        lb, ub, status = L.copy(), U.copy(), np.zeros(L.shape[0], np.uint8)
+        if len(ok):
+            lb[ok], status[ok], (_, ub[ok], _) = self._launch(st, [take[i] for i in ok], L[ok], U[ok])
+        return lb, status, (lb, ub, take)
+
+    def _launch(self, st, take, L, U):
+        torch, dev = self.torch, self.dev
         N = L.shape[0]
         off = np.zeros(N + 1, np.int32)
         off[1:] = np.cumsum([len(t[2]) for t in take])
@@ -301,8 +322,11 @@ class _ExclRows:
         t_st = torch.zeros(N, dtype=torch.uint8, device=dev)
         t_off = torch.from_numpy(off).to(dev)
         t_ex = torch.from_numpy(flat if len(flat) else np.zeros((1, 2), np.int32)).to(dev)  # (never a null pointer: an empty list is offsets alone)
-        t_dirty = torch.tensor([t[3] for t in take], dtype=torch.int32, device=dev) if self.hints else None
-        self.ctx.propagate_device_excl(N, t_lb, t_ub, t_lb, t_ub, None, t_st, t_off, t_ex, self.stream, dirty=t_dirty)
+        t_dirty = torch.tensor([t[3] for t in take], dtype=torch.int32, device=dev) if (self.hints and not self.small) else None
+        if self.small:
+            self.ctx.propagate_device_small_excl(N, t_lb, t_ub, t_lb, t_ub, None, t_st, t_off, t_ex, None, self.stream)
+        else:
+            self.ctx.propagate_device_excl(N, t_lb, t_ub, t_lb, t_ub, None, t_st, t_off, t_ex, self.stream, dirty=t_dirty)
         lb, ub, status = t_lb.cpu().numpy(), t_ub.cpu().numpy(), t_st.cpu().numpy()
         st.launches += 1
         if (status > UNKNOWN).any():
@@ -321,15 +345,23 @@ class _ExclRows:
 
 
 def dfs_enumerate(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = False, node_limit: int = 0, batch: int = 1, val: str = "middle",
-                  record: Optional[list] = None, hints: bool = True) -> SearchStats:
+                  record: Optional[list] = None, hints: bool = True, objective=None) -> SearchStats:
     """The batched host-stepped depth-first search of ``dfs`` under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>: the top
     ``batch`` open nodes go through ``ctx.propagate_device_excl`` in one launch, each with its own exclusions (and, with ``hints``, the
     variable it was branched on as its dirty-variable hint).  ``record``: a list that receives, per node in the order propagated,
-    (lb_in, ub_in, exclusions [k, 2], status, lb_out, ub_out)."""
-    kind, V = _ExclRows(ctx, val, record, hints), ctx.n_vars
+    (lb_in, ub_in, exclusions [k, 2], status, lb_out, ub_out).
+    A model that is not all-XNeqY (``ctx.all_neq``) — a small store of any plain propagators, the Golomb network — goes through
+    ``ctx.propagate_device_small_excl`` instead (no hints: that kernel sweeps a node as a whole).  So does every search with an
+    ``objective`` (as in dfs: BranchAndBound wraps any brancher, branch_and_bound.rs:64-84): the bound is folded into a node's bounds before
+    its propagation exactly as under BinarySplit; this is the host specification of DeviceSearch(brancher="enumerate", objective=), so a
+    batch is taken in the order of DeviceSearch's rows (``rows_up`` of _search): the same nodes, solutions, failures and incumbents at every
+    batch size."""
+    obj = _objective(objective)
+    small = obj is not None or not getattr(ctx, "all_neq", True)
+    kind, V = _ExclRows(ctx, val, record, hints, small), ctx.n_vars
     steps0 = ctx.stats_read(kind.stream)
     root = (np.ascontiguousarray(lb0, np.int32).reshape(V), np.ascontiguousarray(ub0, np.int32).reshape(V), np.zeros((0, 2), np.int32), -1)
-    st = _search(kind, root, all_solutions, node_limit, batch)
+    st = _search(kind, root, all_solutions, node_limit, batch, obj, rows_up=obj is not None)
     steps1 = ctx.stats_read(kind.stream)
     st.filter_steps = (steps1["steps"] + steps1["steps3"]) - (steps0["steps"] + steps0["steps3"])  # over the whole call, not per launch
     return st

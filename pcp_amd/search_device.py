@@ -10,7 +10,10 @@ search/branch_and_bound.rs:64-84): the incumbent stays on the device, is folded 
 and replaced by the batch's best Satisfiable node after it; it comes back in the same copy as the counts.
 With ``brancher="enumerate"`` the round is `pcp_propagate_device_excl` + `pcp_branch_device_excl` (Brancher<FirstSmallestVar, MiddleVal | MinVal,
 Enumerate>, search/branching/enumerate.rs:33-60): every open node owns a list of value exclusions, the lists live in a device arena next to the
-rows and are written by the brancher — rows, hints and lists stay on the GPU from the root to the leaves.  Over a set-mode context the same
+rows and are written by the brancher — rows, hints and lists stay on the GPU from the root to the leaves.  A model that is not all-XNeqY (a
+small store of any plain propagators: the Golomb network) and every Enumerate search with an ``objective`` propagate through
+`pcp_propagate_device_small_excl` instead: the same lists on the one-wavefront-per-node kernel, the incumbent folded as a node is staged and
+reduced behind the launch (no hints: that kernel sweeps a node as a whole).  Over a set-mode context the same
 ``brancher="enumerate"`` needs none of that: x = v and x != v are exact operations on the sets, so the round is `pcp_propagate_device` +
 `pcp_branch_device_set_enum` on the rows of the BinarySplit search (no arena, no hints).
 PyTorch provides the device buffers; every kernel is this repository's.
@@ -174,7 +177,10 @@ class _Enumerate(_Int32Rows):
         (start, length), (o, e0, cnt, emax) = s.segs[-1], s.esegs[-1]
         k = lo - start  # the batch's first row within its segment
         lb, ub, poff, pex, etop, oc = s.lb[lo:top], s.ub[lo:top], s.eoff[o + k:o + length + 1], s.ex[e0:], e0 + cnt, o + length + 1
-        ctx.propagate_device_excl(n, lb, ub, lb, ub, None, status, poff, pex, stream, dirty=_cut(s.dirty, lo, top))
+        if s.enum_small:
+            ctx.propagate_device_small_excl(n, lb, ub, lb, ub, None, status, poff, pex, None if s.objective is None else s._obj, stream)
+        else:
+            ctx.propagate_device_excl(n, lb, ub, lb, ub, None, status, poff, pex, stream, dirty=_cut(s.dirty, lo, top))
         ctx.branch_device_excl(n, lb, ub, status, poff, pex, s.val, s.lb[top:], s.ub[top:], s.eoff[oc:], s.ex[etop:], s.ecap - etop, s.counts, stream,
                                child_dirty=_cut(s.dirty, top))
         s.round_buf[8:9].copy_(s.eoff[o + k:o + k + 1])  # where the popped nodes' entries begin: what the segment keeps
@@ -214,8 +220,10 @@ class DeviceSearch:
                 raise ValueError(f"val must be 'middle' or 'min', not {val!r}")
             if cells:
                 raise ValueError("Enumerate runs on int32 rows: cells=True is refused")
-            if objective is not None:
-                raise ValueError("Enumerate takes no objective (branch and bound runs under BinarySplit)")
+            if objective is not None and getattr(ctx, "set_words", 0):
+                raise ValueError("Enumerate takes no objective in set mode (branch and bound runs under BinarySplit there; forest_bnb_set(brancher=\"enumerate\") is the set-mode column)")
+            if objective is not None and not hasattr(ctx, "propagate_device_small_excl"):
+                raise ValueError("Enumerate with an objective needs a context that offers propagate_device_small_excl (pcp_propagate_device_small_excl): this one does not")
             if getattr(ctx, "set_words", 0) and not getattr(ctx, "supports_set_enumerate", False):
                 raise ValueError("Enumerate in set mode needs a context that offers branch_device_set_enum (pcp_branch_device_set_enum): this one does not")
             if not implicit and ctx.words:
@@ -254,7 +262,9 @@ class DeviceSearch:
         # one hint per open node (pcp_device_batch.dirty_var): a child is its parent's fixpoint with ONE variable branched on, so the engine
         # may start the child's propagation from that variable alone; the root has none (-1).  Interval mode, implicit nodes, an engine
         # that knows the field (the CPU stand-in of the tests does not).
-        want = bool(getattr(ctx, "supports_hints", False)) and self.implicit and not self.set_words and self.objective is None  # (bnb: no hints)
+        # Enumerate on pcp_propagate_device_small_excl: an objective, or a model that is not all-XNeqY (a context that does not say is taken as all-XNeqY)
+        self.enum_small = brancher == "enumerate" and not self.set_words and (self.objective is not None or not getattr(ctx, "all_neq", True))
+        want = bool(getattr(ctx, "supports_hints", False)) and self.implicit and not self.set_words and self.objective is None and not self.enum_small  # (bnb, small stores: no hints)
         self.dirty = torch.full((self.cap,), -1, dtype=i32, device=self.dev) if (want if hints is None else (hints and want)) else None
         self.status = torch.zeros(self.batch, dtype=u8, device=self.dev)
         self.segs: List[List[int]] = []  # [start, length], bottom to top
@@ -262,10 +272,12 @@ class DeviceSearch:
         self.kind = ((_SetsEnumerate(self) if self.set_words else _Enumerate(self, excl_capacity)) if brancher == "enumerate"
                      else _Cells(self) if self.cells else _Sets(self) if self.set_words else _Int32Rows(self))
         # what a round brings back, side by side: its one copy to the host reads all of it
-        self.round_buf = torch.zeros(9, dtype=i32, device=self.dev)
+        # (under Enumerate words 5 .. 8 are the brancher's and the arena's: the incumbent and the improvement count follow them)
+        self._ibest = 9 if (self.objective is not None and self.kind.n_counts > 5) else 5
+        self.round_buf = torch.zeros(max(9, self._ibest + 2), dtype=i32, device=self.dev)
         self.counts = self.round_buf[:self.kind.n_counts]
         if self.objective is not None:
-            self.best, self.improved = self.round_buf[5:6], self.round_buf[6:7]
+            self.best, self.improved = self.round_buf[self._ibest:self._ibest + 1], self.round_buf[self._ibest + 1:self._ibest + 2]
             self.best_lb, self.best_ub = torch.zeros(V, dtype=i32, device=self.dev), torch.zeros(V, dtype=i32, device=self.dev)
             self.best_bits = torch.zeros((V, self.set_words), dtype=i64, device=self.dev) if self.set_words else None
             self._obj = {"var": self.objective[0], "mode": self.objective[1], "best": self.best, "best_lb": self.best_lb, "best_ub": self.best_ub,
@@ -404,10 +416,10 @@ class DeviceSearch:
             if n_other:
                 raise RuntimeError(f"{n_other} nodes were refused by the engine (bounds outside the declared hull): the search cannot continue")
             kind.check(buf)
-            if bnb and buf[6] != self._improved_seen:
-                self._improved_seen = buf[6]
-                st.best = buf[5]
-                st.incumbents.append(buf[5])
+            if bnb and buf[self._ibest + 1] != self._improved_seen:
+                self._improved_seen = buf[self._ibest + 1]
+                st.best = buf[self._ibest]
+                st.incumbents.append(buf[self._ibest])
             st.rounds += 1
             st.num_nodes += n
             s_last = None
