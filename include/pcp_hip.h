@@ -355,6 +355,24 @@ int32_t pcp_propagate_device_bnb(pcp_ctx* ctx, uint32_t n_nodes, const pcp_devic
  * Enqueued on hip_stream, not synchronised, no host read-back. */
 int32_t pcp_propagate_device_small_excl(pcp_ctx* ctx, uint32_t n_nodes, const pcp_device_batch* batch, const uint32_t* excl_off, const pcp_excl* excl,
                                         const pcp_objective* obj, void* hip_stream);
+/* Node exclusions on stores WITH FORMULA UNITS, optionally under branch and bound — the same distributor over the stores pcp_model_push_formula
+ * builds (schedules: propagators::Cumulative::join, cumulative.rs:59-114), which the two entries above refuse.  (Added without a new ABI number:
+ * no layout changed.)
+ *   excl_off, excl : as for pcp_propagate_device_small_excl, entry for entry: XNeqY(Identity(var), Constant(value)) behind the model's units; a value
+ *                    is removed only at a bound, x assigned to it gives PCP_FALSE, an entry whose value lies inside [lb, ub] keeps the node
+ *                    PCP_UNKNOWN even when every unit is entailed.  excl_off[0] need not be 0; excl_off == NULL: no node has any, and the call is
+ *                    pcp_propagate_device on the same rows.  An entry with var >= n_vars refuses that node only (PCP_STATUS_HULL, outputs
+ *                    untouched, sticky flag).  pcp_stats: every test of an entry is one step.
+ *   obj            : as for pcp_propagate_device_small_excl (NULL: no branch and bound; the fold is done while each node is staged, a node the
+ *                    fold would empty comes out PCP_FALSE with its *_out row equal to its *_in row).  var >= n_vars, an unknown mode, a null
+ *                    best, reserved != 0: PCP_ERR_ARG.
+ * Accepted: interval mode, int32 rows, implicit nodes (active_in == NULL; active_out on request), a store with formula propagators four nodes of
+ * which fit one CU's LDS (8 bytes per variable and node) — formfix_kernel's one-wavefront-per-node mapping, plan.path 3.  Anything else returns
+ * PCP_ERR_UNSUPPORTED with a message: set mode, a store without formula propagators (the two entries above serve those), cell_format != 0,
+ * active_in, the device DFS stack.
+ * Enqueued on hip_stream, not synchronised, no host read-back. */
+int32_t pcp_propagate_device_form_excl(pcp_ctx* ctx, uint32_t n_nodes, const pcp_device_batch* batch, const uint32_t* excl_off, const pcp_excl* excl,
+                                       const pcp_objective* obj, void* hip_stream);
 /* One context = one queue of launches: the device-side scratch behind a launch (counters, team words, `active` scratch, the tile tickets of the
  * persistent kernels) belongs to the context, so the launches of one context must not overlap on the device — enqueue them on one stream, or order
  * the streams; concurrent launches take one context each (the model is uploaded per context).  The tile tickets are guarded at run time as well:

@@ -213,6 +213,9 @@ extern "C" {
     /// incumbent is folded into every node as it is staged (search/branching/enumerate.rs:33-60 under search/branch_and_bound.rs:64-84).
     pub fn pcp_propagate_device_small_excl(ctx: *mut pcp_ctx, n_nodes: u32, batch: *const pcp_device_batch, excl_off: *const u32, excl: *const pcp_excl,
                                            obj: *const pcp_objective, hip_stream: *mut c_void) -> i32;
+    /// The same on stores WITH formula units (schedules: one wavefront per node, the lists swept next to the trees); `obj` as above.
+    pub fn pcp_propagate_device_form_excl(ctx: *mut pcp_ctx, n_nodes: u32, batch: *const pcp_device_batch, excl_off: *const u32, excl: *const pcp_excl,
+                                          obj: *const pcp_objective, hip_stream: *mut c_void) -> i32;
     pub fn pcp_branch_device(ctx: *mut pcp_ctx, n_nodes: u32, lb: *const i32, ub: *const i32, active: *const u64, status: *const u8,
                              child_lb: *mut i32, child_ub: *mut i32, child_active: *mut u64, counts: *mut u32,
                              hip_stream: *mut c_void) -> i32; // Brancher<FirstSmallestVar, MiddleVal, BinarySplit>::enter

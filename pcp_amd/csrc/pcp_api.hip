@@ -1450,6 +1450,66 @@ int32_t pcp_propagate_device_small_excl(pcp_ctx* c, uint32_t n_nodes, const pcp_
   return PCP_OK;
 }
 
+// ≡ Consistency::consistency for nodes of a store WITH formula units that carry value exclusions of their own (pcp_formexcl.hip: one wavefront
+// per node, the lists swept at the top of every round, then every live unit as a tree), optionally under branch and bound: the incumbent is
+// folded while a node is staged, bnb_reduce_kernel runs behind the launch on the marks the kernel leaves in d_bnb_empty.
+int32_t pcp_propagate_device_form_excl(pcp_ctx* c, uint32_t n_nodes, const pcp_device_batch* bt, const uint32_t* excl_off, const pcp_excl* excl,
+                                       const pcp_objective* obj, void* hip_stream) {
+  if (!c || !bt) return PCP_ERR_ARG;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  HIP_TRY(c, hipSetDevice(c->device));
+  int32_t rc = finalize_model(c);
+  if (rc) return rc;
+  c->ev_valid = false;
+  if (obj) {
+    if (obj->mode > PCP_MAXIMIZE || obj->reserved) return fail(c, PCP_ERR_ARG, "formula-store exclusions: unknown objective mode (or reserved != 0)");
+    if (obj->var >= c->n_vars) return fail(c, PCP_ERR_ARG, "formula-store exclusions: the objective variable is not a variable of the model");
+    if (!obj->best) return fail(c, PCP_ERR_ARG, "formula-store exclusions: best must not be null");
+  }
+  if (excl_off && !excl) return fail(c, PCP_ERR_ARG, "excl must not be null when excl_off is given");
+  if (n_nodes == 0) return PCP_OK;
+  if (!bt->status) return fail(c, PCP_ERR_ARG, "status must not be null");
+  if (bt->cell_format > PCP_CELLS_PACKED16 || bt->reserved) return fail(c, PCP_ERR_ARG, "unknown cell_format (or reserved != 0)");
+  if (c->set_words) return fail(c, PCP_ERR_UNSUPPORTED, "formula-store exclusions: interval mode only (set mode needs none: x != v is an exact set operation on `bits`)");
+  if (!c->has_formulas)
+    return fail(c, PCP_ERR_UNSUPPORTED, "formula-store exclusions: stores with formula propagators only (pcp_propagate_device_excl serves all-XNeqY models, "
+                                        "pcp_propagate_device_small_excl small stores of plain propagators)");
+  if (bt->cell_format) return fail(c, PCP_ERR_UNSUPPORTED, "formula-store exclusions: int32 rows only (cell_format PCP_CELLS_PACKED16 is refused)");
+  if (bt->active_in || !c->opt_implicit) return fail(c, PCP_ERR_UNSUPPORTED, "formula-store exclusions: implicit nodes only (active_in must be null)");
+  if (c->dfs_sp) return fail(c, PCP_ERR_UNSUPPORTED, "formula-store exclusions: not on the device DFS stack");
+  const uint32_t P = (uint32_t)c->props.size(), S = c->n_slots, V = c->n_vars, waves = 4;
+  const size_t lds = lds_bytes_formula(S, c->n_units, waves);
+  if (!lds || lds > c->lds_max)
+    return fail(c, PCP_ERR_UNSUPPORTED, "formula-store exclusions: four nodes of the store (8 bytes per variable each, one per wavefront) must fit one CU's LDS");
+  if (!bt->lb_in || !bt->ub_in || !bt->lb_out || !bt->ub_out) return fail(c, PCP_ERR_ARG, "domain pointers must not be null");
+  FormExclArgs x;
+  memset(&x, 0, sizeof(x));
+  FormArgs& a = x.f;
+  a.m.recs = c->d_recs; a.m.const_val = c->d_const; a.m.n_recs = P; a.m.n_vars = V; a.m.n_slots = S;
+  a.m.sums = SumTab{c->d_sum_off, c->d_sum_mem, V, c->n_sum_slots, c->d_mul_off};
+  a.nodes = c->d_fnodes; a.unit_root = c->d_unit_root; a.n_units = c->n_units; a.n_nodes = n_nodes; a.violation = c->d_retry + 1;
+  a.lb_in = bt->lb_in; a.ub_in = bt->ub_in; a.lb_out = bt->lb_out; a.ub_out = bt->ub_out;
+  a.active_out = bt->active_out; a.status = bt->status; a.stats = c->d_stats;
+  x.excl_off = excl_off; x.excl = excl;
+  if (obj) {
+    if ((rc = ensure(c, c->d_bnb_empty, c->cap_bnb_empty, n_nodes))) return rc;
+    x.obj_var = obj->var; x.obj_mode = obj->mode; x.obj_best = obj->best; x.empty = c->d_bnb_empty;
+  }
+  LaunchPlan plan;
+  plan.block = 64 * waves; plan.lds_bytes = lds;
+  const uint32_t per_cu = std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)(c->lds_max / lds), 2048u / plan.block));
+  plan.grid = std::min<uint32_t>((n_nodes + waves - 1) / waves, per_cu * (uint32_t)c->num_cu);
+  c->last_plan = pcp_plan{1u, 1u, 0u, 0u, 0u, 0u, 1u, 0u, plan.grid, plan.block, (uint32_t)plan.lds_bytes, 0u, 3u};
+  if (c->opt_time_kernels) HIP_TRY(c, hipEventRecord(c->ev_start, stream));
+  HIP_TRY(c, launch_formexcl(x, plan, stream));
+  if (c->opt_time_kernels) HIP_TRY(c, hipEventRecord(c->ev_stop, stream));
+  c->ev_valid = c->opt_time_kernels != 0;
+  if (obj)
+    HIP_TRY(c, launch_bnb_reduce(n_nodes, V, obj->var, obj->mode, c->d_bnb_empty, bt->status, bt->lb_out, bt->ub_out, nullptr, 0, obj->best, obj->best_lb, obj->best_ub,
+                                 nullptr, obj->improved, stream));
+  return PCP_OK;
+}
+
 // Branch and bound (pcp_bnb.hip): fold the incumbent into the objective's domain, the fixpoint of pcp_propagate_device on the folded rows,
 // then force the emptied nodes to PCP_FALSE and reduce the batch's PCP_TRUE nodes into the incumbent.  Rows not in place are copied to
 // *_out first: the fold narrows the rows the fixpoint then runs on in place.

@@ -107,6 +107,18 @@ struct FormArgs {
 size_t lds_bytes_formula(uint32_t n_slots, uint32_t n_units, uint32_t waves);  // one slice per wavefront (= per node in flight)
 hipError_t launch_formfix(const FormArgs& a, const LaunchPlan& p, hipStream_t stream);
 
+// Such stores whose implicit nodes carry value exclusions of their own, optionally under branch and bound (pcp_formexcl.hip,
+// pcp_propagate_device_form_excl): formfix_kernel's mapping; of `f`, active_in / sp_ptr / stop_ptr are not read.
+struct FormExclArgs {
+  FormArgs f;
+  const uint32_t* excl_off;   // [n_nodes + 1] CSR offsets into excl (the first need not be 0), or null: no node has any
+  const pcp_excl* excl;       //   x(var) != value, 8 bytes each
+  uint32_t obj_var, obj_mode; // branch and bound (obj_best != null): the objective variable (< n_vars), PCP_MINIMIZE / PCP_MAXIMIZE
+  const int32_t* obj_best;    //   device int32[1]: the incumbent, folded into the objective's cell as a node is staged; null = no objective
+  uint8_t* empty;             //   [n_nodes]: receives 1 where the fold would empty the node (PCP_FALSE, row unchanged), else 0: bnb_reduce_kernel's input
+};
+hipError_t launch_formexcl(const FormExclArgs& a, const LaunchPlan& p, hipStream_t stream);
+
 // The search loop over such a store on the device: one tree per WAVEFRONT on its own stack of (lb, ub) rows, the node being run in that
 // wavefront's LDS slice (pcp_formdfs.hip).  The stacks are a pcp_dfs_state laid out as for pcp_dfs_forest_device.
 struct FormDfsArgs {

@@ -25,7 +25,7 @@ ERRORS = {-1: "PCP_ERR_ARG", -2: "PCP_ERR_CONTRACT", -3: "PCP_ERR_HIP", -4: "PCP
 ABI_SYMBOLS = [
     "pcp_ctx_create", "pcp_ctx_destroy", "pcp_last_error", "pcp_strerror", "pcp_abi_version",
     "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull",
-    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
+    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
 ]
 
 
@@ -141,6 +141,7 @@ def load_library():
     L.pcp_propagate_device.argtypes = [vp, u32, C.POINTER(DeviceBatch), vp]
     L.pcp_propagate_device_excl.argtypes = [vp, u32, C.POINTER(DeviceBatch), vp, vp, vp]
     L.pcp_propagate_device_small_excl.argtypes = [vp, u32, C.POINTER(DeviceBatch), vp, vp, C.POINTER(Objective), vp]
+    L.pcp_propagate_device_form_excl.argtypes = [vp, u32, C.POINTER(DeviceBatch), vp, vp, C.POINTER(Objective), vp]
     L.pcp_propagate_device_bnb.argtypes = [vp, u32, C.POINTER(DeviceBatch), C.POINTER(Objective), vp]
     L.pcp_branch_device.argtypes = [vp, u32] + [vp] * 9
     L.pcp_branch_device_hint.argtypes = [vp, u32] + [vp] * 10
@@ -169,7 +170,7 @@ def load_library():
     L.pcp_last_plan.argtypes = [vp, C.POINTER(PcpPlan)]
     L.pcp_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
     for f in ("pcp_ctx_create", "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull", "pcp_model_set_hull",
-              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
+              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
         getattr(L, f).restype = i32
     _lib = L
     return L
@@ -216,6 +217,7 @@ class Context:
         self.supports_hints = True  # pcp_device_batch.dirty_var / pcp_branch_device_hint (ABI v7): search drivers keep a hint per open node
         self.supports_set_enumerate = True  # pcp_branch_device_set_enum / pcp_dfs_forest_device_set_enum: Enumerate over set-mode stores
         self._neq_flags = []  # per elementary filter pushed: an XNeqY outside a formula with a variable among its operands (all_neq)
+        self._form_flags = []  # per elementary filter pushed: a leaf of a formula unit, or a Boolean / BooleanNeg (has_formulas)
         for kv in filter(None, os.environ.get("PCP_SET_OPTIONS", "").split(",")):  # experiments: pcp_set_option on every new context (k=v,k=v)
             k_, v_ = kv.split("=")
             self.set_option(k_, int(v_))
@@ -240,7 +242,7 @@ class Context:
         self._check(self._L.pcp_model_reset(self._h, n_vars, int(set_words)))
         self.n_vars = int(n_vars)
         self.set_words = int(set_words)
-        self._neq_flags = []
+        self._neq_flags, self._form_flags = [], []
         for members in (sums or []):  # term::Sum views, numbered in order (pcp_model_push_sum)
             mv = np.ascontiguousarray(members, np.uint32)
             t = C.c_uint32()
@@ -254,13 +256,14 @@ class Context:
             x, y = props["var"][:, 0].astype(np.int64), props["var"][:, 1].astype(np.int64)
             plain = lambda v: (v < 0xC0000000) | (v == 0xFFFFFFFF)  # a variable or a Constant: no term::Sum view (PCP_SUM)
             self._neq_flags += ((props["kind"] == 0) & plain(x) & plain(y) & ((x < 0xC0000000) | (y < 0xC0000000))).tolist()
+            self._form_flags += (props["kind"] >= 7).tolist()  # PCP_BOOL, PCP_NBOOL
         self._refresh()
 
     # ---- the push interface pcp_amd.model.push_model drives (stores with formula propagators) ------------------------------
     def reset_model(self, n_vars: int, set_words: int = 0):
         self._check(self._L.pcp_model_reset(self._h, n_vars, int(set_words)))
         self.n_vars, self.set_words = int(n_vars), int(set_words)
-        self._neq_flags = []
+        self._neq_flags, self._form_flags = [], []
         self._refresh()
 
     def push_sum(self, members) -> int:
@@ -276,6 +279,7 @@ class Context:
         leaves = np.ascontiguousarray(leaves, dtype=PROP_DTYPE)
         self._check(self._L.pcp_model_push_formula(self._h, len(nodes), _np_ptr(nodes), len(leaves), _np_ptr(leaves)))
         self._neq_flags += [False] * len(leaves)
+        self._form_flags += [True] * len(leaves)
         self._refresh()
 
     def set_hull(self, lo: int, hi: int):
@@ -292,12 +296,19 @@ class Context:
         self.n_units, self.n_props = nu.value, npr.value
         self.words = (self.n_units + 63) // 64
         del self._neq_flags[self.n_props:]  # (truncate keeps a prefix of the filters)
+        del self._form_flags[self.n_props:]
 
     @property
     def all_neq(self) -> bool:
         """Every elementary filter of the store is a plain XNeqY with a variable among its operands: the models the assignment-driven kernel
         takes (pcp_propagate_device_excl).  The search drivers choose between that entry and pcp_propagate_device_small_excl by it."""
         return bool(self._neq_flags) and len(self._neq_flags) == self.n_props and all(self._neq_flags)
+
+    @property
+    def has_formulas(self) -> bool:
+        """The store holds a formula unit or a Boolean / BooleanNeg filter: it runs the tree kernels (last_plan path 3).  The search drivers send
+        such a store's Enumerate rounds to pcp_propagate_device_form_excl, every other store's where they went before."""
+        return any(self._form_flags)
 
     def set_option(self, key: str, value: int):
         self._check(self._L.pcp_set_option(self._h, key.encode(), int(value)))
@@ -393,6 +404,16 @@ class Context:
         ob = _objective_struct(objective)
         self._check(self._L.pcp_propagate_device_small_excl(self._h, n_nodes, C.byref(bt), _ptr(excl_off), _ptr(excl), None if ob is None else C.byref(ob),
                                                             C.c_void_p(stream_ptr)))
+
+    def propagate_device_form_excl(self, n_nodes: int, lb_in, ub_in, lb_out, ub_out, active_out, status, excl_off, excl, objective=None, stream_ptr: int = 0):
+        """pcp_propagate_device_form_excl: the batch of `propagate_device_small_excl` on a store WITH formula units (a schedule; four nodes of it
+        must fit LDS: the one-wavefront-per-node tree kernel, last_plan path 3) — node i carries the value exclusions
+        excl[excl_off[i] : excl_off[i + 1]], swept at the top of every round next to the units (tensors, ``objective`` and the fold / reduce
+        as in propagate_device_small_excl; excl_off = None: exactly propagate_device)."""
+        bt = _batch(lb_in=lb_in, ub_in=ub_in, lb_out=lb_out, ub_out=ub_out, active_out=active_out, status=status)
+        ob = _objective_struct(objective)
+        self._check(self._L.pcp_propagate_device_form_excl(self._h, n_nodes, C.byref(bt), _ptr(excl_off), _ptr(excl), None if ob is None else C.byref(ob),
+                                                           C.c_void_p(stream_ptr)))
 
     def propagate_device_bnb(self, n_nodes: int, lb_in, ub_in, lb_out, ub_out, active_in, active_out, status, objective, stream_ptr: int = 0,
                              bits_in=None, bits_out=None):

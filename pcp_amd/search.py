@@ -287,13 +287,15 @@ def branch_enumerate(lb: np.ndarray, ub: np.ndarray, excl_off=None, excl=None, v
 
 class _ExclRows:
     """A node is (lb, ub, exclusions [k, 2], dirty variable), propagated on torch tensors through ``ctx.propagate_device_excl`` (an all-XNeqY
-    model without an objective) or ``ctx.propagate_device_small_excl`` (``small``: any other small store, and every search with an objective).
+    model without an objective), ``ctx.propagate_device_small_excl`` (``small``: any other small store, and every search with an objective) or
+    ``ctx.propagate_device_form_excl`` (a context that says ``has_formulas``: a store with formula units, with or without an objective).
     The children of branch_enumerate are never empty; with an objective the incumbent is folded into the bounds here, as _IntervalRows does,
     and a node the fold empties is failed without a launch."""
 
     def __init__(self, ctx, val, record, hints, small=False):
         import torch
         self.torch, self.ctx, self.val, self.record, self.hints, self.small = torch, ctx, val, record, hints, small
+        self.form = bool(getattr(ctx, "has_formulas", False))  # a store with formula units: ctx.propagate_device_form_excl, whatever `small` says
         on_gpu = getattr(ctx, "device", 0) != "cpu"  # (the CPU tests drive this class with an oracle-backed stand-in context)
         self.dev = torch.device("cuda", ctx.device) if on_gpu else torch.device("cpu")
         self.stream = torch.cuda.current_stream(self.dev).cuda_stream if on_gpu else 0
@@ -322,8 +324,10 @@ class _ExclRows:
         t_st = torch.zeros(N, dtype=torch.uint8, device=dev)
         t_off = torch.from_numpy(off).to(dev)
         t_ex = torch.from_numpy(flat if len(flat) else np.zeros((1, 2), np.int32)).to(dev)  # (never a null pointer: an empty list is offsets alone)
-        t_dirty = torch.tensor([t[3] for t in take], dtype=torch.int32, device=dev) if (self.hints and not self.small) else None
-        if self.small:
+        t_dirty = torch.tensor([t[3] for t in take], dtype=torch.int32, device=dev) if (self.hints and not self.small and not self.form) else None
+        if self.form:
+            self.ctx.propagate_device_form_excl(N, t_lb, t_ub, t_lb, t_ub, None, t_st, t_off, t_ex, None, self.stream)
+        elif self.small:
             self.ctx.propagate_device_small_excl(N, t_lb, t_ub, t_lb, t_ub, None, t_st, t_off, t_ex, None, self.stream)
         else:
             self.ctx.propagate_device_excl(N, t_lb, t_ub, t_lb, t_ub, None, t_st, t_off, t_ex, self.stream, dirty=t_dirty)
@@ -352,7 +356,8 @@ def dfs_enumerate(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = F
     (lb_in, ub_in, exclusions [k, 2], status, lb_out, ub_out).
     A model that is not all-XNeqY (``ctx.all_neq``) — a small store of any plain propagators, the Golomb network — goes through
     ``ctx.propagate_device_small_excl`` instead (no hints: that kernel sweeps a node as a whole).  So does every search with an
-    ``objective`` (as in dfs: BranchAndBound wraps any brancher, branch_and_bound.rs:64-84): the bound is folded into a node's bounds before
+    ``objective`` (as in dfs: BranchAndBound wraps any brancher, branch_and_bound.rs:64-84) — unless the context says ``has_formulas`` (a store
+    with formula units, a schedule): then every launch is ``ctx.propagate_device_form_excl``.  The bound is folded into a node's bounds before
     its propagation exactly as under BinarySplit; this is the host specification of DeviceSearch(brancher="enumerate", objective=), so a
     batch is taken in the order of DeviceSearch's rows (``rows_up`` of _search): the same nodes, solutions, failures and incumbents at every
     batch size."""

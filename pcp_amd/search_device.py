@@ -13,7 +13,8 @@ Enumerate>, search/branching/enumerate.rs:33-60): every open node owns a list of
 rows and are written by the brancher — rows, hints and lists stay on the GPU from the root to the leaves.  A model that is not all-XNeqY (a
 small store of any plain propagators: the Golomb network) and every Enumerate search with an ``objective`` propagate through
 `pcp_propagate_device_small_excl` instead: the same lists on the one-wavefront-per-node kernel, the incumbent folded as a node is staged and
-reduced behind the launch (no hints: that kernel sweeps a node as a whole).  Over a set-mode context the same
+reduced behind the launch (no hints: that kernel sweeps a node as a whole).  A store with formula units (a schedule; ``ctx.has_formulas``)
+takes `pcp_propagate_device_form_excl` in that place: the same call on the one-wavefront-per-node tree kernel.  Over a set-mode context the same
 ``brancher="enumerate"`` needs none of that: x = v and x != v are exact operations on the sets, so the round is `pcp_propagate_device` +
 `pcp_branch_device_set_enum` on the rows of the BinarySplit search (no arena, no hints).
 PyTorch provides the device buffers; every kernel is this repository's.
@@ -177,7 +178,9 @@ class _Enumerate(_Int32Rows):
         (start, length), (o, e0, cnt, emax) = s.segs[-1], s.esegs[-1]
         k = lo - start  # the batch's first row within its segment
         lb, ub, poff, pex, etop, oc = s.lb[lo:top], s.ub[lo:top], s.eoff[o + k:o + length + 1], s.ex[e0:], e0 + cnt, o + length + 1
-        if s.enum_small:
+        if s.enum_form:
+            ctx.propagate_device_form_excl(n, lb, ub, lb, ub, None, status, poff, pex, None if s.objective is None else s._obj, stream)
+        elif s.enum_small:
             ctx.propagate_device_small_excl(n, lb, ub, lb, ub, None, status, poff, pex, None if s.objective is None else s._obj, stream)
         else:
             ctx.propagate_device_excl(n, lb, ub, lb, ub, None, status, poff, pex, stream, dirty=_cut(s.dirty, lo, top))
@@ -222,7 +225,7 @@ class DeviceSearch:
                 raise ValueError("Enumerate runs on int32 rows: cells=True is refused")
             if objective is not None and getattr(ctx, "set_words", 0):
                 raise ValueError("Enumerate takes no objective in set mode (branch and bound runs under BinarySplit there; forest_bnb_set(brancher=\"enumerate\") is the set-mode column)")
-            if objective is not None and not hasattr(ctx, "propagate_device_small_excl"):
+            if objective is not None and not getattr(ctx, "has_formulas", False) and not hasattr(ctx, "propagate_device_small_excl"):
                 raise ValueError("Enumerate with an objective needs a context that offers propagate_device_small_excl (pcp_propagate_device_small_excl): this one does not")
             if getattr(ctx, "set_words", 0) and not getattr(ctx, "supports_set_enumerate", False):
                 raise ValueError("Enumerate in set mode needs a context that offers branch_device_set_enum (pcp_branch_device_set_enum): this one does not")
@@ -263,7 +266,10 @@ class DeviceSearch:
         # may start the child's propagation from that variable alone; the root has none (-1).  Interval mode, implicit nodes, an engine
         # that knows the field (the CPU stand-in of the tests does not).
         # Enumerate on pcp_propagate_device_small_excl: an objective, or a model that is not all-XNeqY (a context that does not say is taken as all-XNeqY)
-        self.enum_small = brancher == "enumerate" and not self.set_words and (self.objective is not None or not getattr(ctx, "all_neq", True))
+        # Enumerate on pcp_propagate_device_form_excl: a store with formula units, with or without an objective (the rows, the arena and the round
+        # buffer are enum_small's: only the propagate call differs)
+        self.enum_form = brancher == "enumerate" and not self.set_words and bool(getattr(ctx, "has_formulas", False))
+        self.enum_small = brancher == "enumerate" and not self.set_words and (self.objective is not None or self.enum_form or not getattr(ctx, "all_neq", True))
         want = bool(getattr(ctx, "supports_hints", False)) and self.implicit and not self.set_words and self.objective is None and not self.enum_small  # (bnb, small stores: no hints)
         self.dirty = torch.full((self.cap,), -1, dtype=i32, device=self.dev) if (want if hints is None else (hints and want)) else None
         self.status = torch.zeros(self.batch, dtype=u8, device=self.dev)
