@@ -155,7 +155,7 @@ uint32_t pcp_abi_version(void);
  *     formula units, Interval        pcp_dfs_forest_device_form, _form_bnb   (what Cumulative::join builds: XEqYMulZ and Sum keep it here)
  *     records, IntervalSet           pcp_dfs_forest_device_set, _set_enum, _set_bnb
  *     formula units, IntervalSet     pcp_dfs_forest_device_setform, _setform_bnb
- *     small stores, Interval         pcp_dfs_forest_device_small, _small_bnb (plain propagators of any kind, <= 128 slots, <= 2048 filters: Golomb)
+ *     small stores, Interval         pcp_dfs_forest_device_small, _small_bnb, _small_enum (plain propagators of any kind, <= 128 slots, <= 2048 filters: Golomb)
  *     any other Interval store has no forest: pcp_dfs_device searches it, one tree.
  *   ENUMERATE (search/branching/enumerate.rs:33-60: children `x = v` and `x != v`) needs no engine support in set mode — both children are
  *   exact set operations the caller applies to `bits` before propagating (keep bit v / clear bit v), as pcp_branch_device_set does for
@@ -636,6 +636,43 @@ int32_t pcp_dfs_forest_device_small(pcp_ctx* ctx, const pcp_dfs_state* st, uint3
  * solution.  Also PCP_ERR_ARG: var >= n_vars, mode > PCP_MAXIMIZE, a null best / tree_best. */
 int32_t pcp_dfs_forest_device_small_bnb(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_objective* obj,
                                         uint32_t n_steps, uint64_t node_limit, void* hip_stream);
+/* The same forest under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate> (search/branching/enumerate.rs:33-60), with (obj != NULL)
+ * or without branch and bound: a node's children are `x = v` and `x != v`, variable and value as pcp_branch_device_excl chooses them — v is
+ * MiddleVal's or MinVal's value, or, when the node's list already holds (x, v), the nearest value of [lb, ub] without an entry on x, the
+ * lower one first.  `x != v` with v at a bound is folded into that bound; an interior one stays with its node as a pcp_excl entry and is
+ * propagated with the store at the top of every round as pcp_propagate_device_small_excl does (a value is removed only at a bound; x
+ * assigned to it fails the node; an entry whose value lies inside [lb, ub] keeps the node PCP_UNKNOWN; every test of an entry is a step).
+ * A depth-first tree needs no list per open node: every open row is the right child of an ancestor of the current node, so its list is a
+ * prefix of the entries appended along the current path plus at most one entry of its own.
+ *   path          : [n_trees][path_capacity] device pcp_excl: the exclusions along each tree's current path; may be NULL when path_capacity == 0
+ *   row_base      : [n_trees][capacity] device uint32: how many path entries stack row r inherits
+ *   row_excl      : [n_trees][capacity] device pcp_excl: the one entry appended behind them when row r is popped; var == 0xFFFFFFFF: none
+ *   path_capacity : entries per tree
+ *   val           : PCP_VAL_MIDDLE / PCP_VAL_MIN
+ * THE STATE BETWEEN CALLS: for every row r in [0, sp) of tree t, node r is the row's bounds under the list path[t][0 .. row_base[t][r])
+ * plus row_excl[t][r].  row_base does not decrease with r, and no length word is stored: a call derives the current list from the top row.  A
+ * caller that moves a tree's bottom row to another tree moves its two words and the first row_base[0] path entries along (the donor's path
+ * stays: its other rows use that prefix); a root is row 0 with its list in path[t][0 .. k), row_base = k and row_excl = none.  Entries are
+ * never filtered out of the path: one whose value lies outside [lb, ub] is entailed for good.
+ * Counters, StopNode, first solutions, stop_on_solution (ignored when obj != NULL), tree_best / tree_row and the errors are those of
+ * pcp_dfs_forest_device_small / _small_bnb, and two more cases: error 5, "exclusion path full" — a popped row has an entry and
+ * row_base == path_capacity: nothing is changed, the row stays on the stack, uncounted, stop is raised, and a caller that resumes with a
+ * larger path runs it then (the contract of error 1); error 2 also for a path or row entry with var >= n_vars (never used as an index) or
+ * a row_base beyond path_capacity: the node is counted and popped, the tree stops and the sticky violation flag is set.  With n_trees = 1
+ * the nodes are search.dfs_enumerate's, one for one.  pcp_last_plan: as for pcp_dfs_forest_device_small (path 4).
+ * Accepted stores: those of pcp_dfs_forest_device_small.  Set-mode model, val > PCP_VAL_MIN, a null required buffer (ex, row_base, row_excl,
+ * path with path_capacity > 0), n_trees == 0, capacity < 2, a bad objective as for _small_bnb: PCP_ERR_ARG.  Formula propagators or a
+ * store over the limits: PCP_ERR_UNSUPPORTED.  n_steps == 0: PCP_OK, nothing is launched. */
+typedef struct {
+  pcp_excl* path;
+  uint32_t* row_base;
+  pcp_excl* row_excl;
+  uint32_t path_capacity;
+  uint32_t val;
+} pcp_forest_excl;
+int32_t pcp_dfs_forest_device_small_enum(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex,
+                                         const pcp_forest_objective* obj, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
+                                         void* hip_stream);
 /* Between two calls of pcp_dfs_forest_device_set* / _setform*: finished trees take over work from trees that still have some.  pairs = n_pairs x
  * (donor, receiver) tree indices (device uint32).  For every pair whose receiver is finished and whose donor has an open right branch
  * left, the donor's OLDEST open right branch (the subtree nearest its root) becomes the receiver's new root — built from the donor's

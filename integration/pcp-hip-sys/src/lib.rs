@@ -164,6 +164,17 @@ pub struct pcp_forest_objective {
     pub tree_row: *mut i32,   // [n_trees][n_vars] or null
 }
 
+/// The exclusions of `pcp_dfs_forest_device_small_enum`: one path of entries per tree and two words per stack row (include/pcp_hip.h).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct pcp_forest_excl {
+    pub path: *mut pcp_excl,      // [n_trees][path_capacity]; may be null when path_capacity == 0
+    pub row_base: *mut u32,       // [n_trees][capacity]: the path entries a row inherits
+    pub row_excl: *mut pcp_excl,  // [n_trees][capacity]: the entry appended when the row is popped (var 0xFFFF_FFFF: none)
+    pub path_capacity: u32,
+    pub val: u32,                 // PCP_VAL_MIDDLE / PCP_VAL_MIN
+}
+
 /// The objective of `pcp_propagate_device_small_excl` (and of the header's `pcp_propagate_device_bnb`): branch and bound around a batch.
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -246,6 +257,9 @@ extern "C" {
                                        hip_stream: *mut c_void) -> i32; // the same forest for small Interval stores of plain propagators (Golomb)
     pub fn pcp_dfs_forest_device_small_bnb(ctx: *mut pcp_ctx, st: *const pcp_dfs_state, n_trees: u32, obj: *const pcp_forest_objective, n_steps: u32,
                                            node_limit: u64, hip_stream: *mut c_void) -> i32; // BranchAndBound around it
+    pub fn pcp_dfs_forest_device_small_enum(ctx: *mut pcp_ctx, st: *const pcp_dfs_state, n_trees: u32, ex: *const pcp_forest_excl,
+                                            obj: *const pcp_forest_objective, n_steps: u32, stop_on_solution: u32, node_limit: u64,
+                                            hip_stream: *mut c_void) -> i32; // the same forest under Enumerate; obj null: no branch and bound
     pub fn pcp_dfs_forest_device_set(ctx: *mut pcp_ctx, st: *const pcp_forest_state, n_steps: u32, stop_on_solution: u32, node_limit: u64,
                                      hip_stream: *mut c_void) -> i32;
     pub fn pcp_dfs_forest_device_set_enum(ctx: *mut pcp_ctx, st: *const pcp_forest_state, val: u32, n_steps: u32, stop_on_solution: u32,

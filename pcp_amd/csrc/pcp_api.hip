@@ -1252,13 +1252,17 @@ int32_t pcp_dfs_forest_device_form_bnb(pcp_ctx* c, const pcp_dfs_state* st, uint
 
 // The same loop over a SMALL Interval store of plain propagators — what smallfix_kernel propagates (plan.path 4): one tree per wavefront,
 // that kernel's round inside the loop (pcp_smalldfs.hip); obj != nullptr: under branch and bound.  The stacks are those of
-// pcp_dfs_forest_device.
-static int32_t dfs_forest_small(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_objective* obj, uint32_t n_steps, uint32_t stop_on_solution,
-                                uint64_t node_limit, void* hip_stream) {
-  const std::string who = obj ? "pcp_dfs_forest_device_small_bnb" : "pcp_dfs_forest_device_small";
+// pcp_dfs_forest_device.  ex != nullptr: under Enumerate (pcp_dfs_forest_device_small_enum), each tree with its exclusion path.
+static int32_t dfs_forest_small(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex, const pcp_forest_objective* obj, uint32_t n_steps,
+                                uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
+  const std::string who = ex ? "pcp_dfs_forest_device_small_enum" : obj ? "pcp_dfs_forest_device_small_bnb" : "pcp_dfs_forest_device_small";
   if (c->set_words) return fail(c, PCP_ERR_ARG, who + " runs interval-mode models (sets: pcp_dfs_forest_device_set)");
   if (!n_trees || !st->lb || !st->ub || !st->sp || !st->stop || !st->status || !st->counters || st->capacity < 2)
     return fail(c, PCP_ERR_ARG, who + ": null buffer / no tree / capacity < 2");
+  if (ex) {
+    if (ex->val > PCP_VAL_MIN) return fail(c, PCP_ERR_ARG, who + ": val must be PCP_VAL_MIDDLE or PCP_VAL_MIN");
+    if (!ex->row_base || !ex->row_excl || (ex->path_capacity && !ex->path)) return fail(c, PCP_ERR_ARG, who + ": null row_base / row_excl / path");
+  }
   if (obj) {
     if (obj->var >= c->n_vars) return fail(c, PCP_ERR_ARG, who + ": objective variable out of range");
     if (obj->mode > PCP_MAXIMIZE) return fail(c, PCP_ERR_ARG, who + ": mode must be PCP_MINIMIZE or PCP_MAXIMIZE");
@@ -1288,6 +1292,7 @@ static int32_t dfs_forest_small(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_
   a.first_solution = obj ? nullptr : st->first_solution;
   a.violation = c->d_retry + 1; a.stats = c->d_stats;
   if (obj) { a.obj_var = obj->var; a.obj_mode = obj->mode; a.obj_best = obj->best; a.tree_best = obj->tree_best; a.tree_row = obj->tree_row; }
+  if (ex) { a.path = ex->path; a.row_base = ex->row_base; a.row_excl = ex->row_excl; a.path_capacity = ex->path_capacity; a.val = ex->val; }
   LaunchPlan plan;
   plan.block = 64 * waves; plan.lds_bytes = lds; plan.grid = (n_trees + waves - 1) / waves;
   c->last_plan = pcp_plan{waves, 1u, 0u, 0u, 0u, 0u, 1u, 0u, plan.grid, plan.block, (uint32_t)lds, 0u, 4u};
@@ -1298,13 +1303,19 @@ static int32_t dfs_forest_small(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_
 int32_t pcp_dfs_forest_device_small(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
                                     void* hip_stream) {
   if (!c || !st) return c ? fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_small: null state") : PCP_ERR_ARG;
-  return dfs_forest_small(c, st, n_trees, nullptr, n_steps, stop_on_solution, node_limit, hip_stream);
+  return dfs_forest_small(c, st, n_trees, nullptr, nullptr, n_steps, stop_on_solution, node_limit, hip_stream);
 }
 
 int32_t pcp_dfs_forest_device_small_bnb(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_objective* obj, uint32_t n_steps, uint64_t node_limit,
                                         void* hip_stream) {
   if (!c || !st || !obj) return c ? fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_small_bnb: null state / objective") : PCP_ERR_ARG;
-  return dfs_forest_small(c, st, n_trees, obj, n_steps, 0, node_limit, hip_stream);
+  return dfs_forest_small(c, st, n_trees, nullptr, obj, n_steps, 0, node_limit, hip_stream);
+}
+
+int32_t pcp_dfs_forest_device_small_enum(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex, const pcp_forest_objective* obj,
+                                         uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
+  if (!c || !st || !ex) return c ? fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_small_enum: null state / exclusions") : PCP_ERR_ARG;
+  return dfs_forest_small(c, st, n_trees, ex, obj, n_steps, obj ? 0u : stop_on_solution, node_limit, hip_stream);
 }
 
 int32_t pcp_dfs_device(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {

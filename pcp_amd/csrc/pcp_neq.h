@@ -242,6 +242,11 @@ struct SmallDfsArgs {
   int32_t* obj_best;             // device int32[1]: the forest's incumbent
   int32_t* tree_best;            // [n_trees]: the value of each tree's last solution
   int32_t* tree_row;             // [n_trees][n_vars] or null: its lower bounds
+  // Enumerate only (smalldfs_kernel<.., true>, pcp_dfs_forest_device_small_enum; row_base == null: BinarySplit)
+  pcp_excl* path;                // [n_trees][path_capacity]: the exclusions along each tree's current path
+  uint32_t* row_base;            // [n_trees][capacity]: the path entries a stack row inherits
+  pcp_excl* row_excl;            // [n_trees][capacity]: the entry appended when the row is popped (var 0xFFFFFFFF: none)
+  uint32_t path_capacity, val;   // PCP_VAL_MIDDLE / PCP_VAL_MIN
 };
 size_t lds_bytes_smalldfs(uint32_t n_slots, uint32_t n_units, uint32_t n_recs, uint32_t waves);  // the records' copy + one slice per tree; 0 = beyond a CU's LDS
 hipError_t launch_smalldfs(const SmallDfsArgs& a, bool bnb, const LaunchPlan& p, hipStream_t stream);

@@ -24,6 +24,16 @@
 //   - unit liveness is derived, never stored: an entailed unit stays entailed as domains shrink, so the descent to the left
 //     child keeps the live bits; popping any other row sets every unit live, and the round that narrows nothing unlinks again what is
 //     entailed (`ent`, as in smallfix_kernel).
+//
+// ENUM = true: the same loop under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate> (search/branching/enumerate.rs:33-60):
+// pcp_dfs_forest_device_small_enum.  The children are `x = v` and `x != v`; an interior `x != v` removes nothing from an Interval and stays
+// with its node as a pcp_excl entry (pcp_smallexcl.hip).  The batched search carries a CSR list per open node and copies it at every
+// branch; a depth-first tree needs none of that: every open row of the stack is the right child of an ancestor of the current node, so its
+// list is a PREFIX of the exclusions appended along the current path plus at most one entry of its own.  A tree keeps ONE path of
+// entries in HBM and per stack row (row_base, row_excl) — how many path entries the row inherits and the entry appended when it is popped.
+// The current node's list is path[0 .. n), n wave-uniform in a register and re-derived from the top row at every launch; nothing is
+// copied at a branch.  Entries are never filtered out of the path: an entry whose value lies outside [lb, ub] is entailed and stays so
+// (domains only shrink below a node), and the value rule only looks inside [lb, ub] — the same tree as search.branch_enumerate's lists.
 // Integer bound work: no MFMA.
 #include <algorithm>
 
@@ -33,7 +43,9 @@ namespace pcp {
 
 namespace {
 
-template <bool BNB>
+constexpr uint32_t kNoExcl = 0xFFFFFFFFu;  // row_excl[r].var: the row appends nothing when it is popped
+
+template <bool BNB, bool ENUM>
 __global__ void __launch_bounds__(256) smalldfs_kernel(const SmallDfsArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t lane = threadIdx.x & 63;
@@ -87,12 +99,42 @@ __global__ void __launch_bounds__(256) smalldfs_kernel(const SmallDfsArgs a) {
     for (uint32_t v = lane; v < V; v += 64) { const int2 d = dom[v]; lb[(size_t)r * V + v] = -d.x; ub[(size_t)r * V + v] = d.y; }
   };
 
+  // ENUM: this tree's exclusion path and its rows' two words; n = the entries of the current node's list, path[0 .. n)
+  pcp_excl* const path = ENUM ? a.path + (size_t)t * a.path_capacity : nullptr;
+  uint32_t* const row_base = ENUM ? a.row_base + (size_t)t * a.capacity : nullptr;
+  pcp_excl* const row_excl = ENUM ? a.row_excl + (size_t)t * a.capacity : nullptr;
+  uint32_t n = 0;
+  // a row whose list is in the path already: the left child nobody has popped, a node kept by error 1 — popping it again changes nothing
+  auto store_row_words = [&](uint32_t r) {
+    if (lane == 0) { row_base[r] = n; row_excl[r] = pcp_excl{kNoExcl, 0}; }
+  };
+
   bool in_lds = false;  // the row on top of the stack is the LDS node (the left child of the node before) and has not been written
   for (uint32_t step = 0; step < a.n_steps && sp != 0 && !stop; ++step) {
     // ---- pop: row sp - 1 as (-lb, ub) cells ---------------------------------------------------------------------------------------------
     const uint32_t node = sp - 1;
     bool bad = false;
     if (lane == 0) misc[S_FAIL] = 0;
+    if (ENUM && !in_lds) {
+      // the row's list: the prefix it inherits, then its own entry.  (Wave-uniform loads: every lane reads the same two words)
+      const uint32_t base = row_base[node];
+      const pcp_excl own = row_excl[node];
+      if (base > a.path_capacity || (own.var != kNoExcl && own.var >= V)) {
+        // malformed: never used as an index.  Refused like a bound beyond +-(2^29 - 1): counted, popped, error 2, the sticky flag
+        if (lane == 0) atomicMax(a.violation, 1u);
+        ++nodes; error = 2; stop = 1; sp = node;
+        break;
+      }
+      if (own.var != kNoExcl) {
+        // 5: the exclusion path is full — nothing has been changed: the row stays on the stack, uncounted, and a caller that resumes
+        // with a larger path runs it then (the contract of error 1)
+        if (base == a.path_capacity) { error = 5; stop = 1; break; }
+        if (lane == 0) path[base] = own;
+        n = base + 1;
+      } else {
+        n = base;
+      }
+    }
     if (!in_lds) {
       bool wide = false;
       for (uint32_t v = lane; v < V; v += 64) {
@@ -128,10 +170,34 @@ __global__ void __launch_bounds__(256) smalldfs_kernel(const SmallDfsArgs a) {
     // ---- propagate: smallfix_kernel's rounds over the live units until a round narrows nothing or the node fails --------------------------
     bool failed = __ballot(bad) != 0;
     uint32_t rounds = 0, s2 = 0, s3 = 0;
+    bool ex_open = false;  // ENUM: one of the node's exclusions is not entailed
     while (!failed) {
       ++rounds;
       const uint32_t before = ctr.narrow;
-      small_round(sh, P, Wu, sl, dm, lane, s2, s3, [] {});
+      if constexpr (ENUM) {
+        ex_open = false;
+        // the node's exclusions at the top of every round, lane-strided from global memory, exactly as smallexcl_kernel sweeps a CSR slice
+        small_round(sh, P, Wu, sl, dm, lane, s2, s3, [&] {
+          for (uint32_t i = lane; i < n; i += 64) {
+            const pcp_excl e = path[i];
+            if (e.var >= V) { dm.set_fail(); misc[S_OOB] = 1u; continue; }  // malformed: the tree is refused below
+            const int K = e.value;
+            const int2 c_ = dom[e.var];
+            const int xl0 = -c_.x, xu0 = c_.y;
+            int xl = xl0, xu = xu0;
+            ++s2;
+            // XNeqY(Identity(var), Constant(value))::propagate (x_neq_y.rs:82-93): a value is removed only at a bound
+            if (xl0 == xu0) { if (xl0 == K) { dm.set_fail(); continue; } }
+            else if (K == xl0) xl = xl0 + 1;
+            else if (K == xu0) xu = xu0 - 1;
+            if (xl > xl0) dm.raise_lb(e.var, xl);
+            if (xu < xu0) dm.lower_ub(e.var, xu);
+            ex_open |= !(K < xl || K > xu);  // is_subsumed() on what propagate() left (store.rs:166-175): True iff disjoint (x_neq_y.rs:71-73)
+          }
+        });
+      } else {
+        small_round(sh, P, Wu, sl, dm, lane, s2, s3, [] {});
+      }
       wave_sync();
       failed = __builtin_amdgcn_readfirstlane(misc[S_FAIL]) != 0;
       if (!__ballot(ctr.narrow != before)) break;
@@ -139,6 +205,11 @@ __global__ void __launch_bounds__(256) smalldfs_kernel(const SmallDfsArgs a) {
     steps2 += s2; steps3 += s3;
     acc_rounds += rounds ? rounds : 1;
     ++acc_nodes;
+    if (ENUM && __builtin_amdgcn_readfirstlane(misc[S_OOB]) != 0) {  // a path entry with var >= n_vars: refused like the row's own (above)
+      if (lane == 0) atomicMax(a.violation, 1u);
+      ++nodes; error = 2; stop = 1; sp = node;
+      break;
+    }
 
     // ---- Consistency::consistency (store.rs:250-256): False if a propagate failed, True if no subscription remains, else Unknown; and the
     //      key of FirstSmallestVar (first_smallest_var.rs:30-39): the smallest size > 1, the lowest index on a tie -------------------------
@@ -158,7 +229,8 @@ __global__ void __launch_bounds__(256) smalldfs_kernel(const SmallDfsArgs a) {
         live[w] = left;
         any_live |= left != 0;
       }
-    const bool unknown = !failed && __ballot(any_live) != 0;
+    // (ENUM: an exclusion that is not entailed keeps the node Unknown even when every unit is entailed)
+    const bool unknown = !failed && __ballot(any_live || (ENUM && ex_open)) != 0;
 
     // ---- the step of dfs_step_kernel ----------------------------------------------------------------------------------------------------
     uint32_t new_sp = sp - 1;
@@ -169,19 +241,61 @@ __global__ void __launch_bounds__(256) smalldfs_kernel(const SmallDfsArgs a) {
         // again (idempotent) and counts it then.  3: Unknown, yet no variable with more than one value: the reference panics here
         // (first_smallest_var.rs:36)
         store_row(node);
+        if (ENUM) store_row_words(node);
         error = key == ~0ull ? 3u : 1u; stop = 1;
         break;
       }
       const uint32_t var = (uint32_t)key;
       const int2 dv = dom[var];
       const int val = (int)(((long long)dv.y - (long long)dv.x) / 2);  // MiddleVal (middle_val.rs:25-27): `/` truncates toward zero like Rust's
-      // Brancher (brancher.rs:52-71, binary_split.rs:46-57): the parent's row becomes the right child `x > val`; the left child `x <= val`
-      // goes on top — it is the LDS node from here on
-      for (uint32_t v = lane; v < V; v += 64) {
-        const int2 d = dom[v];
-        lb[(size_t)node * V + v] = (v == var) ? max(-d.x, val + 1) : -d.x;
-        ub[(size_t)node * V + v] = d.y;
-        if (v == var) dom[v].y = min(d.y, val);
+      if constexpr (ENUM) {
+        // Enumerate (enumerate.rs:47-60) on MiddleVal's or MinVal's value (min_val.rs:25-27: the lower bound).  A value the node has excluded
+        // already is not chosen again (search.branch_enumerate, pcp_branch_device_excl): the nearest value of [lo, hi] without an entry on
+        // `var`, m - d before m + d.  At a fixpoint neither bound of a variable is excluded — the sweep would have removed it — so a free
+        // value always exists (there is no error code for "every value excluded") and MinVal's value is always free: under MinVal the
+        // right child is always folded and the path never grows.  Every candidate inside [lo, hi] that is not free uses up an entry of its
+        // own, so the search ends after at most n + 1 sweeps of n entries, whatever the width of the domain.
+        const int lo = -dv.x, hi = dv.y;
+        int v = a.val == PCP_VAL_MIN ? lo : val;
+        if (a.val != PCP_VAL_MIN && n) {
+          bool hit = false;
+          for (uint32_t i = lane; i < n; i += 64) { const pcp_excl e = path[i]; hit |= e.var == var && e.value == v; }
+          if (__ballot(hit)) {
+            for (int d = 1;; ++d) {
+              const int c0 = val - d, c1 = val + d;
+              const bool in0 = c0 >= lo, in1 = c1 <= hi;
+              if (!in0 && !in1) break;  // (not at a fixpoint, see above)
+              bool h0 = false, h1 = false;
+              for (uint32_t i = lane; i < n; i += 64) {
+                const pcp_excl e = path[i];
+                h0 |= e.var == var && e.value == c0;
+                h1 |= e.var == var && e.value == c1;
+              }
+              if (in0 && !__ballot(h0)) { v = c0; break; }
+              if (in1 && !__ballot(h1)) { v = c1; break; }
+            }
+          }
+        }
+        // Brancher (brancher.rs:52-71): the parent's row becomes the right child `x != v` — folded into the bound v sits at, else the
+        // bounds as they are and the entry (var, v) for when the row is popped; either way it inherits the n entries of this node.  The
+        // left child `x = v` goes on top, the path unchanged — it is the LDS node from here on
+        const bool at_lb = v == lo, at_ub = v == hi;
+        for (uint32_t u = lane; u < V; u += 64) {
+          const int2 d = dom[u];
+          lb[(size_t)node * V + u] = (u == var && at_lb) ? v + 1 : -d.x;
+          ub[(size_t)node * V + u] = (u == var && at_ub && !at_lb) ? v - 1 : d.y;
+          if (u == var) dom[u] = make_int2(-v, v);
+        }
+        if (lane == 0) { row_base[node] = n; row_excl[node] = (at_lb || at_ub) ? pcp_excl{kNoExcl, 0} : pcp_excl{var, v}; }
+      } else {
+        // Brancher (brancher.rs:52-71, binary_split.rs:46-57): the parent's row becomes the right child `x > val`; the left child `x <= val`
+        // goes on top — it is the LDS node from here on
+        for (uint32_t v = lane; v < V; v += 64) {
+          const int2 d = dom[v];
+          lb[(size_t)node * V + v] = (v == var) ? max(-d.x, val + 1) : -d.x;
+          ub[(size_t)node * V + v] = d.y;
+          if (v == var) dom[v].y = min(d.y, val);
+        }
       }
       new_sp = sp + 1;
       in_lds = true;
@@ -212,7 +326,10 @@ __global__ void __launch_bounds__(256) smalldfs_kernel(const SmallDfsArgs a) {
     wave_sync();  // (the branch's LDS write, the live bits, and this tree's rows, before the next pop reads them)
   }
 
-  if (in_lds) store_row(sp - 1);  // the left child nobody has popped yet
+  if (in_lds) {  // the left child nobody has popped yet
+    store_row(sp - 1);
+    if (ENUM) store_row_words(sp - 1);
+  }
   for (int o = 32; o > 0; o >>= 1) { steps2 += __shfl_down(steps2, o); steps3 += __shfl_down(steps3, o); ctr.narrow += __shfl_down(ctr.narrow, o); }
   if (lane == 0) {
     a.sp[t] = sp; a.stop[t] = stop;
@@ -233,13 +350,13 @@ __global__ void __launch_bounds__(256) smalldfs_kernel(const SmallDfsArgs a) {
   }
 }
 
-template <bool BNB>
+template <bool BNB, bool ENUM>
 hipError_t launch_smalldfs_as(const SmallDfsArgs& a, const LaunchPlan& p, hipStream_t stream) {
   hipError_t e;
   if (p.lds_bytes > 64 * 1024 &&
-      (e = hipFuncSetAttribute(reinterpret_cast<const void*>(smalldfs_kernel<BNB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes)) != hipSuccess)
+      (e = hipFuncSetAttribute(reinterpret_cast<const void*>(smalldfs_kernel<BNB, ENUM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes)) != hipSuccess)
     return e;
-  hipLaunchKernelGGL((smalldfs_kernel<BNB>), dim3(p.grid), dim3(p.block), p.lds_bytes, stream, a);
+  hipLaunchKernelGGL((smalldfs_kernel<BNB, ENUM>), dim3(p.grid), dim3(p.block), p.lds_bytes, stream, a);
   return hipGetLastError();
 }
 
@@ -253,7 +370,11 @@ size_t lds_bytes_smalldfs(uint32_t n_slots, uint32_t n_units, uint32_t n_recs, u
 // p.block = 64 x the trees of a workgroup, p.grid = ceil(n_trees / those), p.lds_bytes = lds_bytes_smalldfs of them
 hipError_t launch_smalldfs(const SmallDfsArgs& a, bool bnb, const LaunchPlan& p, hipStream_t stream) {
   if (!a.m.recs) return hipErrorInvalidValue;
-  return bnb ? launch_smalldfs_as<true>(a, p, stream) : launch_smalldfs_as<false>(a, p, stream);
+  if (a.row_base) {  // Enumerate: the rows' words are there (pcp_dfs_forest_device_small_enum)
+    if (!a.row_excl || (a.path_capacity && !a.path)) return hipErrorInvalidValue;
+    return bnb ? launch_smalldfs_as<true, true>(a, p, stream) : launch_smalldfs_as<false, true>(a, p, stream);
+  }
+  return bnb ? launch_smalldfs_as<true, false>(a, p, stream) : launch_smalldfs_as<false, false>(a, p, stream);
 }
 
 }  // namespace pcp

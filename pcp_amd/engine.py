@@ -25,7 +25,7 @@ ERRORS = {-1: "PCP_ERR_ARG", -2: "PCP_ERR_CONTRACT", -3: "PCP_ERR_HIP", -4: "PCP
 ABI_SYMBOLS = [
     "pcp_ctx_create", "pcp_ctx_destroy", "pcp_last_error", "pcp_strerror", "pcp_abi_version",
     "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull",
-    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
+    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
 ]
 
 
@@ -84,6 +84,11 @@ class ForestState(C.Structure):
 class ForestObjective(C.Structure):
     """pcp_forest_objective: the objective of pcp_dfs_forest_device_set_bnb (branch and bound in the set-mode forest)."""
     _fields_ = [("var", C.c_uint32), ("mode", C.c_uint32), ("best", C.c_void_p), ("tree_best", C.c_void_p), ("tree_row", C.c_void_p)]
+
+
+class ForestExcl(C.Structure):
+    """pcp_forest_excl: the exclusions of pcp_dfs_forest_device_small_enum — one path of entries per tree, two words per stack row."""
+    _fields_ = [("path", C.c_void_p), ("row_base", C.c_void_p), ("row_excl", C.c_void_p), ("path_capacity", C.c_uint32), ("val", C.c_uint32)]
 
 
 DFS_FULL = 0xFFFFFFFF
@@ -163,6 +168,7 @@ def load_library():
     L.pcp_dfs_forest_device_form_bnb.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestObjective), u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_small.argtypes = [vp, C.POINTER(DfsState), u32, u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_small_bnb.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestObjective), u32, C.c_uint64, vp]
+    L.pcp_dfs_forest_device_small_enum.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestExcl), C.POINTER(ForestObjective), u32, u32, C.c_uint64, vp]
     L.pcp_stats_reset.argtypes = [vp, vp]
     L.pcp_stats_read.argtypes = [vp, C.POINTER(PcpStats), vp]
     L.pcp_debug_counters.argtypes = [vp, C.POINTER(C.c_uint64), u32, vp]
@@ -170,7 +176,7 @@ def load_library():
     L.pcp_last_plan.argtypes = [vp, C.POINTER(PcpPlan)]
     L.pcp_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
     for f in ("pcp_ctx_create", "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull", "pcp_model_set_hull",
-              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
+              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
         getattr(L, f).restype = i32
     _lib = L
     return L
@@ -514,7 +520,8 @@ class Context:
 
     def dfs_forest(self, root_lb, root_ub, stop_on_solution: bool = False, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
                    max_launches: int = 1 << 30, node_budget: int = 0, want_solution: bool = False, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
-                   sp0=None, hints: bool = True, formulas: bool = False, small: bool = False, _call=None):
+                   sp0=None, hints: bool = True, formulas: bool = False, small: bool = False, _call=None, brancher: str = "split", val: str = "middle",
+                   root_excl=None, path_capacity: int = 64, max_path: int = 1 << 20, _obj=None):
         """pcp_dfs_forest_device: the reference's search loop (interval mode, all-XNeqY models) on many subtrees at once, one workgroup per
         tree, each exactly a pcp_dfs_device instance.  root_lb / root_ub: [n_trees, n_vars] int32 (numpy or CUDA tensors): the roots, not yet
         propagated.  Launches of steps_per_launch nodes per tree are repeated until every stack is empty, a tree stopped (solution with
@@ -529,10 +536,16 @@ class Context:
         Stacks, growth, refill, ``dist`` and the result dict are the same.
         ``small``: a small store of plain propagators of any kind (at most 128 slots and 2048 elementary filters, no formula units — the
         Golomb network): the trees run in pcp_dfs_forest_device_small, one per wavefront (last_plan: path 4); no ``dirty`` rows either.
-        Together with ``formulas`` it is a ValueError: a store is one or the other."""
+        Together with ``formulas`` it is a ValueError: a store is one or the other.
+        ``brancher="enumerate"`` (``small=True`` only; otherwise, or with ``dist``, a ValueError): the trees run under Enumerate on MiddleVal
+        (``val="middle"``) or MinVal (``"min"``) in pcp_dfs_forest_device_small_enum.  ``root_excl``: a list of [k, 2] int32 arrays of (var, value),
+        one per root — the exclusions the root arrives with (None: no root has any); they are written into each tree's path.  A tree's path
+        holds ``path_capacity`` entries and is doubled, up to ``max_path``, when a tree reports error 5, as its stack is on error 1.  ``info``
+        also receives ``path_grown`` and ``path_capacity``.  The default ``brancher="split"`` issues exactly the calls it issued before."""
         import torch
         if small and formulas:
             raise ValueError("dfs_forest: small=True and formulas=True name two different forests (a store has formula units or it has none)")
+        enum = _check_forest_brancher("dfs_forest", brancher, val, small, dist, root_excl)
         dev = torch.device("cuda", self.device)
         V = self.n_vars
         to_dev = lambda x: (torch.from_numpy(np.ascontiguousarray(x, np.int32)) if isinstance(x, np.ndarray) else x).to(dev).reshape(-1, V)
@@ -553,18 +566,39 @@ class Context:
         stream = torch.cuda.current_stream(dev).cuda_stream
         box = {}
 
-        def point(fs):  # (re)build the pcp_dfs_state over the forest's current buffers
+        path = row_base = row_excl = None
+        if enum:
+            lists = [np.ascontiguousarray(e, np.int32).reshape(-1, 2) for e in root_excl] if root_excl is not None else []
+            if lists and len(lists) != T:
+                raise ValueError(f"dfs_forest: root_excl names {len(lists)} roots, there are {T}")
+            path_capacity = max(int(path_capacity), max((len(e) for e in lists), default=0))
+            h_path = np.zeros((T, max(path_capacity, 1), 2), np.int32)
+            h_base = np.zeros((T, capacity), np.int32)
+            for t, e in enumerate(lists):
+                h_path[t, :len(e)] = e
+                h_base[t, 0] = len(e)
+            path, row_base = torch.from_numpy(h_path).to(dev), torch.from_numpy(h_base).to(dev)
+            row_excl = torch.zeros((T, capacity, 2), dtype=torch.int32, device=dev)
+            row_excl[:, :, 0] = -1  # var 0xFFFFFFFF: the row appends nothing
+
+        def point(fs):  # (re)build the pcp_dfs_state — and the pcp_forest_excl — over the forest's current buffers
             box["st"] = DfsState(fs.lb.data_ptr(), fs.ub.data_ptr(), fs.capacity, sp.data_ptr(), stop.data_ptr(), fs.status.data_ptr(), counters.data_ptr(),
                                  sol.data_ptr() if want_solution else None, fs.dirty.data_ptr() if fs.dirty is not None else None)
+            if enum:
+                box["ex"] = ForestExcl(fs.path.data_ptr(), fs.row_base.data_ptr(), fs.row_excl.data_ptr(), fs.path_capacity, VAL_MODES[val])
 
-        fs = ForestStacks(lb, ub, status, sp, stop, counters, max_capacity=max(max_capacity, capacity), on_grow=point, dirty=dirty)
-        del lb, ub, status, dirty
+        fs = ForestStacks(lb, ub, status, sp, stop, counters, max_capacity=max(max_capacity, capacity), on_grow=point, dirty=dirty,
+                          **(dict(path=path, row_base=row_base, row_excl=row_excl, path_capacity=path_capacity, max_path=max(int(max_path), path_capacity)) if enum else {}))
+        del lb, ub, status, dirty, path, row_base, row_excl
         point(fs)
 
         entry = self._L.pcp_dfs_forest_device_small if small else (self._L.pcp_dfs_forest_device_form if formulas else self._L.pcp_dfs_forest_device)
 
         def launch():
-            if _call is not None:  # (dfs_forest_bnb: the same loop over another entry point)
+            if enum:  # (_obj: dfs_forest_bnb's objective)
+                self._check(self._L.pcp_dfs_forest_device_small_enum(self._h, C.byref(box["st"]), T, C.byref(box["ex"]), C.byref(_obj) if _obj is not None else None,
+                                                                    int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit_per_tree), C.c_void_p(stream)))
+            elif _call is not None:  # (dfs_forest_bnb: the same loop over another entry point)
                 self._check(_call(box["st"], T, stream))
             else:
                 self._check(entry(self._h, C.byref(box["st"]), T, int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit_per_tree), C.c_void_p(stream)))
@@ -576,6 +610,8 @@ class Context:
             info.update(loop)
             spc = sp.cpu().tolist()  # the open nodes each tree left on its stack, bottom row first
             info["rows"] = [(fs.lb[t, :spc[t]].cpu().numpy(), fs.ub[t, :spc[t]].cpu().numpy()) for t in range(T)] if T <= 64 else None
+            if enum:
+                info["path_grown"], info["path_capacity"] = fs.path_grown, fs.path_capacity
         cn = counters.cpu().numpy()
         return {"nodes": int(cn[:, 0].sum()), "solutions": int(cn[:, 1].sum()), "failed": int(cn[:, 2].sum()), "error": int(cn[:, 3].max()),
                 "open": int(sp.sum().item()), "launches": launches, "per_tree": cn, "trees": T, "steals": steals,
@@ -583,7 +619,8 @@ class Context:
 
     def dfs_forest_bnb(self, root_lb, root_ub, objective, best0=None, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
                        max_launches: int = 1 << 30, node_budget: int = 0, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
-                       sp0=None, small: bool = False):
+                       sp0=None, small: bool = False, brancher: str = "split", val: str = "middle", root_excl=None, path_capacity: int = 64,
+                       max_path: int = 1 << 20):
         """pcp_dfs_forest_device_form_bnb: branch and bound (branch_and_bound.rs:64-84) in the forest over an Interval store with formula
         propagators — the loop, stacks, growth and refill of dfs_forest(formulas=True), every popped row entered with the forest's incumbent
         (one device word) folded into the objective's bounds.  ``objective`` = (var, "min" | "max").  ``best0``: a known bound to start from
@@ -591,8 +628,10 @@ class Context:
         ``best_solution`` (the row of the lowest tree whose value is ``best``) and ``tree_best`` ([n_trees]; a tree without a solution: the
         "no solution yet" value).
         ``small``: the store is a small one of plain propagators (dfs_forest(small=True)): the same loop and result over
-        pcp_dfs_forest_device_small_bnb."""
+        pcp_dfs_forest_device_small_bnb.  ``brancher`` / ``val`` / ``root_excl`` / ``path_capacity`` / ``max_path``: as for dfs_forest
+        (Enumerate needs ``small=True``: pcp_dfs_forest_device_small_enum with the objective)."""
         import torch
+        _check_forest_brancher("dfs_forest_bnb", brancher, val, small, dist, root_excl)
         var, mode = objective
         if mode not in OBJ_MODES:
             raise ValueError(f"objective mode must be 'min' or 'max', not {mode!r}")
@@ -609,7 +648,8 @@ class Context:
             return entry(self._h, C.byref(st), n_trees, C.byref(obj), int(steps_per_launch), int(node_limit_per_tree), C.c_void_p(stream))
 
         out = self.dfs_forest(root_lb, root_ub, node_limit_per_tree=node_limit_per_tree, steps_per_launch=steps_per_launch, capacity=capacity, max_launches=max_launches,
-                              node_budget=node_budget, rebalance=rebalance, info=info, dist=dist, max_capacity=max_capacity, sp0=sp0, formulas=not small, small=small, _call=call)
+                              node_budget=node_budget, rebalance=rebalance, info=info, dist=dist, max_capacity=max_capacity, sp0=sp0, formulas=not small, small=small, _call=call,
+                              **(dict(brancher=brancher, val=val, root_excl=root_excl, path_capacity=path_capacity, max_path=max_path, _obj=obj) if brancher != "split" else {}))
         tb = tree_best.cpu().numpy()
         found = tb != none
         out["tree_best"] = tb
@@ -796,6 +836,19 @@ def _check_brancher(brancher, val):
         raise ValueError(f"brancher must be 'split' or 'enumerate', not {brancher!r}")
     if brancher == "enumerate" and val not in VAL_MODES:
         raise ValueError(f"val must be 'middle' or 'min', not {val!r}")
+
+
+def _check_forest_brancher(who, brancher, val, small, dist, root_excl=None) -> bool:
+    """The distributor of an Interval forest: True under Enumerate.  Enumerate runs in the small-store forest alone, on one rank."""
+    _check_brancher(brancher, val)
+    enum = brancher == "enumerate"
+    if enum and not small:
+        raise ValueError(f"{who}: brancher='enumerate' runs in the small-store forest only (small=True); the all-XNeqY forest and the formula-store forest stay on BinarySplit")
+    if enum and dist is not None:
+        raise ValueError(f"{who}: brancher='enumerate' does not run on several ranks (moving exclusion lists between ranks is not built)")
+    if root_excl is not None and not enum:
+        raise ValueError(f"{who}: root_excl needs brancher='enumerate'")
+    return enum
 
 
 def full_active(n_nodes: int, n_units: int) -> np.ndarray:

@@ -182,10 +182,18 @@ def refill_across_ranks(lb, ub, sp, spc, dist, info: dict | None = None, dirty=N
 class ForestStacks:
     """The interval forest's state: stacks ``lb``/``ub`` [T, capacity, V], ``status`` [T, capacity], sizes ``sp`` [T], flags ``stop`` [T],
     ``counters`` [T, 5] (nodes, solutions, failed, error, ..).  ``grow()`` doubles the rows per tree (a tree's rows stay where they are
-    within its slice) up to ``max_capacity``; ``on_grow`` lets the owner re-point its pcp_dfs_state."""
+    within its slice) up to ``max_capacity``; ``on_grow`` lets the owner re-point its pcp_dfs_state.
+    Under Enumerate (pcp_dfs_forest_device_small_enum) also ``path`` [T, path_capacity, 2] — each tree's exclusions along its current path —
+    and per stack row ``row_base`` [T, capacity] and ``row_excl`` [T, capacity, 2] (pcp_forest_excl); ``grow()`` carries the two row arrays,
+    ``grow_path()`` doubles the path up to ``max_path``."""
 
-    def __init__(self, lb, ub, status, sp, stop, counters, max_capacity: int = 0, on_grow=None, dirty=None):
+    def __init__(self, lb, ub, status, sp, stop, counters, max_capacity: int = 0, on_grow=None, dirty=None, path=None, row_base=None, row_excl=None,
+                 path_capacity: int = 0, max_path: int = 0):
         self.lb, self.ub, self.status, self.sp, self.stop, self.counters = lb, ub, status, sp, stop, counters
+        self.path, self.row_base, self.row_excl = path, row_base, row_excl
+        self.path_capacity = int(path_capacity)  # what the kernel is told (the buffer holds at least one entry)
+        self.max_path = int(max_path) if max_path else self.path_capacity
+        self.path_grown = 0
         self.dirty = dirty  # [T, capacity] int32 or None: per stack row the variable it was branched on (pcp_dfs_state.dirty); moves with its row
         self.max_capacity = int(max_capacity) if max_capacity else int(lb.shape[1])
         self.on_grow = on_grow
@@ -216,7 +224,30 @@ class ForestStacks:
             t = torch.full((T, new), -1, dtype=self.dirty.dtype, device=self.dirty.device)
             t[:, :cap] = self.dirty
             self.dirty = t
+        if self.row_base is not None:  # (rows beyond sp are written before they are read)
+            t = torch.zeros((T, new), dtype=self.row_base.dtype, device=self.row_base.device)
+            t[:, :cap] = self.row_base
+            self.row_base = t
+            t = torch.zeros((T, new, 2), dtype=self.row_excl.dtype, device=self.row_excl.device)
+            t[:, :, 0] = -1
+            t[:, :cap] = self.row_excl
+            self.row_excl = t
         self.grown += 1
+        if self.on_grow:
+            self.on_grow(self)
+        return True
+
+    def grow_path(self) -> bool:
+        """Double every tree's exclusion path (entries stay where they are) up to ``max_path``; False at the ceiling."""
+        import torch
+        cap = self.path_capacity
+        new = min(max(2 * cap, 1), self.max_path)
+        if new <= cap:
+            return False
+        t = torch.zeros((self.path.shape[0], new, 2), dtype=self.path.dtype, device=self.path.device)
+        t[:, :self.path.shape[1]] = self.path
+        self.path, self.path_capacity = t, new
+        self.path_grown += 1
         if self.on_grow:
             self.on_grow(self)
         return True
@@ -228,11 +259,24 @@ def run_forest_loop(launch, fs: ForestStacks, stop_on_solution: bool = False, no
     stacks ``fs``; between launches a tree whose stack is full gets more rows (ForestStacks.grow: memory follows the depth actually
     reached instead of being reserved for the worst case) and finished trees take work — from trees of this GPU, then (``dist``) from
     other ranks.  With ``dist`` every rank runs the same number of launches and the end of the search / node_budget are decided on
-    the all-reduced summary.  Returns dict(launches, steals, moved_rows, moved_bytes, exchange_s, grown, capacity)."""
+    the all-reduced summary.  Returns dict(launches, steals, moved_rows, moved_bytes, exchange_s, grown, capacity).
+    Under Enumerate (``fs.path`` is there; one rank) a tree that reports error 5 gets a longer path (ForestStacks.grow_path) and is resumed
+    as one with error 1 is, and a stolen bottom row takes its list along: the first row_base[d, 0] entries of the donor's path and the row's
+    two words go to the receiver, the donor's row words shift down with its rows, and the donor's path stays — its other rows still use that
+    prefix.  The result then also names ``first_steal``: the donor's bottom node before the first steal and the receiver's row 0 after it,
+    each as (lb, ub, entries [k, 2])."""
     import time
     import torch
     T = int(fs.sp.shape[0])
     launches = steals = fatal = 0
+    enum = fs.path is not None
+    first_steal = None
+
+    def node_of(t):  # row 0 of tree t as (lb, ub, its list)
+        nb = int(fs.row_base[t, 0])
+        own = fs.row_excl[t, 0].cpu().numpy()
+        ent = fs.path[t, :nb].cpu().numpy()
+        return fs.lb[t, 0].cpu().numpy(), fs.ub[t, 0].cpu().numpy(), (np.concatenate([ent, own[None]]) if own[0] != -1 else ent)
     xinfo = {"moved_rows": 0, "moved_bytes": 0}
     exchange_s = 0.0
     multi = dist is not None and dist.get_world_size() > 1
@@ -243,7 +287,11 @@ def run_forest_loop(launch, fs: ForestStacks, stop_on_solution: bool = False, no
         live = (sp > 0) & (stop == 0)
         err = counters[:, 3]
         full = err == 1  # stack full: the node stayed on top of its stack, uncounted (pcp_hip.h, pcp_dfs_device)
-        summary = torch.stack([live.sum(), counters[:, 0].sum(), counters[:, 1].sum(), full.sum(), ((err != 0) & ~full).sum() + fatal]).to(torch.int64)
+        pfull = (err == 5) if enum else None  # exclusion path full: the same contract
+        if enum:
+            summary = torch.stack([live.sum(), counters[:, 0].sum(), counters[:, 1].sum(), full.sum(), ((err != 0) & ~full & ~pfull).sum() + fatal, pfull.sum()]).to(torch.int64)
+        else:
+            summary = torch.stack([live.sum(), counters[:, 0].sum(), counters[:, 1].sum(), full.sum(), ((err != 0) & ~full).sum() + fatal]).to(torch.int64)
         mine = summary.cpu().tolist()  # (the launch's only synchronisation on one GPU)
         vals = mine
         if multi:
@@ -262,8 +310,16 @@ def run_forest_loop(launch, fs: ForestStacks, stop_on_solution: bool = False, no
                 break  # the ceiling is reached: the trees keep error 1 (the caller reports it)
             else:
                 fatal = 1  # (several ranks leave the loop TOGETHER: the flag travels with the next launch's summary)
+        elif enum and mine[5]:
+            pass
         elif vals[0] == 0 and vals[3] == 0:
             break
+        if enum and mine[5]:
+            if not fs.grow_path():
+                break  # the ceiling is reached: the trees keep error 5
+            idx = torch.nonzero(pfull).flatten()
+            fs.counters[idx, 3] = 0
+            fs.stop[idx] = 0
         if not rebalance:
             continue
         lb, ub, sp = fs.lb, fs.ub, fs.sp
@@ -275,8 +331,15 @@ def run_forest_loop(launch, fs: ForestStacks, stop_on_solution: bool = False, no
             spc = sp.cpu().numpy().copy()
             idle = [int(i) for i in np.nonzero(spc == 0)[0]]
             donors = [int(i) for i in np.argsort(-spc, kind="stable") if spc[i] >= 2][:len(idle)]
+            rb0 = fs.row_base[:, 0].cpu().numpy() if enum and donors else None
             for d, r in zip(donors, idle):
                 k = int(spc[d])
+                if enum:
+                    before = node_of(d) if first_steal is None else None
+                    nb = int(rb0[d])
+                    fs.path[r, :nb] = fs.path[d, :nb]
+                    fs.row_base[r, 0] = nb; fs.row_excl[r, 0] = fs.row_excl[d, 0]
+                    fs.row_base[d, 0:k - 1] = fs.row_base[d, 1:k].clone(); fs.row_excl[d, 0:k - 1] = fs.row_excl[d, 1:k].clone()
                 lb[r, 0] = lb[d, 0]; ub[r, 0] = ub[d, 0]
                 lb[d, 0:k - 1] = lb[d, 1:k].clone(); ub[d, 0:k - 1] = ub[d, 1:k].clone()
                 if fs.dirty is not None:  # a row's hint moves with it
@@ -285,35 +348,54 @@ def run_forest_loop(launch, fs: ForestStacks, stop_on_solution: bool = False, no
                 sp[d] = k - 1; sp[r] = 1
                 spc[d] = k - 1; spc[r] = 1
                 steals += 1
+                if enum and first_steal is None:
+                    first_steal = {"donor": d, "receiver": r, "before": before, "after": node_of(r)}
         if multi:
             t0 = time.perf_counter()
             if spc is None:
                 spc = sp.cpu().numpy().copy()
             refill_across_ranks(lb, ub, sp, spc, dist, xinfo, dirty=fs.dirty)
             exchange_s += time.perf_counter() - t0
-    return {"launches": launches, "steals": steals, "moved_rows": xinfo["moved_rows"], "moved_bytes": xinfo["moved_bytes"], "exchange_s": exchange_s,
-            "grown": fs.grown, "capacity": fs.capacity}
+    out = {"launches": launches, "steals": steals, "moved_rows": xinfo["moved_rows"], "moved_bytes": xinfo["moved_bytes"], "exchange_s": exchange_s,
+           "grown": fs.grown, "capacity": fs.capacity}
+    if enum:
+        out["first_steal"] = first_steal
+    return out
 
 
-def seed_roots_interval(ctx, lb0, ub0, want: int, objective=None):
+def seed_roots_interval(ctx, lb0, ub0, want: int, objective=None, brancher: str = "split", val: str = "middle"):
     """Interval mode: breadth-first expansion of the root to at least `want` open nodes.  ``objective``: the expansion runs under branch and
-    bound (DeviceSearch(objective=)), its stats carry the incumbent (``best``, ``best_solution``).  Returns (lb rows, ub rows, stats)."""
+    bound (DeviceSearch(objective=)), its stats carry the incumbent (``best``, ``best_solution``).  Returns (lb rows, ub rows, stats).
+    ``brancher="enumerate"``: the expansion runs under Enumerate on ``val`` (DeviceSearch(brancher="enumerate", val=, objective=)) and a
+    fourth value is returned: each root's exclusion list, a [k, 2] int32 array of (var, value)."""
     from .search_device import DeviceSearch
-    ds = DeviceSearch(ctx, batch=max(want, 1), capacity=4 * max(want, 1) + 64, implicit=True, objective=objective)
+    if brancher == "split":
+        ds = DeviceSearch(ctx, batch=max(want, 1), capacity=4 * max(want, 1) + 64, implicit=True, objective=objective)
+    else:
+        ds = DeviceSearch(ctx, batch=max(want, 1), capacity=4 * max(want, 1) + 64, implicit=True, objective=objective, brancher=brancher, val=val)
     ds.reset(lb0, ub0)
     while 0 < ds.size < want:
         if ds.advance(all_solutions=True, max_rounds=1, keep_solutions=0):
             break
     ds.compact()
     k = ds.size
-    return ds.lb[:k].clone(), ds.ub[:k].clone(), ds.stats
+    if brancher == "split":
+        return ds.lb[:k].clone(), ds.ub[:k].clone(), ds.stats
+    lists = []
+    if k:  # the one segment's offsets (relative to its first entry) and entries
+        o, e0, _, _ = ds.esegs[-1]
+        off = ds.eoff[o:o + k + 1].cpu().numpy().astype(np.int64)
+        ex = ds.ex[e0:e0 + int(off[-1])].cpu().numpy().reshape(-1, 2)
+        lists = [np.ascontiguousarray(ex[off[i]:off[i + 1]], np.int32) for i in range(k)]
+    return ds.lb[:k].clone(), ds.ub[:k].clone(), ds.stats, lists
 
 
 STACK_BYTES_CAP = 64 << 30  # default ceiling of the forest's stack rows per GPU (both bound arrays together); rows are allocated as trees get deep
 
 
 def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_per_launch: int = 512, rank: int = 0, world: int = 1, capacity: int = 0,
-                  dist=None, info: dict | None = None, stack_bytes: int = STACK_BYTES_CAP, formulas: bool = False, small: bool = False) -> dict:
+                  dist=None, info: dict | None = None, stack_bytes: int = STACK_BYTES_CAP, formulas: bool = False, small: bool = False, brancher: str = "split",
+                  val: str = "middle") -> dict:
     """Interval mode, all-XNeqY models: expansion + one in-kernel DFS per open node (pcp_dfs_forest_device).  formulas: the store holds
     formula propagators (what Cumulative.join builds): the trees run in pcp_dfs_forest_device_form, one per wavefront.  small: a small store of
     plain propagators of any kind (the Golomb network): pcp_dfs_forest_device_small, one tree per wavefront; with formulas=True a ValueError.  The node limit is checked
@@ -321,10 +403,21 @@ def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_
     its share of the limit; with ``dist`` (torch.distributed, world ranks) the limit is global, finished trees are refilled (also across
     ranks) and the returned counters are still this rank's.  A tree's stack holds its OPEN nodes (one right branch per level of
     its current path); the rows are allocated on demand (ForestStacks.grow) up to ``stack_bytes`` for the whole forest — a tree
-    that needs more reports error 1."""
+    that needs more reports error 1.
+    brancher / val: the distributor of the expansion AND of the trees ("enumerate": Enumerate on MiddleVal or MinVal; small=True only, one
+    rank — with ``dist``, ``world`` > 1, ``formulas=True`` or the all-XNeqY forest a ValueError): the roots arrive with the exclusion lists the
+    expansion gave them, so that the expansion and the trees together are one Enumerate tree."""
     if small and formulas:
         raise ValueError("forest_search: small=True and formulas=True name two different forests (a store has formula units or it has none)")
-    rl, ru, st = seed_roots_interval(ctx, lb0, ub0, n_trees * world)
+    from .engine import _check_forest_brancher
+    enum = _check_forest_brancher("forest_search", brancher, val, small, dist)
+    if enum and world > 1:
+        raise ValueError("forest_search: brancher='enumerate' does not run on several ranks (moving exclusion lists between ranks is not built)")
+    lists = None
+    if enum:
+        rl, ru, st, lists = seed_roots_interval(ctx, lb0, ub0, n_trees, brancher=brancher, val=val)
+    else:
+        rl, ru, st = seed_roots_interval(ctx, lb0, ub0, n_trees * world)
     ml, mu = rl[rank::world].contiguous(), ru[rank::world].contiguous()
     out = {"seeded_nodes": st.num_nodes if rank == 0 else 0, "trees": int(ml.shape[0]), "launches": 0,
            "nodes": st.num_nodes if rank == 0 else 0, "solutions": st.num_solution if rank == 0 else 0, "failed": st.num_failed_node if rank == 0 else 0, "error": 0}
@@ -359,14 +452,15 @@ def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_
             upfront = max(upfront, torch.cuda.mem_get_info(ml.device)[0] // 8)
         capacity = ceiling if (per_tree and not multi and ceiling * row_bytes <= upfront) else min(128, ceiling)
     r = ctx.dfs_forest(ml, mu, node_limit_per_tree=0 if multi else per_tree, steps_per_launch=steps_per_launch, capacity=capacity, max_capacity=max(ceiling, capacity),
-                       node_budget=max(node_limit - st.num_nodes, 1) if multi else budget, dist=dist if multi else None, info=info, sp0=sp0, formulas=formulas, small=small)
+                       node_budget=max(node_limit - st.num_nodes, 1) if multi else budget, dist=dist if multi else None, info=info, sp0=sp0, formulas=formulas, small=small,
+                       **(dict(brancher=brancher, val=val, root_excl=lists) if enum else {}))
     out["nodes"] += r["nodes"]; out["solutions"] += r["solutions"]; out["failed"] += r["failed"]
     out["error"] = r["error"]; out["launches"] = r["launches"]
     return out
 
 
 def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: int = 512, best0=None, capacity: int = 128, max_capacity: int = 1 << 16,
-               info: dict | None = None, formulas: bool = True, small: bool = False) -> dict:
+               info: dict | None = None, formulas: bool = True, small: bool = False, brancher: str = "split", val: str = "middle") -> dict:
     """Branch and bound over an Interval store with formula propagators (branch_and_bound.rs:64-84 around the loop of forest_search):
     minimize / maximize ``objective`` = (var, "min" | "max") below (lb0, ub0).  The root is expanded breadth-first under branch and bound
     (seed_roots_interval with DeviceSearch(objective=)) to at least ``n_trees`` open nodes; each becomes a tree of
@@ -374,11 +468,18 @@ def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: i
     expansion's solutions take part.  Returns the dict of Context.dfs_forest_bnb (``nodes`` / ``solutions`` / ``failed`` include the
     expansion's, ``seeded_nodes`` names them); ``best`` is None when neither the expansion nor a tree found a solution beating ``best0``.
     ``small``: a small store of plain propagators instead (Context.dfs_forest_bnb(small=True) — model.golomb_ruler); it wins over
-    ``formulas``, whose default is True."""
+    ``formulas``, whose default is True.  brancher / val: as for forest_search — Enumerate needs ``small=True``; the expansion then
+    runs under DeviceSearch(brancher="enumerate", val=, objective=) and the roots keep their exclusion lists."""
     if not formulas and not small:
         raise ValueError("forest_bnb searches stores with formula propagators (all-XNeqY stores have no objective to bound)")
+    from .engine import _check_forest_brancher
+    enum = _check_forest_brancher("forest_bnb", brancher, val, small, None)
     var, mode = objective
-    rl, ru, st = seed_roots_interval(ctx, lb0, ub0, n_trees, objective=(int(var), mode))
+    lists = None
+    if enum:
+        rl, ru, st, lists = seed_roots_interval(ctx, lb0, ub0, n_trees, objective=(int(var), mode), brancher=brancher, val=val)
+    else:
+        rl, ru, st = seed_roots_interval(ctx, lb0, ub0, n_trees, objective=(int(var), mode))
     better = min if mode == "min" else max
     known = [b for b in (best0, st.best) if b is not None]
     start = better(known) if known else None
@@ -388,7 +489,8 @@ def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: i
                "best": None, "best_solution": None}
     else:
         out = ctx.dfs_forest_bnb(rl, ru, (int(var), mode), best0=start, steps_per_launch=steps_per_launch, capacity=capacity,
-                                 max_capacity=max(max_capacity, capacity), info=info, small=small)
+                                 max_capacity=max(max_capacity, capacity), info=info, small=small,
+                                 **(dict(brancher=brancher, val=val, root_excl=lists) if enum else {}))
     out["seeded_nodes"] = st.num_nodes
     out["nodes"] += st.num_nodes; out["solutions"] += st.num_solution; out["failed"] += st.num_failed_node
     # no tree beat the expansion's incumbent: it is the optimum, unless the caller's bound was already as good
