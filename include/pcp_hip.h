@@ -673,6 +673,38 @@ typedef struct {
 int32_t pcp_dfs_forest_device_small_enum(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex,
                                          const pcp_forest_objective* obj, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
                                          void* hip_stream);
+/* The solution sink: every solution of an Interval forest, not only their number.  A device-side append buffer of (lb, ub) rows that every
+ * tree of pcp_dfs_forest_device_form, pcp_dfs_forest_device_small and pcp_dfs_forest_device_small_enum (obj == NULL) writes its solutions
+ * into — the visitor of AllSolution (search/engine/all_solution.rs), resp. OneSolution called in a loop (one_solution.rs:92-105).  A row is
+ * the WHOLE node: in interval mode a True node is a box — every unit is entailed while domains may still be wider than one value — and
+ * every point of it is a solution; first_solution keeps its lower bounds only.
+ *   lb, ub   : [capacity][n_vars] device int32: row i = the i-th solution appended
+ *   tree     : [capacity] device uint32 or NULL: the tree that wrote row i
+ *   count    : device uint32: tickets drawn since the caller last zeroed it.  It may exceed capacity: the valid rows are min(*count, capacity)
+ *   capacity : rows (> 0);  reserved : 0
+ * The sink belongs to the context, like the options: the struct is copied at the call, the buffers stay the caller's, NULL detaches.  One
+ * context is one queue of launches; the caller reads and zeroes *count between launches, never during one.
+ * THE PROTOCOL.  A node found to be a solution (not the StopNode limit node, which is none: stop_node.rs:57-62) draws a ticket,
+ * slot = (*count)++, BEFORE it is counted.  slot < capacity: the node's (lb, ub) go to row slot, tree[slot] = t, and the step goes on as
+ * without a sink — the node is counted, first_solution kept, stop raised under stop_on_solution.  slot >= capacity: error 6, "sink full" —
+ * nothing is counted, the node stays on the stack as row sp - 1, propagated (under Enumerate its row_base / row_excl name the list it ran
+ * under, with no entry of its own), and stop is raised: the contract of error 1.  A caller that copies the rows out, zeroes *count, clears
+ * that tree's error and stop and calls again runs the node again — propagation is idempotent — and it is counted and appended then.  So
+ * after any number of such hand-backs nodes / solutions / failed of every tree are what a sink that never fills leaves, and no solution is
+ * lost or written twice.  Rows are in ticket order, which between trees is an order in time.
+ * With a sink attached the branch-and-bound entries (pcp_dfs_forest_device_form_bnb, _small_bnb, _small_enum with obj != NULL: they keep
+ * tree_row), the all-XNeqY forest pcp_dfs_forest_device and every set-mode forest entry (pcp_dfs_forest_device_set, _set_enum, _set_bnb,
+ * _setform, _setform_bnb) return PCP_ERR_UNSUPPORTED and launch nothing; with none attached every entry does what it did before.
+ * A null lb, ub or count, capacity == 0, reserved != 0: PCP_ERR_ARG, and the sink attached before stays. */
+typedef struct {
+  int32_t* lb;
+  int32_t* ub;
+  uint32_t* tree;
+  uint32_t* count;
+  uint32_t capacity;
+  uint32_t reserved;
+} pcp_solution_sink;
+int32_t pcp_solution_sink_set(pcp_ctx* ctx, const pcp_solution_sink* sink);
 /* Between two calls of pcp_dfs_forest_device_set* / _setform*: finished trees take over work from trees that still have some.  pairs = n_pairs x
  * (donor, receiver) tree indices (device uint32).  For every pair whose receiver is finished and whose donor has an open right branch
  * left, the donor's OLDEST open right branch (the subtree nearest its root) becomes the receiver's new root — built from the donor's

@@ -72,6 +72,7 @@ struct pcp_ctx : HostModel, LoweredInfo {
   // host-buffer path staging
   void* d_stage = nullptr; size_t cap_stage = 0;
 
+  SinkDev sink{};         // pcp_solution_sink_set: the solution sink of the Interval forests (sink.lb == null: none attached)
   pcp_plan last_plan{};   // geometry of the last launch (pcp_last_plan)
   const uint32_t* dfs_sp = nullptr;    // set by pcp_dfs_device around its launches: LaunchArgs::sp_ptr / stop_ptr
   size_t dfs_team_words = 0;           // words of d_team the step kernel zeroes after each step (0: the launch clears them itself)
@@ -132,6 +133,12 @@ int32_t hip_fail(pcp_ctx* c, hipError_t e, const char* what) {
     hipError_t e__ = (call);                                 \
     if (e__ != hipSuccess) return hip_fail((c), e__, #call); \
   } while (0)
+
+// A forest entry that cannot write into the context's solution sink refuses to run while one is attached (pcp_solution_sink_set): a caller
+// that asked for every solution never gets a count without them.
+int32_t refuse_sink(pcp_ctx* c, const std::string& who, const char* why) {
+  return fail(c, PCP_ERR_UNSUPPORTED, who + ": a solution sink is attached (pcp_solution_sink_set) and " + why + "; detach it with pcp_solution_sink_set(ctx, NULL)");
+}
 
 template <class T>
 int32_t ensure(pcp_ctx* c, T*& p, size_t& cap, size_t n) {
@@ -1059,6 +1066,7 @@ static int32_t dfs_forest_set(pcp_ctx* c, const pcp_forest_state* st, const pcp_
                               uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
   if (!c || !st) return PCP_ERR_ARG;
   const char* const who = obj ? "pcp_dfs_forest_device_set_bnb" : (enumerate ? "pcp_dfs_forest_device_set_enum" : "pcp_dfs_forest_device_set");
+  if (c->sink.lb) return refuse_sink(c, who, "the set-mode forests do not write into it");
   SetDfsArgs a;
   const int32_t rc = forest_set_args(c, who, st, obj, val,
                                      c->has_formulas ? ": pcp_dfs_forest_device_set evaluates records, not formula trees: a store with formula propagators (Boolean / pcp_model_push_formula) is searched by pcp_dfs_forest_device_setform" : nullptr,
@@ -1100,6 +1108,7 @@ int32_t pcp_dfs_forest_device_set_bnb(pcp_ctx* c, const pcp_forest_state* st, co
 static int32_t dfs_forest_setform(pcp_ctx* c, const pcp_forest_state* st, const pcp_forest_objective* obj, uint32_t enumerate, uint32_t val, uint32_t n_steps,
                                   uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
   const char* const who = obj ? "pcp_dfs_forest_device_setform_bnb" : "pcp_dfs_forest_device_setform";
+  if (c->sink.lb) return refuse_sink(c, who, "the set-mode forests do not write into it");
   if (enumerate > 1) return fail(c, PCP_ERR_ARG, std::string(who) + ": enumerate must be 0 or 1");
   SetFormDfsArgs fa;
   memset(&fa, 0, sizeof(fa));
@@ -1186,6 +1195,7 @@ static int32_t launch_neq_dfs(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_tr
 
 int32_t pcp_dfs_forest_device(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
   if (!c || !st) return PCP_ERR_ARG;
+  if (c->sink.lb) return refuse_sink(c, "pcp_dfs_forest_device", "the all-XNeqY forest does not write into it (pcp_dfs_forest_device_small takes an all-XNeqY store within its limits)");
   if (c->set_words) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device runs interval-mode models (sets: pcp_dfs_forest_device_set)");
   if (!n_trees || !st->lb || !st->ub || !st->sp || !st->stop || !st->status || !st->counters || st->capacity < 2) return fail(c, PCP_ERR_ARG, "null buffer / no tree / capacity < 2");
   HIP_TRY(c, hipSetDevice(c->device));
@@ -1202,6 +1212,7 @@ int32_t pcp_dfs_forest_device(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_tr
 static int32_t dfs_forest_form(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_objective* obj, uint32_t n_steps, uint32_t stop_on_solution,
                                uint64_t node_limit, void* hip_stream) {
   const std::string who = obj ? "pcp_dfs_forest_device_form_bnb" : "pcp_dfs_forest_device_form";
+  if (obj && c->sink.lb) return refuse_sink(c, who, "branch and bound keeps tree_row instead");
   if (c->set_words) return fail(c, PCP_ERR_ARG, who + " runs interval-mode models (sets: pcp_dfs_forest_device_setform)");
   if (!n_trees || !st->lb || !st->ub || !st->sp || !st->stop || !st->status || !st->counters || st->capacity < 2)
     return fail(c, PCP_ERR_ARG, who + ": null buffer / no tree / capacity < 2");
@@ -1231,6 +1242,7 @@ static int32_t dfs_forest_form(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_t
   a.first_solution = obj ? nullptr : st->first_solution;
   a.violation = c->d_retry + 1; a.stats = c->d_stats;
   if (obj) { a.obj_var = obj->var; a.obj_mode = obj->mode; a.obj_best = obj->best; a.tree_best = obj->tree_best; a.tree_row = obj->tree_row; }
+  a.sink = c->sink;
   LaunchPlan plan;
   plan.block = 64 * waves; plan.lds_bytes = lds; plan.grid = (n_trees + waves - 1) / waves;
   c->last_plan = pcp_plan{waves, 1u, 0u, 0u, 0u, 0u, 1u, 0u, plan.grid, plan.block, (uint32_t)lds, 0u, 3u};
@@ -1256,6 +1268,7 @@ int32_t pcp_dfs_forest_device_form_bnb(pcp_ctx* c, const pcp_dfs_state* st, uint
 static int32_t dfs_forest_small(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex, const pcp_forest_objective* obj, uint32_t n_steps,
                                 uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
   const std::string who = ex ? "pcp_dfs_forest_device_small_enum" : obj ? "pcp_dfs_forest_device_small_bnb" : "pcp_dfs_forest_device_small";
+  if (obj && c->sink.lb) return refuse_sink(c, who, "branch and bound keeps tree_row instead");
   if (c->set_words) return fail(c, PCP_ERR_ARG, who + " runs interval-mode models (sets: pcp_dfs_forest_device_set)");
   if (!n_trees || !st->lb || !st->ub || !st->sp || !st->stop || !st->status || !st->counters || st->capacity < 2)
     return fail(c, PCP_ERR_ARG, who + ": null buffer / no tree / capacity < 2");
@@ -1293,6 +1306,7 @@ static int32_t dfs_forest_small(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_
   a.violation = c->d_retry + 1; a.stats = c->d_stats;
   if (obj) { a.obj_var = obj->var; a.obj_mode = obj->mode; a.obj_best = obj->best; a.tree_best = obj->tree_best; a.tree_row = obj->tree_row; }
   if (ex) { a.path = ex->path; a.row_base = ex->row_base; a.row_excl = ex->row_excl; a.path_capacity = ex->path_capacity; a.val = ex->val; }
+  a.sink = c->sink;
   LaunchPlan plan;
   plan.block = 64 * waves; plan.lds_bytes = lds; plan.grid = (n_trees + waves - 1) / waves;
   c->last_plan = pcp_plan{waves, 1u, 0u, 0u, 0u, 0u, 1u, 0u, plan.grid, plan.block, (uint32_t)lds, 0u, 4u};
@@ -1316,6 +1330,16 @@ int32_t pcp_dfs_forest_device_small_enum(pcp_ctx* c, const pcp_dfs_state* st, ui
                                          uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
   if (!c || !st || !ex) return c ? fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_small_enum: null state / exclusions") : PCP_ERR_ARG;
   return dfs_forest_small(c, st, n_trees, ex, obj, n_steps, obj ? 0u : stop_on_solution, node_limit, hip_stream);
+}
+
+int32_t pcp_solution_sink_set(pcp_ctx* c, const pcp_solution_sink* sink) {
+  if (!c) return PCP_ERR_ARG;
+  if (!sink) { c->sink = SinkDev{}; return PCP_OK; }
+  if (!sink->lb || !sink->ub || !sink->count) return fail(c, PCP_ERR_ARG, "pcp_solution_sink_set: lb, ub and count are required");
+  if (!sink->capacity) return fail(c, PCP_ERR_ARG, "pcp_solution_sink_set: capacity must be at least one row");
+  if (sink->reserved) return fail(c, PCP_ERR_ARG, "pcp_solution_sink_set: reserved must be 0");
+  c->sink = SinkDev{sink->lb, sink->ub, sink->tree, sink->count, sink->capacity};
+  return PCP_OK;
 }
 
 int32_t pcp_dfs_device(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {

@@ -28,7 +28,9 @@ namespace pcp {
 
 namespace {
 
-template <bool BNB>
+// SINK = true (never with BNB): every solution is appended to the context's solution sink (SinkDev, pcp_neq.h) as a whole (lb, ub) row — a
+// True node is a box, not a point.  A template flag, so that the instantiations without a sink are the code they were.
+template <bool BNB, bool SINK>
 __global__ void __launch_bounds__(256) formdfs_kernel(const FormDfsArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t lane = threadIdx.x & 63;
@@ -174,6 +176,23 @@ __global__ void __launch_bounds__(256) formdfs_kernel(const FormDfsArgs a) {
       new_sp = sp + 1;
       in_lds = true;
     }
+    if constexpr (SINK) {
+      // A solution draws its ticket BEFORE it is counted (the limit node, `nodes + 1` at the limit, is no solution and draws none).  6: the
+      // sink is full — the node stays on the stack, propagated and uncounted, and a caller that drains the sink and resumes runs it again
+      // (idempotent), counts it then and appends it then (the contract of error 1)
+      if (!failed && !unknown && !(a.node_limit && nodes + 1 >= a.node_limit)) {
+        uint32_t slot = 0;
+        if (lane == 0) slot = __hip_atomic_fetch_add(a.sink.count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        slot = __builtin_amdgcn_readfirstlane(slot);
+        if (slot >= a.sink.capacity) {
+          store_row(node);
+          error = kDfsSinkFull; stop = 1;
+          break;
+        }
+        for (uint32_t v = lane; v < V; v += 64) { const int2 d = dom[v]; a.sink.lb[(size_t)slot * V + v] = -d.x; a.sink.ub[(size_t)slot * V + v] = d.y; }
+        if (lane == 0 && a.sink.tree) a.sink.tree[slot] = t;
+      }
+    }
     // Monitor<Statistics, StopNode>: the node that reaches the limit is a node, but neither a solution nor a failure (stop_node.rs:57-62, 90-97)
     ++nodes;
     const bool last = a.node_limit && nodes >= a.node_limit;
@@ -221,13 +240,13 @@ __global__ void __launch_bounds__(256) formdfs_kernel(const FormDfsArgs a) {
   }
 }
 
-template <bool BNB>
+template <bool BNB, bool SINK>
 hipError_t launch_formdfs_as(const FormDfsArgs& a, const LaunchPlan& p, hipStream_t stream) {
   hipError_t e;
   if (p.lds_bytes > 64 * 1024 &&
-      (e = hipFuncSetAttribute(reinterpret_cast<const void*>(formdfs_kernel<BNB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes)) != hipSuccess)
+      (e = hipFuncSetAttribute(reinterpret_cast<const void*>(formdfs_kernel<BNB, SINK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes)) != hipSuccess)
     return e;
-  hipLaunchKernelGGL((formdfs_kernel<BNB>), dim3(p.grid), dim3(p.block), p.lds_bytes, stream, a);
+  hipLaunchKernelGGL((formdfs_kernel<BNB, SINK>), dim3(p.grid), dim3(p.block), p.lds_bytes, stream, a);
   return hipGetLastError();
 }
 
@@ -240,7 +259,11 @@ size_t lds_bytes_formdfs(uint32_t n_slots, uint32_t n_units, uint32_t waves) {
 
 // p.block = 64 x the trees of a workgroup, p.grid = ceil(n_trees / those), p.lds_bytes = lds_bytes_formdfs of them
 hipError_t launch_formdfs(const FormDfsArgs& a, bool bnb, const LaunchPlan& p, hipStream_t stream) {
-  return bnb ? launch_formdfs_as<true>(a, p, stream) : launch_formdfs_as<false>(a, p, stream);
+  if (a.sink.lb) {  // the context's solution sink (pcp_solution_sink_set); the branch-and-bound entries refuse it
+    if (bnb || !a.sink.ub || !a.sink.count || !a.sink.capacity) return hipErrorInvalidValue;
+    return launch_formdfs_as<false, true>(a, p, stream);
+  }
+  return bnb ? launch_formdfs_as<true, false>(a, p, stream) : launch_formdfs_as<false, false>(a, p, stream);
 }
 
 }  // namespace pcp

@@ -119,6 +119,18 @@ struct FormExclArgs {
 };
 hipError_t launch_formexcl(const FormExclArgs& a, const LaunchPlan& p, hipStream_t stream);
 
+// The solution sink of a context (pcp_solution_sink_set): an append buffer of (lb, ub) rows every tree of an Interval forest writes its
+// solutions into.  A solution draws a ticket from *count BEFORE it is counted; a ticket >= capacity hands the node back to the caller
+// (error kDfsSinkFull, the contract of error 1).  The SINK = false instantiations never read the struct.
+struct SinkDev {
+  int32_t* lb;        // [capacity][n_vars]
+  int32_t* ub;
+  uint32_t* tree;     // [capacity] or null: the tree that wrote the row
+  uint32_t* count;    // tickets drawn since the caller last zeroed it
+  uint32_t capacity;
+};
+constexpr uint32_t kDfsSinkFull = 6;  // counters[t][3]: the sink was full — the node stays on the stack, propagated and uncounted
+
 // The search loop over such a store on the device: one tree per WAVEFRONT on its own stack of (lb, ub) rows, the node being run in that
 // wavefront's LDS slice (pcp_formdfs.hip).  The stacks are a pcp_dfs_state laid out as for pcp_dfs_forest_device.
 struct FormDfsArgs {
@@ -141,8 +153,10 @@ struct FormDfsArgs {
   int32_t* obj_best;             // device int32[1]: the forest's incumbent
   int32_t* tree_best;            // [n_trees]: the value of each tree's last solution
   int32_t* tree_row;             // [n_trees][n_vars] or null: its lower bounds
+  SinkDev sink;                  // the context's solution sink (formdfs_kernel<false, true>); sink.lb == null: none
 };
 size_t lds_bytes_formdfs(uint32_t n_slots, uint32_t n_units, uint32_t waves);  // one slice per tree; 0 = beyond a CU's LDS
+// (a.sink.lb != null: the instantiation that appends every solution to the sink; never together with bnb)
 hipError_t launch_formdfs(const FormDfsArgs& a, bool bnb, const LaunchPlan& p, hipStream_t stream);
 
 // The same stores over IntervalSet<i32> domains (set mode): the trees as above, the node's sets as bit words in LDS (pcp_setform.hip).
@@ -247,8 +261,10 @@ struct SmallDfsArgs {
   uint32_t* row_base;            // [n_trees][capacity]: the path entries a stack row inherits
   pcp_excl* row_excl;            // [n_trees][capacity]: the entry appended when the row is popped (var 0xFFFFFFFF: none)
   uint32_t path_capacity, val;   // PCP_VAL_MIDDLE / PCP_VAL_MIN
+  SinkDev sink;                  // the context's solution sink (smalldfs_kernel<false, .., true>); sink.lb == null: none
 };
 size_t lds_bytes_smalldfs(uint32_t n_slots, uint32_t n_units, uint32_t n_recs, uint32_t waves);  // the records' copy + one slice per tree; 0 = beyond a CU's LDS
+// (a.sink.lb != null: the instantiations that append every solution to the sink; never together with bnb)
 hipError_t launch_smalldfs(const SmallDfsArgs& a, bool bnb, const LaunchPlan& p, hipStream_t stream);
 
 }  // namespace pcp

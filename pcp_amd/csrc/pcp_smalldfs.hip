@@ -45,7 +45,9 @@ namespace {
 
 constexpr uint32_t kNoExcl = 0xFFFFFFFFu;  // row_excl[r].var: the row appends nothing when it is popped
 
-template <bool BNB, bool ENUM>
+// SINK = true (never with BNB): every solution is appended to the context's solution sink (SinkDev, pcp_neq.h) as a whole (lb, ub) row — a
+// True node is a box, not a point.  A template flag, so that the instantiations without a sink are the code they were.
+template <bool BNB, bool ENUM, bool SINK>
 __global__ void __launch_bounds__(256) smalldfs_kernel(const SmallDfsArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t lane = threadIdx.x & 63;
@@ -300,6 +302,24 @@ __global__ void __launch_bounds__(256) smalldfs_kernel(const SmallDfsArgs a) {
       new_sp = sp + 1;
       in_lds = true;
     }
+    if constexpr (SINK) {
+      // A solution draws its ticket BEFORE it is counted (the limit node, `nodes + 1` at the limit, is no solution and draws none).  6: the
+      // sink is full — the node stays on the stack, propagated and uncounted, and a caller that drains the sink and resumes runs it again
+      // (idempotent), counts it then and appends it then (the contract of error 1)
+      if (!failed && !unknown && !(a.node_limit && nodes + 1 >= a.node_limit)) {
+        uint32_t slot = 0;
+        if (lane == 0) slot = __hip_atomic_fetch_add(a.sink.count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        slot = __builtin_amdgcn_readfirstlane(slot);
+        if (slot >= a.sink.capacity) {
+          store_row(node);
+          if (ENUM) store_row_words(node);
+          error = kDfsSinkFull; stop = 1;
+          break;
+        }
+        for (uint32_t v = lane; v < V; v += 64) { const int2 d = dom[v]; a.sink.lb[(size_t)slot * V + v] = -d.x; a.sink.ub[(size_t)slot * V + v] = d.y; }
+        if (lane == 0 && a.sink.tree) a.sink.tree[slot] = t;
+      }
+    }
     // Monitor<Statistics, StopNode>: the node that reaches the limit is a node, but neither a solution nor a failure (stop_node.rs:57-62, 90-97)
     ++nodes;
     const bool last = a.node_limit && nodes >= a.node_limit;
@@ -350,13 +370,13 @@ __global__ void __launch_bounds__(256) smalldfs_kernel(const SmallDfsArgs a) {
   }
 }
 
-template <bool BNB, bool ENUM>
+template <bool BNB, bool ENUM, bool SINK>
 hipError_t launch_smalldfs_as(const SmallDfsArgs& a, const LaunchPlan& p, hipStream_t stream) {
   hipError_t e;
   if (p.lds_bytes > 64 * 1024 &&
-      (e = hipFuncSetAttribute(reinterpret_cast<const void*>(smalldfs_kernel<BNB, ENUM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes)) != hipSuccess)
+      (e = hipFuncSetAttribute(reinterpret_cast<const void*>(smalldfs_kernel<BNB, ENUM, SINK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes)) != hipSuccess)
     return e;
-  hipLaunchKernelGGL((smalldfs_kernel<BNB, ENUM>), dim3(p.grid), dim3(p.block), p.lds_bytes, stream, a);
+  hipLaunchKernelGGL((smalldfs_kernel<BNB, ENUM, SINK>), dim3(p.grid), dim3(p.block), p.lds_bytes, stream, a);
   return hipGetLastError();
 }
 
@@ -370,11 +390,16 @@ size_t lds_bytes_smalldfs(uint32_t n_slots, uint32_t n_units, uint32_t n_recs, u
 // p.block = 64 x the trees of a workgroup, p.grid = ceil(n_trees / those), p.lds_bytes = lds_bytes_smalldfs of them
 hipError_t launch_smalldfs(const SmallDfsArgs& a, bool bnb, const LaunchPlan& p, hipStream_t stream) {
   if (!a.m.recs) return hipErrorInvalidValue;
+  // the context's solution sink (pcp_solution_sink_set); the branch-and-bound entries refuse it
+  const bool sink = a.sink.lb != nullptr;
+  if (sink && (bnb || !a.sink.ub || !a.sink.count || !a.sink.capacity)) return hipErrorInvalidValue;
   if (a.row_base) {  // Enumerate: the rows' words are there (pcp_dfs_forest_device_small_enum)
     if (!a.row_excl || (a.path_capacity && !a.path)) return hipErrorInvalidValue;
-    return bnb ? launch_smalldfs_as<true, true>(a, p, stream) : launch_smalldfs_as<false, true>(a, p, stream);
+    if (sink) return launch_smalldfs_as<false, true, true>(a, p, stream);
+    return bnb ? launch_smalldfs_as<true, true, false>(a, p, stream) : launch_smalldfs_as<false, true, false>(a, p, stream);
   }
-  return bnb ? launch_smalldfs_as<true, false>(a, p, stream) : launch_smalldfs_as<false, false>(a, p, stream);
+  if (sink) return launch_smalldfs_as<false, false, true>(a, p, stream);
+  return bnb ? launch_smalldfs_as<true, false, false>(a, p, stream) : launch_smalldfs_as<false, false, false>(a, p, stream);
 }
 
 }  // namespace pcp

@@ -25,7 +25,7 @@ ERRORS = {-1: "PCP_ERR_ARG", -2: "PCP_ERR_CONTRACT", -3: "PCP_ERR_HIP", -4: "PCP
 ABI_SYMBOLS = [
     "pcp_ctx_create", "pcp_ctx_destroy", "pcp_last_error", "pcp_strerror", "pcp_abi_version",
     "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull",
-    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
+    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
 ]
 
 
@@ -89,6 +89,55 @@ class ForestObjective(C.Structure):
 class ForestExcl(C.Structure):
     """pcp_forest_excl: the exclusions of pcp_dfs_forest_device_small_enum — one path of entries per tree, two words per stack row."""
     _fields_ = [("path", C.c_void_p), ("row_base", C.c_void_p), ("row_excl", C.c_void_p), ("path_capacity", C.c_uint32), ("val", C.c_uint32)]
+
+
+class PcpSolutionSink(C.Structure):
+    """pcp_solution_sink: the append buffer of (lb, ub) rows the Interval forests write every solution into (pcp_solution_sink_set)."""
+    _fields_ = [("lb", C.c_void_p), ("ub", C.c_void_p), ("tree", C.c_void_p), ("count", C.c_void_p), ("capacity", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+SINK_FULL = 6  # counters[t][3]: the sink was full — the node stays on top of its stack, propagated and uncounted (the contract of error 1)
+
+
+class SolutionSink:
+    """The buffers of a pcp_solution_sink and the host's side of its protocol: ``lb`` / ``ub`` [capacity, n_vars] int32, ``tree`` [capacity]
+    int32, ``count`` [1] int32 (torch tensors on ``device``; a CPU device serves the bookkeeping's tests).  ``drain()`` copies the
+    min(count, capacity) valid rows to the host — in ticket order, behind what earlier drains brought — and zeroes the count; the copies
+    are torch's, on the current stream of the device: the one Context.dfs_forest launches on.  ``rows()`` is everything drained so far."""
+
+    def __init__(self, capacity: int, n_vars: int, device):
+        import torch
+        if int(capacity) < 1:
+            raise ValueError(f"SolutionSink: capacity must be at least 1, not {capacity}")
+        self.capacity, self.n_vars = int(capacity), int(n_vars)
+        self.lb = torch.zeros((self.capacity, self.n_vars), dtype=torch.int32, device=device)
+        self.ub = torch.zeros((self.capacity, self.n_vars), dtype=torch.int32, device=device)
+        self.tree = torch.zeros(self.capacity, dtype=torch.int32, device=device)
+        self.count = torch.zeros(1, dtype=torch.int32, device=device)
+        self.drains = 0     # drain() calls
+        self.overdrawn = 0  # tickets beyond the capacity, over all drains: the nodes that were handed back
+        self._lb, self._ub, self._tree = [], [], []
+
+    def struct(self) -> PcpSolutionSink:
+        return PcpSolutionSink(self.lb.data_ptr(), self.ub.data_ptr(), self.tree.data_ptr(), self.count.data_ptr(), self.capacity, 0)
+
+    def drain(self) -> int:
+        """Move the valid rows to the host and zero the count.  Returns the number of rows moved."""
+        drawn = int(self.count.item()) & 0xFFFFFFFF  # (synchronises: the launches before it have ended)
+        n = min(drawn, self.capacity)
+        if n:
+            self._lb.append(self.lb[:n].cpu().numpy().copy())
+            self._ub.append(self.ub[:n].cpu().numpy().copy())
+            self._tree.append(self.tree[:n].cpu().numpy().copy())
+        self.drains += 1
+        self.overdrawn += drawn - n
+        self.count.zero_()
+        return n
+
+    def rows(self):
+        """(lb [n, n_vars], ub [n, n_vars], tree [n]) of every row drained so far, int32 numpy arrays."""
+        cat = lambda parts, shape: np.concatenate(parts) if parts else np.zeros(shape, np.int32)
+        return cat(self._lb, (0, self.n_vars)), cat(self._ub, (0, self.n_vars)), cat(self._tree, (0,))
 
 
 DFS_FULL = 0xFFFFFFFF
@@ -169,6 +218,7 @@ def load_library():
     L.pcp_dfs_forest_device_small.argtypes = [vp, C.POINTER(DfsState), u32, u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_small_bnb.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestObjective), u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_small_enum.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestExcl), C.POINTER(ForestObjective), u32, u32, C.c_uint64, vp]
+    L.pcp_solution_sink_set.argtypes = [vp, C.POINTER(PcpSolutionSink)]
     L.pcp_stats_reset.argtypes = [vp, vp]
     L.pcp_stats_read.argtypes = [vp, C.POINTER(PcpStats), vp]
     L.pcp_debug_counters.argtypes = [vp, C.POINTER(C.c_uint64), u32, vp]
@@ -176,7 +226,7 @@ def load_library():
     L.pcp_last_plan.argtypes = [vp, C.POINTER(PcpPlan)]
     L.pcp_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
     for f in ("pcp_ctx_create", "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull", "pcp_model_set_hull",
-              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
+              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
         getattr(L, f).restype = i32
     _lib = L
     return L
@@ -518,10 +568,18 @@ class Context:
         return {"nodes": cn[0], "solutions": cn[1], "failed": cn[2], "error": cn[3], "open": sp, "stopped": bool(stop), "steps_enqueued": done,
                 "first_solution": sol.cpu().numpy() if cn[1] else None}
 
+    def solution_sink_set(self, sink=None):
+        """pcp_solution_sink_set: attach a solution sink — a SolutionSink or a PcpSolutionSink over device buffers — to this context, or
+        detach the one attached (None).  While one is attached the forests dfs_forest(formulas=True) and dfs_forest(small=True) append every
+        solution to it as an (lb, ub) row and hand a node back with error 6 (SINK_FULL) when it is full; every other forest entry refuses to
+        run (PCP_ERR_UNSUPPORTED).  The struct is copied; the buffers must outlive the attachment."""
+        st = sink.struct() if isinstance(sink, SolutionSink) else sink
+        self._check(self._L.pcp_solution_sink_set(self._h, None if st is None else C.byref(st)))
+
     def dfs_forest(self, root_lb, root_ub, stop_on_solution: bool = False, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
                    max_launches: int = 1 << 30, node_budget: int = 0, want_solution: bool = False, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
                    sp0=None, hints: bool = True, formulas: bool = False, small: bool = False, _call=None, brancher: str = "split", val: str = "middle",
-                   root_excl=None, path_capacity: int = 64, max_path: int = 1 << 20, _obj=None):
+                   root_excl=None, path_capacity: int = 64, max_path: int = 1 << 20, _obj=None, collect_solutions: bool = False, sink_capacity: int = 4096):
         """pcp_dfs_forest_device: the reference's search loop (interval mode, all-XNeqY models) on many subtrees at once, one workgroup per
         tree, each exactly a pcp_dfs_device instance.  root_lb / root_ub: [n_trees, n_vars] int32 (numpy or CUDA tensors): the roots, not yet
         propagated.  Launches of steps_per_launch nodes per tree are repeated until every stack is empty, a tree stopped (solution with
@@ -541,11 +599,19 @@ class Context:
         (``val="middle"``) or MinVal (``"min"``) in pcp_dfs_forest_device_small_enum.  ``root_excl``: a list of [k, 2] int32 arrays of (var, value),
         one per root — the exclusions the root arrives with (None: no root has any); they are written into each tree's path.  A tree's path
         holds ``path_capacity`` entries and is doubled, up to ``max_path``, when a tree reports error 5, as its stack is on error 1.  ``info``
-        also receives ``path_grown`` and ``path_capacity``.  The default ``brancher="split"`` issues exactly the calls it issued before."""
+        also receives ``path_grown`` and ``path_capacity``.  The default ``brancher="split"`` issues exactly the calls it issued before.
+        ``collect_solutions`` (``formulas=True`` or ``small=True``, either brancher, one rank; otherwise a ValueError): every solution is
+        returned, not only counted — a SolutionSink of ``sink_capacity`` rows is attached for the duration of the call, a tree that finds it
+        full hands its node back (error 6), the loop drains the sink and resumes that tree, as it grows a stack on error 1; the counters
+        are those of the same call without it.  The result then also holds ``solutions_lb`` / ``solutions_ub`` ([n, n_vars] int32: a solution
+        is a box of the interval store — every point of it satisfies the model; ``first_solutions`` keeps lower bounds only) and
+        ``solution_tree`` ([n]: the tree that wrote each row); ``info`` receives ``drains``, the drains a full sink forced.  With the default
+        False the calls issued and the keys returned are those of before."""
         import torch
         if small and formulas:
             raise ValueError("dfs_forest: small=True and formulas=True name two different forests (a store has formula units or it has none)")
         enum = _check_forest_brancher("dfs_forest", brancher, val, small, dist, root_excl)
+        _check_collect("dfs_forest", collect_solutions, sink_capacity, small, formulas, dist, _call is not None or _obj is not None)
         dev = torch.device("cuda", self.device)
         V = self.n_vars
         to_dev = lambda x: (torch.from_numpy(np.ascontiguousarray(x, np.int32)) if isinstance(x, np.ndarray) else x).to(dev).reshape(-1, V)
@@ -603,8 +669,19 @@ class Context:
             else:
                 self._check(entry(self._h, C.byref(box["st"]), T, int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit_per_tree), C.c_void_p(stream)))
 
-        loop = run_forest_loop(launch, fs, stop_on_solution=stop_on_solution, node_budget=node_budget,
-                               rebalance=rebalance and not node_limit_per_tree, max_launches=max_launches, dist=dist)
+        if collect_solutions:
+            # the sink is the context's for the duration of the loop only: drained behind the last launch, detached on every way out
+            sink = SolutionSink(sink_capacity, V, dev)
+            self.solution_sink_set(sink)
+            try:
+                loop = run_forest_loop(launch, fs, stop_on_solution=stop_on_solution, node_budget=node_budget,
+                                       rebalance=rebalance and not node_limit_per_tree, max_launches=max_launches, dist=dist, sink=sink)
+                sink.drain()
+            finally:
+                self.solution_sink_set(None)
+        else:
+            loop = run_forest_loop(launch, fs, stop_on_solution=stop_on_solution, node_budget=node_budget,
+                                   rebalance=rebalance and not node_limit_per_tree, max_launches=max_launches, dist=dist)
         launches, steals = loop["launches"], loop["steals"]
         if info is not None:
             info.update(loop)
@@ -613,14 +690,17 @@ class Context:
             if enum:
                 info["path_grown"], info["path_capacity"] = fs.path_grown, fs.path_capacity
         cn = counters.cpu().numpy()
-        return {"nodes": int(cn[:, 0].sum()), "solutions": int(cn[:, 1].sum()), "failed": int(cn[:, 2].sum()), "error": int(cn[:, 3].max()),
-                "open": int(sp.sum().item()), "launches": launches, "per_tree": cn, "trees": T, "steals": steals,
-                "first_solutions": sol.cpu().numpy() if want_solution else None}
+        out = {"nodes": int(cn[:, 0].sum()), "solutions": int(cn[:, 1].sum()), "failed": int(cn[:, 2].sum()), "error": int(cn[:, 3].max()),
+               "open": int(sp.sum().item()), "launches": launches, "per_tree": cn, "trees": T, "steals": steals,
+               "first_solutions": sol.cpu().numpy() if want_solution else None}
+        if collect_solutions:
+            out["solutions_lb"], out["solutions_ub"], out["solution_tree"] = sink.rows()
+        return out
 
     def dfs_forest_bnb(self, root_lb, root_ub, objective, best0=None, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
                        max_launches: int = 1 << 30, node_budget: int = 0, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
                        sp0=None, small: bool = False, brancher: str = "split", val: str = "middle", root_excl=None, path_capacity: int = 64,
-                       max_path: int = 1 << 20):
+                       max_path: int = 1 << 20, collect_solutions: bool = False):
         """pcp_dfs_forest_device_form_bnb: branch and bound (branch_and_bound.rs:64-84) in the forest over an Interval store with formula
         propagators — the loop, stacks, growth and refill of dfs_forest(formulas=True), every popped row entered with the forest's incumbent
         (one device word) folded into the objective's bounds.  ``objective`` = (var, "min" | "max").  ``best0``: a known bound to start from
@@ -629,9 +709,11 @@ class Context:
         "no solution yet" value).
         ``small``: the store is a small one of plain propagators (dfs_forest(small=True)): the same loop and result over
         pcp_dfs_forest_device_small_bnb.  ``brancher`` / ``val`` / ``root_excl`` / ``path_capacity`` / ``max_path``: as for dfs_forest
-        (Enumerate needs ``small=True``: pcp_dfs_forest_device_small_enum with the objective)."""
+        (Enumerate needs ``small=True``: pcp_dfs_forest_device_small_enum with the objective).  ``collect_solutions=True`` is a ValueError:
+        branch and bound keeps ``best_solution``, and its entries refuse a solution sink."""
         import torch
         _check_forest_brancher("dfs_forest_bnb", brancher, val, small, dist, root_excl)
+        _check_collect("dfs_forest_bnb", collect_solutions, 1, small, not small, None, bnb=True)
         var, mode = objective
         if mode not in OBJ_MODES:
             raise ValueError(f"objective mode must be 'min' or 'max', not {mode!r}")
@@ -849,6 +931,20 @@ def _check_forest_brancher(who, brancher, val, small, dist, root_excl=None) -> b
     if root_excl is not None and not enum:
         raise ValueError(f"{who}: root_excl needs brancher='enumerate'")
     return enum
+
+
+def _check_collect(who, collect_solutions, sink_capacity, small, formulas, dist, bnb=False):
+    """collect_solutions of an Interval forest: the formula-store and the small-store forest write into a solution sink, on one rank."""
+    if not collect_solutions:
+        return
+    if bnb:
+        raise ValueError(f"{who}: collect_solutions does not go with branch and bound (it keeps best_solution; the entries refuse a solution sink)")
+    if not small and not formulas:
+        raise ValueError(f"{who}: collect_solutions needs formulas=True or small=True (the all-XNeqY forest writes into no solution sink; small=True takes an all-XNeqY store within its limits)")
+    if dist is not None:
+        raise ValueError(f"{who}: collect_solutions does not run on several ranks (gathering the sinks is not built)")
+    if int(sink_capacity) < 1:
+        raise ValueError(f"{who}: sink_capacity must be at least 1, not {sink_capacity}")
 
 
 def full_active(n_nodes: int, n_units: int) -> np.ndarray:

@@ -359,6 +359,7 @@ class DeviceSearch:
         torch, ctx = self.torch, self.ctx
         from .engine import full_active, no_incumbent
         from .model import interval_bits
+        self.solutions_ub = []  # advance(keep_bounds=True): the upper bounds of stats.solutions, row for row
         if self.bits is not None:
             self.base = int(base)
             self.bits[0] = torch.from_numpy(interval_bits(np.asarray(lb0), np.asarray(ub0), self.set_words, self.base).view(np.int64)).to(self.dev)
@@ -380,13 +381,16 @@ class DeviceSearch:
             self._improved_seen = 0
         ctx.stats_reset(self._stream())
 
-    def advance(self, all_solutions: bool = True, node_limit: int = 0, max_rounds: int = 0, keep_solutions: int = 0, batch: int = 0, stop_at: int = 0) -> bool:
+    def advance(self, all_solutions: bool = True, node_limit: int = 0, max_rounds: int = 0, keep_solutions: int = 0, batch: int = 0, stop_at: int = 0,
+                keep_bounds: bool = False) -> bool:
         """Run rounds on the current stack until it is empty, a limit is hit, or (not all_solutions) a solution is
         found.  Returns True when the search is over (stack empty or solution found).
         ``node_limit`` is the search's StopNode limit (stop_node.rs:47-62): the node that reaches it is counted as a node and as nothing
         else.  ``stop_at`` only ends this call after that many nodes in total (a caller's chunk of a larger budget, e.g. one rank's share
         between two exchanges of parallel_search_device): every node's status counts.
-        With an objective, ``all_solutions`` is ignored: branch and bound runs to the end of the search."""
+        With an objective, ``all_solutions`` is ignored: branch and bound runs to the end of the search.
+        ``keep_bounds`` (int32 rows only): every solution kept in ``stats.solutions`` also leaves its upper bounds in ``self.solutions_ub``, row
+        for row (a True node of an interval store is a box; ``stats.solutions`` holds its lower corner, and the stats keep their fields)."""
         torch, ctx, st, kind = self.torch, self.ctx, self.stats, self.kind
         bnb = self.objective is not None
         all_solutions = all_solutions or bnb
@@ -442,6 +446,10 @@ class DeviceSearch:
                     rows = rows[rows != 0]  # (not counted: not kept either)
                 rows = rows[: keep_solutions - len(st.solutions)]
                 st.solutions += list(kind.unpacked(self.lb[lo:top][rows], stream).cpu().numpy())
+                if keep_bounds:
+                    if self.ub is None or self.set_words:
+                        raise ValueError("keep_bounds needs int32 (lb, ub) rows of an interval store")
+                    self.solutions_ub += list(self.ub[lo:top][rows].cpu().numpy())
             # pop the parents; the children, already in left-first order (branch_reverse), become the new top segment
             self.segs[-1][1] = length - n
             kind.pop(buf, length == n)

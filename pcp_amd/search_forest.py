@@ -254,7 +254,7 @@ class ForestStacks:
 
 
 def run_forest_loop(launch, fs: ForestStacks, stop_on_solution: bool = False, node_budget: int = 0, rebalance: bool = True,
-                    max_launches: int = 1 << 30, dist=None) -> dict:
+                    max_launches: int = 1 << 30, dist=None, sink=None) -> dict:
     """The host side of the interval forest (engine.Context.dfs_forest): ``launch()`` enqueues one launch of the forest kernel on the
     stacks ``fs``; between launches a tree whose stack is full gets more rows (ForestStacks.grow: memory follows the depth actually
     reached instead of being reserved for the worst case) and finished trees take work — from trees of this GPU, then (``dist``) from
@@ -264,11 +264,14 @@ def run_forest_loop(launch, fs: ForestStacks, stop_on_solution: bool = False, no
     as one with error 1 is, and a stolen bottom row takes its list along: the first row_base[d, 0] entries of the donor's path and the row's
     two words go to the receiver, the donor's row words shift down with its rows, and the donor's path stays — its other rows still use that
     prefix.  The result then also names ``first_steal``: the donor's bottom node before the first steal and the receiver's row 0 after it,
-    each as (lb, ub, entries [k, 2])."""
+    each as (lb, ub, entries [k, 2]).
+    ``sink`` (an engine.SolutionSink the caller attached to the context; one rank): a tree that reports error 6 found the sink full and kept
+    its node, propagated and uncounted; the sink is drained, the error and ``stop`` of those trees are cleared, and they resume as trees with
+    error 1 do — counters are what a sink that never fills leaves.  The result then also names ``drains``, the drains a full sink forced."""
     import time
     import torch
     T = int(fs.sp.shape[0])
-    launches = steals = fatal = 0
+    launches = steals = fatal = drains = 0
     enum = fs.path is not None
     first_steal = None
 
@@ -288,7 +291,12 @@ def run_forest_loop(launch, fs: ForestStacks, stop_on_solution: bool = False, no
         err = counters[:, 3]
         full = err == 1  # stack full: the node stayed on top of its stack, uncounted (pcp_hip.h, pcp_dfs_device)
         pfull = (err == 5) if enum else None  # exclusion path full: the same contract
-        if enum:
+        sfull = (err == 6) if sink is not None else None  # solution sink full: the same contract
+        if sink is not None:
+            handed = full | sfull | (pfull if enum else torch.zeros_like(full))
+            summary = torch.stack([live.sum(), counters[:, 0].sum(), counters[:, 1].sum(), full.sum(), ((err != 0) & ~handed).sum() + fatal,
+                                   pfull.sum() if enum else full.sum() * 0, sfull.sum()]).to(torch.int64)
+        elif enum:
             summary = torch.stack([live.sum(), counters[:, 0].sum(), counters[:, 1].sum(), full.sum(), ((err != 0) & ~full & ~pfull).sum() + fatal, pfull.sum()]).to(torch.int64)
         else:
             summary = torch.stack([live.sum(), counters[:, 0].sum(), counters[:, 1].sum(), full.sum(), ((err != 0) & ~full).sum() + fatal]).to(torch.int64)
@@ -310,7 +318,7 @@ def run_forest_loop(launch, fs: ForestStacks, stop_on_solution: bool = False, no
                 break  # the ceiling is reached: the trees keep error 1 (the caller reports it)
             else:
                 fatal = 1  # (several ranks leave the loop TOGETHER: the flag travels with the next launch's summary)
-        elif enum and mine[5]:
+        elif (enum and mine[5]) or (sink is not None and mine[6]):
             pass
         elif vals[0] == 0 and vals[3] == 0:
             break
@@ -318,6 +326,12 @@ def run_forest_loop(launch, fs: ForestStacks, stop_on_solution: bool = False, no
             if not fs.grow_path():
                 break  # the ceiling is reached: the trees keep error 5
             idx = torch.nonzero(pfull).flatten()
+            fs.counters[idx, 3] = 0
+            fs.stop[idx] = 0
+        if sink is not None and mine[6]:
+            sink.drain()
+            drains += 1
+            idx = torch.nonzero(sfull).flatten()
             fs.counters[idx, 3] = 0
             fs.stop[idx] = 0
         if not rebalance:
@@ -360,14 +374,18 @@ def run_forest_loop(launch, fs: ForestStacks, stop_on_solution: bool = False, no
            "grown": fs.grown, "capacity": fs.capacity}
     if enum:
         out["first_steal"] = first_steal
+    if sink is not None:
+        out["drains"] = drains
     return out
 
 
-def seed_roots_interval(ctx, lb0, ub0, want: int, objective=None, brancher: str = "split", val: str = "middle"):
+def seed_roots_interval(ctx, lb0, ub0, want: int, objective=None, brancher: str = "split", val: str = "middle", collect_solutions: bool = False):
     """Interval mode: breadth-first expansion of the root to at least `want` open nodes.  ``objective``: the expansion runs under branch and
     bound (DeviceSearch(objective=)), its stats carry the incumbent (``best``, ``best_solution``).  Returns (lb rows, ub rows, stats).
     ``brancher="enumerate"``: the expansion runs under Enumerate on ``val`` (DeviceSearch(brancher="enumerate", val=, objective=)) and a
-    fourth value is returned: each root's exclusion list, a [k, 2] int32 array of (var, value)."""
+    fourth value is returned: each root's exclusion list, a [k, 2] int32 array of (var, value).
+    ``collect_solutions``: one more value is returned behind the others, the solutions the expansion found as boxes: (lb rows, ub rows),
+    two [n, V] int32 numpy arrays (the stats' ``solutions`` hold the lower bounds only)."""
     from .search_device import DeviceSearch
     if brancher == "split":
         ds = DeviceSearch(ctx, batch=max(want, 1), capacity=4 * max(want, 1) + 64, implicit=True, objective=objective)
@@ -375,19 +393,27 @@ def seed_roots_interval(ctx, lb0, ub0, want: int, objective=None, brancher: str 
         ds = DeviceSearch(ctx, batch=max(want, 1), capacity=4 * max(want, 1) + 64, implicit=True, objective=objective, brancher=brancher, val=val)
     ds.reset(lb0, ub0)
     while 0 < ds.size < want:
-        if ds.advance(all_solutions=True, max_rounds=1, keep_solutions=0):
+        if collect_solutions:
+            if ds.advance(all_solutions=True, max_rounds=1, keep_solutions=1 << 62, keep_bounds=True):
+                break
+        elif ds.advance(all_solutions=True, max_rounds=1, keep_solutions=0):
             break
     ds.compact()
     k = ds.size
+    boxes = ()
+    if collect_solutions:
+        V = int(ds.lb.shape[1])
+        rows = lambda r: np.stack(r).astype(np.int32).reshape(-1, V) if r else np.zeros((0, V), np.int32)
+        boxes = ((rows(ds.stats.solutions), rows(ds.solutions_ub)),)
     if brancher == "split":
-        return ds.lb[:k].clone(), ds.ub[:k].clone(), ds.stats
+        return (ds.lb[:k].clone(), ds.ub[:k].clone(), ds.stats) + boxes
     lists = []
     if k:  # the one segment's offsets (relative to its first entry) and entries
         o, e0, _, _ = ds.esegs[-1]
         off = ds.eoff[o:o + k + 1].cpu().numpy().astype(np.int64)
         ex = ds.ex[e0:e0 + int(off[-1])].cpu().numpy().reshape(-1, 2)
         lists = [np.ascontiguousarray(ex[off[i]:off[i + 1]], np.int32) for i in range(k)]
-    return ds.lb[:k].clone(), ds.ub[:k].clone(), ds.stats, lists
+    return (ds.lb[:k].clone(), ds.ub[:k].clone(), ds.stats, lists) + boxes
 
 
 STACK_BYTES_CAP = 64 << 30  # default ceiling of the forest's stack rows per GPU (both bound arrays together); rows are allocated as trees get deep
@@ -395,7 +421,7 @@ STACK_BYTES_CAP = 64 << 30  # default ceiling of the forest's stack rows per GPU
 
 def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_per_launch: int = 512, rank: int = 0, world: int = 1, capacity: int = 0,
                   dist=None, info: dict | None = None, stack_bytes: int = STACK_BYTES_CAP, formulas: bool = False, small: bool = False, brancher: str = "split",
-                  val: str = "middle") -> dict:
+                  val: str = "middle", collect_solutions: bool = False, sink_capacity: int = 4096) -> dict:
     """Interval mode, all-XNeqY models: expansion + one in-kernel DFS per open node (pcp_dfs_forest_device).  formulas: the store holds
     formula propagators (what Cumulative.join builds): the trees run in pcp_dfs_forest_device_form, one per wavefront.  small: a small store of
     plain propagators of any kind (the Golomb network): pcp_dfs_forest_device_small, one tree per wavefront; with formulas=True a ValueError.  The node limit is checked
@@ -406,21 +432,29 @@ def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_
     that needs more reports error 1.
     brancher / val: the distributor of the expansion AND of the trees ("enumerate": Enumerate on MiddleVal or MinVal; small=True only, one
     rank — with ``dist``, ``world`` > 1, ``formulas=True`` or the all-XNeqY forest a ValueError): the roots arrive with the exclusion lists the
-    expansion gave them, so that the expansion and the trees together are one Enumerate tree."""
+    expansion gave them, so that the expansion and the trees together are one Enumerate tree.
+    collect_solutions / sink_capacity (formulas=True or small=True, one rank; otherwise a ValueError): as for Context.dfs_forest — the result
+    also holds ``solutions_lb`` / ``solutions_ub`` ([n, n_vars] int32, every solution as a box) and ``solution_tree`` ([n]; -1: a solution the
+    expansion found, they come first), and ``seeded_solutions`` counts those."""
     if small and formulas:
         raise ValueError("forest_search: small=True and formulas=True name two different forests (a store has formula units or it has none)")
-    from .engine import _check_forest_brancher
+    from .engine import _check_collect, _check_forest_brancher
     enum = _check_forest_brancher("forest_search", brancher, val, small, dist)
     if enum and world > 1:
         raise ValueError("forest_search: brancher='enumerate' does not run on several ranks (moving exclusion lists between ranks is not built)")
+    _check_collect("forest_search", collect_solutions, sink_capacity, small, formulas, dist if dist is not None else (True if world > 1 else None))
     lists = None
     if enum:
-        rl, ru, st, lists = seed_roots_interval(ctx, lb0, ub0, n_trees, brancher=brancher, val=val)
+        rl, ru, st, lists, *boxes = seed_roots_interval(ctx, lb0, ub0, n_trees, brancher=brancher, val=val, **(dict(collect_solutions=True) if collect_solutions else {}))
     else:
-        rl, ru, st = seed_roots_interval(ctx, lb0, ub0, n_trees * world)
+        rl, ru, st, *boxes = seed_roots_interval(ctx, lb0, ub0, n_trees * world, **(dict(collect_solutions=True) if collect_solutions else {}))
     ml, mu = rl[rank::world].contiguous(), ru[rank::world].contiguous()
     out = {"seeded_nodes": st.num_nodes if rank == 0 else 0, "trees": int(ml.shape[0]), "launches": 0,
            "nodes": st.num_nodes if rank == 0 else 0, "solutions": st.num_solution if rank == 0 else 0, "failed": st.num_failed_node if rank == 0 else 0, "error": 0}
+    if collect_solutions:
+        out["solutions_lb"], out["solutions_ub"] = boxes[0]
+        out["solution_tree"] = np.full(len(boxes[0][0]), -1, np.int32)
+        out["seeded_solutions"] = len(boxes[0][0])
     budget = share_of_budget(node_limit, st.num_nodes, rank, world) if node_limit else 0
     multi = dist is not None and world > 1
     sp0 = None
@@ -453,14 +487,19 @@ def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_
         capacity = ceiling if (per_tree and not multi and ceiling * row_bytes <= upfront) else min(128, ceiling)
     r = ctx.dfs_forest(ml, mu, node_limit_per_tree=0 if multi else per_tree, steps_per_launch=steps_per_launch, capacity=capacity, max_capacity=max(ceiling, capacity),
                        node_budget=max(node_limit - st.num_nodes, 1) if multi else budget, dist=dist if multi else None, info=info, sp0=sp0, formulas=formulas, small=small,
-                       **(dict(brancher=brancher, val=val, root_excl=lists) if enum else {}))
+                       **(dict(brancher=brancher, val=val, root_excl=lists) if enum else {}),
+                       **(dict(collect_solutions=True, sink_capacity=sink_capacity) if collect_solutions else {}))
     out["nodes"] += r["nodes"]; out["solutions"] += r["solutions"]; out["failed"] += r["failed"]
     out["error"] = r["error"]; out["launches"] = r["launches"]
+    if collect_solutions:
+        for k in ("solutions_lb", "solutions_ub", "solution_tree"):
+            out[k] = np.concatenate([out[k], r[k]])
     return out
 
 
 def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: int = 512, best0=None, capacity: int = 128, max_capacity: int = 1 << 16,
-               info: dict | None = None, formulas: bool = True, small: bool = False, brancher: str = "split", val: str = "middle") -> dict:
+               info: dict | None = None, formulas: bool = True, small: bool = False, brancher: str = "split", val: str = "middle",
+               collect_solutions: bool = False) -> dict:
     """Branch and bound over an Interval store with formula propagators (branch_and_bound.rs:64-84 around the loop of forest_search):
     minimize / maximize ``objective`` = (var, "min" | "max") below (lb0, ub0).  The root is expanded breadth-first under branch and bound
     (seed_roots_interval with DeviceSearch(objective=)) to at least ``n_trees`` open nodes; each becomes a tree of
@@ -469,7 +508,10 @@ def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: i
     expansion's, ``seeded_nodes`` names them); ``best`` is None when neither the expansion nor a tree found a solution beating ``best0``.
     ``small``: a small store of plain propagators instead (Context.dfs_forest_bnb(small=True) — model.golomb_ruler); it wins over
     ``formulas``, whose default is True.  brancher / val: as for forest_search — Enumerate needs ``small=True``; the expansion then
-    runs under DeviceSearch(brancher="enumerate", val=, objective=) and the roots keep their exclusion lists."""
+    runs under DeviceSearch(brancher="enumerate", val=, objective=) and the roots keep their exclusion lists.
+    collect_solutions=True is a ValueError: branch and bound returns ``best_solution``."""
+    if collect_solutions:
+        raise ValueError("forest_bnb: collect_solutions does not go with branch and bound (it keeps best_solution; the entries refuse a solution sink)")
     if not formulas and not small:
         raise ValueError("forest_bnb searches stores with formula propagators (all-XNeqY stores have no objective to bound)")
     from .engine import _check_forest_brancher
