@@ -1207,47 +1207,74 @@ int32_t pcp_dfs_forest_device(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_tr
   return PCP_OK;
 }
 
-// The same loop over an Interval store with formula propagators: one tree per wavefront, the unit step of formfix_kernel inside the loop
-// (pcp_formdfs.hip); obj != nullptr: under branch and bound.  The stacks are those of pcp_dfs_forest_device.
-static int32_t dfs_forest_form(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_objective* obj, uint32_t n_steps, uint32_t stop_on_solution,
-                               uint64_t node_limit, void* hip_stream) {
-  const std::string who = obj ? "pcp_dfs_forest_device_form_bnb" : "pcp_dfs_forest_device_form";
+// What a launch of either row-stack search forest of Interval stores (row_dfs, pcp_rowdfs.hpp) checks, `who` being the entry point and
+// `sets` the entry that takes the same store in set mode: the sink, the mode, the stacks, the exclusion path (ex != nullptr: under
+// Enumerate), the objective (obj != nullptr: under branch and bound); then the model is finalised.
+static int32_t forest_row_check(pcp_ctx* c, const std::string& who, const char* sets, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex,
+                                const pcp_forest_objective* obj) {
   if (obj && c->sink.lb) return refuse_sink(c, who, "branch and bound keeps tree_row instead");
-  if (c->set_words) return fail(c, PCP_ERR_ARG, who + " runs interval-mode models (sets: pcp_dfs_forest_device_setform)");
+  if (c->set_words) return fail(c, PCP_ERR_ARG, who + " runs interval-mode models (sets: " + sets + ")");
   if (!n_trees || !st->lb || !st->ub || !st->sp || !st->stop || !st->status || !st->counters || st->capacity < 2)
     return fail(c, PCP_ERR_ARG, who + ": null buffer / no tree / capacity < 2");
+  if (ex) {
+    if (ex->val > PCP_VAL_MIN) return fail(c, PCP_ERR_ARG, who + ": val must be PCP_VAL_MIDDLE or PCP_VAL_MIN");
+    if (!ex->row_base || !ex->row_excl || (ex->path_capacity && !ex->path)) return fail(c, PCP_ERR_ARG, who + ": null row_base / row_excl / path");
+  }
   if (obj) {
     if (obj->var >= c->n_vars) return fail(c, PCP_ERR_ARG, who + ": objective variable out of range");
     if (obj->mode > PCP_MAXIMIZE) return fail(c, PCP_ERR_ARG, who + ": mode must be PCP_MINIMIZE or PCP_MAXIMIZE");
     if (!obj->best || !obj->tree_best) return fail(c, PCP_ERR_ARG, who + ": best and tree_best are required");
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  { const int32_t rcf = finalize_model(c); if (rcf) return rcf; }
+  return finalize_model(c);
+}
+
+// Up to four trees per 256-thread workgroup; a store whose four slices (lds_of(4)) exceed half a CU's LDS runs with two or one.
+// lds_bytes = 0: not even one tree's node fits.
+static LaunchPlan forest_row_plan(const pcp_ctx* c, uint32_t n_trees, const std::function<size_t(uint32_t)>& lds_of) {
+  uint32_t waves = 4;
+  while (waves > 1 && (!lds_of(waves) || lds_of(waves) > c->lds_max / 2)) waves /= 2;
+  const size_t lds = lds_of(waves);
+  return LaunchPlan{(n_trees + waves - 1) / waves, 64 * waves, lds <= c->lds_max ? lds : 0};
+}
+
+// The model fields row_dfs and both nodes read, and RowDfsArgs: the stacks, the objective, the exclusion path, the context's sink.
+static void fill_row_args(ModelDev& m, RowDfsArgs& d, const pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_objective* obj,
+                          const pcp_forest_excl* ex, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit) {
+  m.recs = c->d_recs; m.const_val = c->d_const; m.n_recs = (uint32_t)c->props.size(); m.n_vars = c->n_vars; m.n_slots = c->n_slots;
+  m.sums = SumTab{c->d_sum_off, c->d_sum_mem, c->n_vars, c->n_sum_slots, c->d_mul_off};
+  d.n_trees = n_trees; d.capacity = st->capacity; d.n_steps = n_steps; d.stop_on_solution = obj ? 0u : stop_on_solution; d.node_limit = node_limit;
+  d.lb = st->lb; d.ub = st->ub; d.sp = st->sp; d.stop = st->stop; d.counters = reinterpret_cast<unsigned long long*>(st->counters);
+  d.first_solution = obj ? nullptr : st->first_solution;
+  d.violation = c->d_retry + 1; d.stats = c->d_stats;
+  if (obj) { d.obj_var = obj->var; d.obj_mode = obj->mode; d.obj_best = obj->best; d.tree_best = obj->tree_best; d.tree_row = obj->tree_row; }
+  if (ex) { d.path = ex->path; d.row_base = ex->row_base; d.row_excl = ex->row_excl; d.path_capacity = ex->path_capacity; d.val = ex->val; }
+  d.sink = c->sink;
+}
+
+// One launch of such a forest on plan.path `path` (3: formula units, 4: a small store); n_steps = 0: PCP_OK, nothing is launched.
+static int32_t forest_row_launch(pcp_ctx* c, const LaunchPlan& plan, uint32_t path, uint32_t n_steps, void* hip_stream, const std::function<hipError_t(hipStream_t)>& launch) {
+  if (!n_steps) return PCP_OK;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  c->last_plan = pcp_plan{plan.block / 64, 1u, 0u, 0u, 0u, 0u, 1u, 0u, plan.grid, plan.block, (uint32_t)plan.lds_bytes, 0u, path};
+  return forest_launch(c, stream, [&] { return launch(stream); });
+}
+
+// The loop over an Interval store with formula propagators: one tree per wavefront, the unit step of formfix_kernel inside the loop
+// (pcp_formdfs.hip); obj != nullptr: under branch and bound.  The stacks are those of pcp_dfs_forest_device.
+static int32_t dfs_forest_form(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_objective* obj, uint32_t n_steps, uint32_t stop_on_solution,
+                               uint64_t node_limit, void* hip_stream) {
+  const std::string who = obj ? "pcp_dfs_forest_device_form_bnb" : "pcp_dfs_forest_device_form";
+  { const int32_t rc = forest_row_check(c, who, "pcp_dfs_forest_device_setform", st, n_trees, nullptr, obj); if (rc) return rc; }
   if (!c->has_formulas)
     return fail(c, PCP_ERR_UNSUPPORTED, who + " searches stores with formula propagators (Boolean / pcp_model_push_formula): an all-XNeqY store is searched by pcp_dfs_forest_device, any other by pcp_dfs_device, one tree");
-  // up to four trees per 256-thread workgroup; a store whose four slices exceed half a CU's LDS runs with two or one
-  const uint32_t S = c->n_slots;
-  uint32_t waves = 4;
-  while (waves > 1 && (!lds_bytes_formdfs(S, c->n_units, waves) || lds_bytes_formdfs(S, c->n_units, waves) > c->lds_max / 2)) waves /= 2;
-  const size_t lds = lds_bytes_formdfs(S, c->n_units, waves);
-  if (!lds || lds > c->lds_max) return fail(c, PCP_ERR_UNSUPPORTED, who + ": a tree's node must fit one CU's LDS (8 bytes per variable and interned constant, and the unit mask)");
-  if (!n_steps) return PCP_OK;
+  const LaunchPlan plan = forest_row_plan(c, n_trees, [&](uint32_t waves) { return lds_bytes_formdfs(c->n_slots, c->n_units, waves); });
+  if (!plan.lds_bytes) return fail(c, PCP_ERR_UNSUPPORTED, who + ": a tree's node must fit one CU's LDS (8 bytes per variable and interned constant, and the unit mask)");
   FormDfsArgs a;
   memset(&a, 0, sizeof(a));
-  a.m.recs = c->d_recs; a.m.const_val = c->d_const; a.m.n_recs = (uint32_t)c->props.size(); a.m.n_vars = c->n_vars; a.m.n_slots = S;
-  a.m.sums = SumTab{c->d_sum_off, c->d_sum_mem, c->n_vars, c->n_sum_slots, c->d_mul_off};
+  fill_row_args(a.m, a.d, c, st, n_trees, obj, nullptr, n_steps, stop_on_solution, node_limit);
   a.nodes = c->d_fnodes; a.unit_root = c->d_unit_root; a.n_units = c->n_units;
-  a.n_trees = n_trees; a.capacity = st->capacity; a.n_steps = n_steps; a.stop_on_solution = obj ? 0u : stop_on_solution; a.node_limit = node_limit;
-  a.lb = st->lb; a.ub = st->ub; a.sp = st->sp; a.stop = st->stop; a.counters = reinterpret_cast<unsigned long long*>(st->counters);
-  a.first_solution = obj ? nullptr : st->first_solution;
-  a.violation = c->d_retry + 1; a.stats = c->d_stats;
-  if (obj) { a.obj_var = obj->var; a.obj_mode = obj->mode; a.obj_best = obj->best; a.tree_best = obj->tree_best; a.tree_row = obj->tree_row; }
-  a.sink = c->sink;
-  LaunchPlan plan;
-  plan.block = 64 * waves; plan.lds_bytes = lds; plan.grid = (n_trees + waves - 1) / waves;
-  c->last_plan = pcp_plan{waves, 1u, 0u, 0u, 0u, 0u, 1u, 0u, plan.grid, plan.block, (uint32_t)lds, 0u, 3u};
-  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
-  return forest_launch(c, stream, [&] { return launch_formdfs(a, obj != nullptr, plan, stream); });
+  return forest_row_launch(c, plan, 3u, n_steps, hip_stream, [&](hipStream_t stream) { return launch_formdfs(a, obj != nullptr, plan, stream); });
 }
 
 int32_t pcp_dfs_forest_device_form(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
@@ -1268,50 +1295,20 @@ int32_t pcp_dfs_forest_device_form_bnb(pcp_ctx* c, const pcp_dfs_state* st, uint
 static int32_t dfs_forest_small(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex, const pcp_forest_objective* obj, uint32_t n_steps,
                                 uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
   const std::string who = ex ? "pcp_dfs_forest_device_small_enum" : obj ? "pcp_dfs_forest_device_small_bnb" : "pcp_dfs_forest_device_small";
-  if (obj && c->sink.lb) return refuse_sink(c, who, "branch and bound keeps tree_row instead");
-  if (c->set_words) return fail(c, PCP_ERR_ARG, who + " runs interval-mode models (sets: pcp_dfs_forest_device_set)");
-  if (!n_trees || !st->lb || !st->ub || !st->sp || !st->stop || !st->status || !st->counters || st->capacity < 2)
-    return fail(c, PCP_ERR_ARG, who + ": null buffer / no tree / capacity < 2");
-  if (ex) {
-    if (ex->val > PCP_VAL_MIN) return fail(c, PCP_ERR_ARG, who + ": val must be PCP_VAL_MIDDLE or PCP_VAL_MIN");
-    if (!ex->row_base || !ex->row_excl || (ex->path_capacity && !ex->path)) return fail(c, PCP_ERR_ARG, who + ": null row_base / row_excl / path");
-  }
-  if (obj) {
-    if (obj->var >= c->n_vars) return fail(c, PCP_ERR_ARG, who + ": objective variable out of range");
-    if (obj->mode > PCP_MAXIMIZE) return fail(c, PCP_ERR_ARG, who + ": mode must be PCP_MINIMIZE or PCP_MAXIMIZE");
-    if (!obj->best || !obj->tree_best) return fail(c, PCP_ERR_ARG, who + ": best and tree_best are required");
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  { const int32_t rcf = finalize_model(c); if (rcf) return rcf; }
+  { const int32_t rc = forest_row_check(c, who, "pcp_dfs_forest_device_set", st, n_trees, ex, obj); if (rc) return rc; }
   if (c->has_formulas)
     return fail(c, PCP_ERR_UNSUPPORTED, who + " searches stores of plain propagators: a store with formula propagators (Boolean / pcp_model_push_formula) is searched by pcp_dfs_forest_device_form");
   const uint32_t S = c->n_slots, P = (uint32_t)c->props.size();
   const char* const too_large = " searches small stores — at most 128 variables (incl. interned constants) and 2048 elementary filters, a workgroup's records and nodes in one CU's LDS: a larger store is searched by pcp_dfs_device, one tree";
   if (S > 128u || P > 2048u) return fail(c, PCP_ERR_UNSUPPORTED, who + too_large);
-  // up to four trees per 256-thread workgroup; a store whose records and four slices exceed half a CU's LDS runs with two or one
-  uint32_t waves = 4;
-  while (waves > 1 && (!lds_bytes_smalldfs(S, c->n_units, P, waves) || lds_bytes_smalldfs(S, c->n_units, P, waves) > c->lds_max / 2)) waves /= 2;
-  const size_t lds = lds_bytes_smalldfs(S, c->n_units, P, waves);
-  if (!lds || lds > c->lds_max) return fail(c, PCP_ERR_UNSUPPORTED, who + too_large);
-  if (!n_steps) return PCP_OK;
+  const LaunchPlan plan = forest_row_plan(c, n_trees, [&](uint32_t waves) { return lds_bytes_smalldfs(S, c->n_units, P, waves); });
+  if (!plan.lds_bytes) return fail(c, PCP_ERR_UNSUPPORTED, who + too_large);
   SmallDfsArgs a;
   memset(&a, 0, sizeof(a));
-  a.m.recs = c->d_recs; a.m.const_val = c->d_const; a.m.n_recs = P; a.m.n_vars = c->n_vars; a.m.n_slots = S; a.m.has_ternary = c->has_ternary;
-  a.m.sums = SumTab{c->d_sum_off, c->d_sum_mem, c->n_vars, c->n_sum_slots, c->d_mul_off};
+  fill_row_args(a.m, a.d, c, st, n_trees, obj, ex, n_steps, stop_on_solution, node_limit);
   a.rec_unit = c->has_groups ? c->d_rec_unit : nullptr; a.n_units = c->n_units;
   if (c->n_alldiff && c->opt_small_alldiff) { a.ad_tab = c->d_ad_tab; a.ad_vars = c->d_ad_vars; }
-  a.n_trees = n_trees; a.capacity = st->capacity; a.n_steps = n_steps; a.stop_on_solution = obj ? 0u : stop_on_solution; a.node_limit = node_limit;
-  a.lb = st->lb; a.ub = st->ub; a.sp = st->sp; a.stop = st->stop; a.counters = reinterpret_cast<unsigned long long*>(st->counters);
-  a.first_solution = obj ? nullptr : st->first_solution;
-  a.violation = c->d_retry + 1; a.stats = c->d_stats;
-  if (obj) { a.obj_var = obj->var; a.obj_mode = obj->mode; a.obj_best = obj->best; a.tree_best = obj->tree_best; a.tree_row = obj->tree_row; }
-  if (ex) { a.path = ex->path; a.row_base = ex->row_base; a.row_excl = ex->row_excl; a.path_capacity = ex->path_capacity; a.val = ex->val; }
-  a.sink = c->sink;
-  LaunchPlan plan;
-  plan.block = 64 * waves; plan.lds_bytes = lds; plan.grid = (n_trees + waves - 1) / waves;
-  c->last_plan = pcp_plan{waves, 1u, 0u, 0u, 0u, 0u, 1u, 0u, plan.grid, plan.block, (uint32_t)lds, 0u, 4u};
-  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
-  return forest_launch(c, stream, [&] { return launch_smalldfs(a, obj != nullptr, plan, stream); });
+  return forest_row_launch(c, plan, 4u, n_steps, hip_stream, [&](hipStream_t stream) { return launch_smalldfs(a, obj != nullptr, plan, stream); });
 }
 
 int32_t pcp_dfs_forest_device_small(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,

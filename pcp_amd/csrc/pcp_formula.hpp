@@ -1,6 +1,6 @@
 // pcp_formula.hpp — what the two kernels over formula stores on Interval<i32> domains share: the LDS slice of one node (form_carve),
 // is_subsumed() / propagate() of an elementary leaf, and the step of one formula unit.  formfix_kernel (pcp_formula.hip: the fixpoint of a
-// batch of nodes) and formdfs_kernel (pcp_formdfs.hip: the search loop, one tree per wavefront) run them on LdsDom, the node's (-lb, ub)
+// batch of nodes) and formdfs_kernel (pcp_formdfs.hip: FormulaNode::propagate inside row_dfs, pcp_rowdfs.hpp — the search loop, one tree per wavefront) run them on LdsDom, the node's (-lb, ub)
 // cells in LDS.  The interval twin of pcp_setform.hpp.  Device code only; everything lives in an unnamed namespace.
 #pragma once
 #include "pcp_device.hpp"

@@ -131,13 +131,10 @@ struct SinkDev {
 };
 constexpr uint32_t kDfsSinkFull = 6;  // counters[t][3]: the sink was full — the node stays on the stack, propagated and uncounted
 
-// The search loop over such a store on the device: one tree per WAVEFRONT on its own stack of (lb, ub) rows, the node being run in that
-// wavefront's LDS slice (pcp_formdfs.hip).  The stacks are a pcp_dfs_state laid out as for pcp_dfs_forest_device.
-struct FormDfsArgs {
-  ModelDev m;                    // needs recs, const_val, sums, n_vars, n_slots
-  const FNode* nodes;
-  const uint32_t* unit_root;
-  uint32_t n_units;
+// What the two row-stack search forests of Interval stores share (row_dfs, pcp_rowdfs.hpp): one tree per WAVEFRONT on its own stack of
+// (lb, ub) rows, a pcp_dfs_state laid out as for pcp_dfs_forest_device.  Embedded as `d` in FormDfsArgs and SmallDfsArgs, as SetDfsArgs is in
+// SetFormDfsArgs.
+struct RowDfsArgs {
   uint32_t n_trees, capacity, n_steps, stop_on_solution;
   unsigned long long node_limit; // per tree
   int32_t* lb;                   // [n_trees][capacity][n_vars]
@@ -148,15 +145,29 @@ struct FormDfsArgs {
   int32_t* first_solution;       // [n_trees][n_vars] or null
   uint32_t* violation;
   pcp_stats* stats;
-  // branch and bound only (formdfs_kernel<true>, pcp_dfs_forest_device_form_bnb)
+  // branch and bound only (row_dfs<true, ..>: the _bnb entries, pcp_dfs_forest_device_small_enum with an objective)
   uint32_t obj_var, obj_mode;    // the objective variable, PCP_MINIMIZE / PCP_MAXIMIZE
   int32_t* obj_best;             // device int32[1]: the forest's incumbent
   int32_t* tree_best;            // [n_trees]: the value of each tree's last solution
   int32_t* tree_row;             // [n_trees][n_vars] or null: its lower bounds
-  SinkDev sink;                  // the context's solution sink (formdfs_kernel<false, true>); sink.lb == null: none
+  // Enumerate only (row_dfs<.., true, ..>, pcp_dfs_forest_device_small_enum; row_base == null: BinarySplit)
+  pcp_excl* path;                // [n_trees][path_capacity]: the exclusions along each tree's current path
+  uint32_t* row_base;            // [n_trees][capacity]: the path entries a stack row inherits
+  pcp_excl* row_excl;            // [n_trees][capacity]: the entry appended when the row is popped (var 0xFFFFFFFF: none)
+  uint32_t path_capacity, val;   // PCP_VAL_MIDDLE / PCP_VAL_MIN
+  SinkDev sink;                  // the context's solution sink (row_dfs<false, .., true>); sink.lb == null: none
+};
+
+// The search loop over such a store on the device: the node being run in its tree's LDS slice (pcp_formdfs.hip).
+struct FormDfsArgs {
+  ModelDev m;                    // needs recs, const_val, sums, n_vars, n_slots
+  const FNode* nodes;
+  const uint32_t* unit_root;
+  uint32_t n_units;
+  RowDfsArgs d;
 };
 size_t lds_bytes_formdfs(uint32_t n_slots, uint32_t n_units, uint32_t waves);  // one slice per tree; 0 = beyond a CU's LDS
-// (a.sink.lb != null: the instantiation that appends every solution to the sink; never together with bnb)
+// (a.d.sink.lb != null: the instantiation that appends every solution to the sink; never together with bnb)
 hipError_t launch_formdfs(const FormDfsArgs& a, bool bnb, const LaunchPlan& p, hipStream_t stream);
 
 // The same stores over IntervalSet<i32> domains (set mode): the trees as above, the node's sets as bit words in LDS (pcp_setform.hip).
@@ -232,39 +243,18 @@ struct SmallExclArgs {
 };
 hipError_t launch_smallexcl(const SmallExclArgs& a, const LaunchPlan& p, hipStream_t stream);
 
-// The search loop over such a store on the device: one tree per WAVEFRONT on its own stack of (lb, ub) rows, the node being run in that
-// wavefront's LDS slice, the records in the copy its workgroup shares (pcp_smalldfs.hip).  The stacks are a pcp_dfs_state laid out as for
-// pcp_dfs_forest_device.
+// The search loop over such a store on the device (RowDfsArgs `d`): the node being run in its tree's LDS slice, the records in the copy its
+// workgroup shares (pcp_smalldfs.hip).
 struct SmallDfsArgs {
   ModelDev m;                    // needs recs, const_val, sums, n_recs, n_vars, n_slots
   const uint32_t* rec_unit;      // [n_recs] unit of each record, or null: every record is its own unit
   uint32_t n_units;
   const uint32_t* ad_tab;        // all-different units, or null (SmallArgs)
   const uint32_t* ad_vars;
-  uint32_t n_trees, capacity, n_steps, stop_on_solution;
-  unsigned long long node_limit; // per tree
-  int32_t* lb;                   // [n_trees][capacity][n_vars]
-  int32_t* ub;
-  uint32_t* sp;                  // [n_trees]
-  uint32_t* stop;                // [n_trees]
-  unsigned long long* counters;  // [n_trees][5]: nodes, solutions, failed nodes, error, first-solution flag
-  int32_t* first_solution;       // [n_trees][n_vars] or null
-  uint32_t* violation;
-  pcp_stats* stats;
-  // branch and bound only (smalldfs_kernel<true>, pcp_dfs_forest_device_small_bnb)
-  uint32_t obj_var, obj_mode;    // the objective variable, PCP_MINIMIZE / PCP_MAXIMIZE
-  int32_t* obj_best;             // device int32[1]: the forest's incumbent
-  int32_t* tree_best;            // [n_trees]: the value of each tree's last solution
-  int32_t* tree_row;             // [n_trees][n_vars] or null: its lower bounds
-  // Enumerate only (smalldfs_kernel<.., true>, pcp_dfs_forest_device_small_enum; row_base == null: BinarySplit)
-  pcp_excl* path;                // [n_trees][path_capacity]: the exclusions along each tree's current path
-  uint32_t* row_base;            // [n_trees][capacity]: the path entries a stack row inherits
-  pcp_excl* row_excl;            // [n_trees][capacity]: the entry appended when the row is popped (var 0xFFFFFFFF: none)
-  uint32_t path_capacity, val;   // PCP_VAL_MIDDLE / PCP_VAL_MIN
-  SinkDev sink;                  // the context's solution sink (smalldfs_kernel<false, .., true>); sink.lb == null: none
+  RowDfsArgs d;
 };
 size_t lds_bytes_smalldfs(uint32_t n_slots, uint32_t n_units, uint32_t n_recs, uint32_t waves);  // the records' copy + one slice per tree; 0 = beyond a CU's LDS
-// (a.sink.lb != null: the instantiations that append every solution to the sink; never together with bnb)
+// (a.d.sink.lb != null: the instantiations that append every solution to the sink; never together with bnb)
 hipError_t launch_smalldfs(const SmallDfsArgs& a, bool bnb, const LaunchPlan& p, hipStream_t stream);
 
 }  // namespace pcp

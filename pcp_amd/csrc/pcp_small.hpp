@@ -1,7 +1,7 @@
 // pcp_small.hpp — what the two kernels over SMALL Interval<i32> stores share: the carve of a workgroup's LDS (the records' copy all its
 // wavefronts read, then one slice per wavefront), the cooperative copy into the shared part, and one ROUND of the fixpoint — every
 // all-different unit as a group, then every record of a live unit, with the `ent` bookkeeping and the step counts.  smallfix_kernel
-// (pcp_small.hip: the fixpoint of a batch of nodes) and smalldfs_kernel (pcp_smalldfs.hip: the search loop, one tree per wavefront) run it on
+// (pcp_small.hip: the fixpoint of a batch of nodes) and smalldfs_kernel (pcp_smalldfs.hip: SmallNode::propagate inside row_dfs, pcp_rowdfs.hpp — the search loop, one tree per wavefront) run it on
 // LdsDom, the node's (-lb, ub) cells in LDS.  The records' twin of pcp_formula.hpp.  Device code only; everything lives in an unnamed
 // namespace.
 #pragma once
@@ -84,7 +84,7 @@ __device__ __forceinline__ SmallShared small_copy_shared(unsigned char* smem, ui
 }
 
 // ONE ROUND of a node's fixpoint, by its wavefront: a live unit counts as entailed (`ent`) until one of its members says otherwise;
-// `node_units(...)` (the node's own propagators: smallfix_kernel; the search loop has none) runs first; then the all-different units, then
+// `node_units(...)` (the node's own propagators: smallfix_kernel; the search loop: row_dfs's exclusion sweep under Enumerate, else nothing) runs first; then the all-different units, then
 // every record of a live unit, lane-strided.  A round that narrows nothing has evaluated every live record on the final domains, so its
 // `ent` IS the units' entailment.  The caller takes the wavefront barrier after the round, reads misc[S_FAIL] and compares ctr.narrow.
 template <class NodeUnits>
