@@ -152,7 +152,7 @@ uint32_t pcp_abi_version(void);
  *     search exactly those stores and return it for a store without one.  pcp_dfs_forest_split_set serves both.
  *   THE SEARCH FORESTS, one row per kind of store:
  *     all-XNeqY, Interval            pcp_dfs_forest_device
- *     formula units, Interval        pcp_dfs_forest_device_form, _form_bnb   (what Cumulative::join builds: XEqYMulZ and Sum keep it here)
+ *     formula units, Interval        pcp_dfs_forest_device_form, _form_bnb, _form_enum (what Cumulative::join builds: XEqYMulZ and Sum keep it here)
  *     records, IntervalSet           pcp_dfs_forest_device_set, _set_enum, _set_bnb
  *     formula units, IntervalSet     pcp_dfs_forest_device_setform, _setform_bnb
  *     small stores, Interval         pcp_dfs_forest_device_small, _small_bnb, _small_enum (plain propagators of any kind, <= 128 slots, <= 2048 filters: Golomb)
@@ -673,9 +673,22 @@ typedef struct {
 int32_t pcp_dfs_forest_device_small_enum(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex,
                                          const pcp_forest_objective* obj, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
                                          void* hip_stream);
+/* Enumerate in the forest of pcp_dfs_forest_device_form — Interval stores WITH formula propagators: schedules, what Cumulative::join builds —
+ * with (obj != NULL) or without branch and bound: the signature and the contract of pcp_dfs_forest_device_small_enum over the stores of
+ * pcp_dfs_forest_device_form.  `ex`, the state between calls, the counters, StopNode, first solutions, stop_on_solution (ignored when
+ * obj != NULL), tree_best / tree_row and the errors 1, 2, 3, 5 and 6 are those of pcp_dfs_forest_device_small_enum.  A node's rounds are
+ * those of pcp_propagate_device_form_excl: its exclusions at the top of every round, then every live unit.  With n_trees = 1 the nodes are
+ * search.dfs_enumerate's over a store with formula units, one for one.  pcp_last_plan: as for pcp_dfs_forest_device_form (path 3).
+ * Set-mode model, val > PCP_VAL_MIN, a null required buffer (st, ex, row_base, row_excl, path with path_capacity > 0), n_trees == 0,
+ * capacity < 2, a bad objective as for _form_bnb: PCP_ERR_ARG.  A store WITHOUT formula propagators (pcp_dfs_forest_device_small_enum
+ * searches it), a node that does not fit one CU's LDS, obj != NULL with a sink attached: PCP_ERR_UNSUPPORTED.  n_steps == 0: PCP_OK,
+ * nothing is launched. */
+int32_t pcp_dfs_forest_device_form_enum(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex,
+                                        const pcp_forest_objective* obj, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
+                                        void* hip_stream);
 /* The solution sink: every solution of an Interval forest, not only their number.  A device-side append buffer of (lb, ub) rows that every
- * tree of pcp_dfs_forest_device_form, pcp_dfs_forest_device_small and pcp_dfs_forest_device_small_enum (obj == NULL) writes its solutions
- * into — the visitor of AllSolution (search/engine/all_solution.rs), resp. OneSolution called in a loop (one_solution.rs:92-105).  A row is
+ * tree of pcp_dfs_forest_device_form, pcp_dfs_forest_device_small, pcp_dfs_forest_device_small_enum and pcp_dfs_forest_device_form_enum
+ * (the last two with obj == NULL) writes its solutions into — the visitor of AllSolution (search/engine/all_solution.rs), resp. OneSolution called in a loop (one_solution.rs:92-105).  A row is
  * the WHOLE node: in interval mode a True node is a box — every unit is entailed while domains may still be wider than one value — and
  * every point of it is a solution; first_solution keeps its lower bounds only.
  *   lb, ub   : [capacity][n_vars] device int32: row i = the i-th solution appended
@@ -692,7 +705,7 @@ int32_t pcp_dfs_forest_device_small_enum(pcp_ctx* ctx, const pcp_dfs_state* st, 
  * that tree's error and stop and calls again runs the node again — propagation is idempotent — and it is counted and appended then.  So
  * after any number of such hand-backs nodes / solutions / failed of every tree are what a sink that never fills leaves, and no solution is
  * lost or written twice.  Rows are in ticket order, which between trees is an order in time.
- * With a sink attached the branch-and-bound entries (pcp_dfs_forest_device_form_bnb, _small_bnb, _small_enum with obj != NULL: they keep
+ * With a sink attached the branch-and-bound entries (pcp_dfs_forest_device_form_bnb, _small_bnb, _small_enum and _form_enum with obj != NULL: they keep
  * tree_row), the all-XNeqY forest pcp_dfs_forest_device and every set-mode forest entry (pcp_dfs_forest_device_set, _set_enum, _set_bnb,
  * _setform, _setform_bnb) return PCP_ERR_UNSUPPORTED and launch nothing; with none attached every entry does what it did before.
  * A null lb, ub or count, capacity == 0, reserved != 0: PCP_ERR_ARG, and the sink attached before stays. */

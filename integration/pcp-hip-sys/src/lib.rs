@@ -273,6 +273,9 @@ extern "C" {
     pub fn pcp_dfs_forest_device_small_enum(ctx: *mut pcp_ctx, st: *const pcp_dfs_state, n_trees: u32, ex: *const pcp_forest_excl,
                                             obj: *const pcp_forest_objective, n_steps: u32, stop_on_solution: u32, node_limit: u64,
                                             hip_stream: *mut c_void) -> i32; // the same forest under Enumerate; obj null: no branch and bound
+    pub fn pcp_dfs_forest_device_form_enum(ctx: *mut pcp_ctx, st: *const pcp_dfs_state, n_trees: u32, ex: *const pcp_forest_excl,
+                                           obj: *const pcp_forest_objective, n_steps: u32, stop_on_solution: u32, node_limit: u64,
+                                           hip_stream: *mut c_void) -> i32; // Enumerate in the forest of _form (stores with formula units)
     pub fn pcp_dfs_forest_device_set(ctx: *mut pcp_ctx, st: *const pcp_forest_state, n_steps: u32, stop_on_solution: u32, node_limit: u64,
                                      hip_stream: *mut c_void) -> i32;
     pub fn pcp_dfs_forest_device_set_enum(ctx: *mut pcp_ctx, st: *const pcp_forest_state, val: u32, n_steps: u32, stop_on_solution: u32,
@@ -285,7 +288,7 @@ extern "C" {
                                              n_steps: u32, node_limit: u64, hip_stream: *mut c_void) -> i32;
     pub fn pcp_dfs_forest_split_set(ctx: *mut pcp_ctx, st: *const pcp_forest_state, n_pairs: u32, pairs: *const u32, done: *mut u32,
                                     hip_stream: *mut c_void) -> i32; // pairs = n_pairs x (donor, receiver), device memory
-    pub fn pcp_solution_sink_set(ctx: *mut pcp_ctx, sink: *const pcp_solution_sink) -> i32; // null detaches; honoured by _form, _small, _small_enum (obj null)
+    pub fn pcp_solution_sink_set(ctx: *mut pcp_ctx, sink: *const pcp_solution_sink) -> i32; // null detaches; honoured by _form, _small, _small_enum and _form_enum (obj null)
     pub fn pcp_dfs_device(ctx: *mut pcp_ctx, st: *const pcp_dfs_state, n_steps: u32, stop_on_solution: u32, node_limit: u64,
                           hip_stream: *mut c_void) -> i32; // OneSolution/AllSolution<Propagation<Brancher<..>>> under StopNode, n_steps nodes
     pub fn pcp_stats_reset(ctx: *mut pcp_ctx, hip_stream: *mut c_void) -> i32;

@@ -1261,18 +1261,21 @@ static int32_t forest_row_launch(pcp_ctx* c, const LaunchPlan& plan, uint32_t pa
 }
 
 // The loop over an Interval store with formula propagators: one tree per wavefront, the unit step of formfix_kernel inside the loop
-// (pcp_formdfs.hip); obj != nullptr: under branch and bound.  The stacks are those of pcp_dfs_forest_device.
-static int32_t dfs_forest_form(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_objective* obj, uint32_t n_steps, uint32_t stop_on_solution,
-                               uint64_t node_limit, void* hip_stream) {
-  const std::string who = obj ? "pcp_dfs_forest_device_form_bnb" : "pcp_dfs_forest_device_form";
-  { const int32_t rc = forest_row_check(c, who, "pcp_dfs_forest_device_setform", st, n_trees, nullptr, obj); if (rc) return rc; }
+// (pcp_formdfs.hip); obj != nullptr: under branch and bound.  The stacks are those of pcp_dfs_forest_device.  ex != nullptr: under
+// Enumerate (pcp_dfs_forest_device_form_enum), each tree with its exclusion path.
+static int32_t dfs_forest_form(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex, const pcp_forest_objective* obj, uint32_t n_steps,
+                               uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
+  const std::string who = ex ? "pcp_dfs_forest_device_form_enum" : obj ? "pcp_dfs_forest_device_form_bnb" : "pcp_dfs_forest_device_form";
+  { const int32_t rc = forest_row_check(c, who, "pcp_dfs_forest_device_setform", st, n_trees, ex, obj); if (rc) return rc; }
+  if (!c->has_formulas && ex)
+    return fail(c, PCP_ERR_UNSUPPORTED, who + " searches stores with formula propagators (Boolean / pcp_model_push_formula): a small store of plain propagators is searched by pcp_dfs_forest_device_small_enum");
   if (!c->has_formulas)
     return fail(c, PCP_ERR_UNSUPPORTED, who + " searches stores with formula propagators (Boolean / pcp_model_push_formula): an all-XNeqY store is searched by pcp_dfs_forest_device, any other by pcp_dfs_device, one tree");
   const LaunchPlan plan = forest_row_plan(c, n_trees, [&](uint32_t waves) { return lds_bytes_formdfs(c->n_slots, c->n_units, waves); });
   if (!plan.lds_bytes) return fail(c, PCP_ERR_UNSUPPORTED, who + ": a tree's node must fit one CU's LDS (8 bytes per variable and interned constant, and the unit mask)");
   FormDfsArgs a;
   memset(&a, 0, sizeof(a));
-  fill_row_args(a.m, a.d, c, st, n_trees, obj, nullptr, n_steps, stop_on_solution, node_limit);
+  fill_row_args(a.m, a.d, c, st, n_trees, obj, ex, n_steps, stop_on_solution, node_limit);
   a.nodes = c->d_fnodes; a.unit_root = c->d_unit_root; a.n_units = c->n_units;
   return forest_row_launch(c, plan, 3u, n_steps, hip_stream, [&](hipStream_t stream) { return launch_formdfs(a, obj != nullptr, plan, stream); });
 }
@@ -1280,13 +1283,19 @@ static int32_t dfs_forest_form(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_t
 int32_t pcp_dfs_forest_device_form(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
                                    void* hip_stream) {
   if (!c || !st) return c ? fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_form: null state") : PCP_ERR_ARG;
-  return dfs_forest_form(c, st, n_trees, nullptr, n_steps, stop_on_solution, node_limit, hip_stream);
+  return dfs_forest_form(c, st, n_trees, nullptr, nullptr, n_steps, stop_on_solution, node_limit, hip_stream);
 }
 
 int32_t pcp_dfs_forest_device_form_bnb(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_objective* obj, uint32_t n_steps, uint64_t node_limit,
                                        void* hip_stream) {
   if (!c || !st || !obj) return c ? fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_form_bnb: null state / objective") : PCP_ERR_ARG;
-  return dfs_forest_form(c, st, n_trees, obj, n_steps, 0, node_limit, hip_stream);
+  return dfs_forest_form(c, st, n_trees, nullptr, obj, n_steps, 0, node_limit, hip_stream);
+}
+
+int32_t pcp_dfs_forest_device_form_enum(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex, const pcp_forest_objective* obj,
+                                        uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
+  if (!c || !st || !ex) return c ? fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_form_enum: null state / exclusions") : PCP_ERR_ARG;
+  return dfs_forest_form(c, st, n_trees, ex, obj, n_steps, obj ? 0u : stop_on_solution, node_limit, hip_stream);
 }
 
 // The same loop over a SMALL Interval store of plain propagators — what smallfix_kernel propagates (plan.path 4): one tree per wavefront,

@@ -7,7 +7,14 @@
 // 256-thread workgroup, each on its own LDS slice (form_carve, the slice of formfix_kernel: nothing more is needed, the loop's own state is
 // wave-uniform and sits in registers).  A tree is a latency chain; a CU wants as many chains as its registers allow.
 // There is no workgroup barrier: the trees of a workgroup never wait for each other.
+//
+// ENUM = true (pcp_dfs_forest_device_form_enum): the loop under Enumerate.  The exclusion path, the rows' two words and the value re-choice
+// are the loop's (pcp_rowdfs.hpp); this node runs the loop's sweep at the top of every round, fenced from the units that read what it
+// wrote — formexcl_kernel's round (pcp_formexcl.hip) — and lends it the per-lane step count and F_OOB.  No LDS is added: the path and the
+// rows' words are in HBM, the length of the current list is a wave-uniform register.  Unit liveness stays derived: the sweep never
+// touches `live`, and an open exclusion keeps a node Unknown through the loop's ex_open.
 #include <algorithm>
+#include <type_traits>
 
 #include "pcp_formula.hpp"
 #include "pcp_rowdfs.hpp"
@@ -19,7 +26,7 @@ namespace {
 // A node of formula units in its wavefront's slice: Jacobi rounds over the live units, a unit unlinked inside the round that finds it
 // entailed, so that what is left of `live` after the rounds is what is still subscribed.
 struct FormulaNode {
-  enum : uint32_t { FAIL = F_FAIL, WORDS = F_WORDS };
+  enum : uint32_t { FAIL = F_FAIL, OOB = F_OOB, WORDS = F_WORDS };
   const FormDfsArgs& a;
   const uint32_t lane, V, S, U;
   const int32_t* const const_val;
@@ -35,11 +42,14 @@ struct FormulaNode {
         misc(reinterpret_cast<uint32_t*>(mine + cv.misc)), ctr(ctr_), dm{dom, 1u, chg, &misc[F_FAIL], 1u, &ctr_, a_.m.sums} {}
 
   template <class Sweep>
-  __device__ __forceinline__ bool propagate(bool failed, Sweep&&) {
+  __device__ __forceinline__ bool propagate(bool failed, Sweep&& sweep) {
     uint32_t rounds = 0;
     while (!failed) {
       ++rounds;
       const uint32_t before = ctr.narrow;
+      // the node's exclusions, then every live unit: formexcl_kernel's round (pcp_formexcl.hip).  The sweep writes `dom` through `dm`, the
+      // units read it.  BinarySplit's callable is an empty type: nothing to run, no fence
+      if constexpr (!std::is_empty_v<std::remove_reference_t<Sweep>>) { sweep(steps2); wave_sync(); }
       for (uint32_t u = lane; u < U; u += 64) {
         if (!((live[u >> 5] >> (u & 31u)) & 1u)) continue;
         if (form_unit_step(a.nodes, a.unit_root, a.m.recs, u, dm, steps2, steps3))
@@ -61,23 +71,23 @@ struct FormulaNode {
   __device__ __forceinline__ void flush_stats(pcp_stats* stats) const { flush_node_stats(stats, lane, steps2, steps3, ctr.narrow, acc_rounds, acc_nodes); }
 };
 
-template <bool BNB, bool SINK>
+template <bool BNB, bool ENUM, bool SINK>
 __global__ void __launch_bounds__(256) formdfs_kernel(const FormDfsArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwv = blockDim.x >> 6;
   const FormCarve cv = form_carve(a.m.n_slots, a.n_units);
   Ctr ctr;
   FormulaNode node(a, smem + (size_t)wv * cv.total, cv, ctr);
-  row_dfs<BNB, false, SINK>(a.d, blockIdx.x * nwv + wv, node);
+  row_dfs<BNB, ENUM, SINK>(a.d, blockIdx.x * nwv + wv, node);
 }
 
-template <bool BNB, bool SINK>
+template <bool BNB, bool ENUM, bool SINK>
 hipError_t launch_formdfs_as(const FormDfsArgs& a, const LaunchPlan& p, hipStream_t stream) {
   hipError_t e;
   if (p.lds_bytes > 64 * 1024 &&
-      (e = hipFuncSetAttribute(reinterpret_cast<const void*>(formdfs_kernel<BNB, SINK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes)) != hipSuccess)
+      (e = hipFuncSetAttribute(reinterpret_cast<const void*>(formdfs_kernel<BNB, ENUM, SINK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes)) != hipSuccess)
     return e;
-  hipLaunchKernelGGL((formdfs_kernel<BNB, SINK>), dim3(p.grid), dim3(p.block), p.lds_bytes, stream, a);
+  hipLaunchKernelGGL((formdfs_kernel<BNB, ENUM, SINK>), dim3(p.grid), dim3(p.block), p.lds_bytes, stream, a);
   return hipGetLastError();
 }
 
@@ -90,11 +100,16 @@ size_t lds_bytes_formdfs(uint32_t n_slots, uint32_t n_units, uint32_t waves) {
 
 // p.block = 64 x the trees of a workgroup, p.grid = ceil(n_trees / those), p.lds_bytes = lds_bytes_formdfs of them
 hipError_t launch_formdfs(const FormDfsArgs& a, bool bnb, const LaunchPlan& p, hipStream_t stream) {
-  if (a.d.sink.lb) {  // the context's solution sink (pcp_solution_sink_set); the branch-and-bound entries refuse it
-    if (bnb || !a.d.sink.ub || !a.d.sink.count || !a.d.sink.capacity) return hipErrorInvalidValue;
-    return launch_formdfs_as<false, true>(a, p, stream);
+  // the context's solution sink (pcp_solution_sink_set); the branch-and-bound entries refuse it
+  const bool sink = a.d.sink.lb != nullptr;
+  if (sink && (bnb || !a.d.sink.ub || !a.d.sink.count || !a.d.sink.capacity)) return hipErrorInvalidValue;
+  if (a.d.row_base) {  // Enumerate: the rows' words are there (pcp_dfs_forest_device_form_enum)
+    if (!a.d.row_excl || (a.d.path_capacity && !a.d.path)) return hipErrorInvalidValue;
+    if (sink) return launch_formdfs_as<false, true, true>(a, p, stream);
+    return bnb ? launch_formdfs_as<true, true, false>(a, p, stream) : launch_formdfs_as<false, true, false>(a, p, stream);
   }
-  return bnb ? launch_formdfs_as<true, false>(a, p, stream) : launch_formdfs_as<false, false>(a, p, stream);
+  if (sink) return launch_formdfs_as<false, false, true>(a, p, stream);
+  return bnb ? launch_formdfs_as<true, false, false>(a, p, stream) : launch_formdfs_as<false, false, false>(a, p, stream);
 }
 
 }  // namespace pcp

@@ -145,12 +145,12 @@ struct RowDfsArgs {
   int32_t* first_solution;       // [n_trees][n_vars] or null
   uint32_t* violation;
   pcp_stats* stats;
-  // branch and bound only (row_dfs<true, ..>: the _bnb entries, pcp_dfs_forest_device_small_enum with an objective)
+  // branch and bound only (row_dfs<true, ..>: the _bnb entries, pcp_dfs_forest_device_small_enum / _form_enum with an objective)
   uint32_t obj_var, obj_mode;    // the objective variable, PCP_MINIMIZE / PCP_MAXIMIZE
   int32_t* obj_best;             // device int32[1]: the forest's incumbent
   int32_t* tree_best;            // [n_trees]: the value of each tree's last solution
   int32_t* tree_row;             // [n_trees][n_vars] or null: its lower bounds
-  // Enumerate only (row_dfs<.., true, ..>, pcp_dfs_forest_device_small_enum; row_base == null: BinarySplit)
+  // Enumerate only (row_dfs<.., true, ..>, pcp_dfs_forest_device_small_enum / _form_enum; row_base == null: BinarySplit)
   pcp_excl* path;                // [n_trees][path_capacity]: the exclusions along each tree's current path
   uint32_t* row_base;            // [n_trees][capacity]: the path entries a stack row inherits
   pcp_excl* row_excl;            // [n_trees][capacity]: the entry appended when the row is popped (var 0xFFFFFFFF: none)

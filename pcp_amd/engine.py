@@ -25,7 +25,7 @@ ERRORS = {-1: "PCP_ERR_ARG", -2: "PCP_ERR_CONTRACT", -3: "PCP_ERR_HIP", -4: "PCP
 ABI_SYMBOLS = [
     "pcp_ctx_create", "pcp_ctx_destroy", "pcp_last_error", "pcp_strerror", "pcp_abi_version",
     "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull",
-    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
+    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_form_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
 ]
 
 
@@ -87,7 +87,7 @@ class ForestObjective(C.Structure):
 
 
 class ForestExcl(C.Structure):
-    """pcp_forest_excl: the exclusions of pcp_dfs_forest_device_small_enum — one path of entries per tree, two words per stack row."""
+    """pcp_forest_excl: the exclusions of pcp_dfs_forest_device_small_enum / _form_enum — one path of entries per tree, two words per stack row."""
     _fields_ = [("path", C.c_void_p), ("row_base", C.c_void_p), ("row_excl", C.c_void_p), ("path_capacity", C.c_uint32), ("val", C.c_uint32)]
 
 
@@ -218,6 +218,7 @@ def load_library():
     L.pcp_dfs_forest_device_small.argtypes = [vp, C.POINTER(DfsState), u32, u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_small_bnb.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestObjective), u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_small_enum.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestExcl), C.POINTER(ForestObjective), u32, u32, C.c_uint64, vp]
+    L.pcp_dfs_forest_device_form_enum.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestExcl), C.POINTER(ForestObjective), u32, u32, C.c_uint64, vp]
     L.pcp_solution_sink_set.argtypes = [vp, C.POINTER(PcpSolutionSink)]
     L.pcp_stats_reset.argtypes = [vp, vp]
     L.pcp_stats_read.argtypes = [vp, C.POINTER(PcpStats), vp]
@@ -226,7 +227,7 @@ def load_library():
     L.pcp_last_plan.argtypes = [vp, C.POINTER(PcpPlan)]
     L.pcp_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
     for f in ("pcp_ctx_create", "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull", "pcp_model_set_hull",
-              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
+              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_form_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
         getattr(L, f).restype = i32
     _lib = L
     return L
@@ -570,7 +571,7 @@ class Context:
 
     def solution_sink_set(self, sink=None):
         """pcp_solution_sink_set: attach a solution sink — a SolutionSink or a PcpSolutionSink over device buffers — to this context, or
-        detach the one attached (None).  While one is attached the forests dfs_forest(formulas=True) and dfs_forest(small=True) append every
+        detach the one attached (None).  While one is attached the forests dfs_forest(formulas=True), dfs_forest(small=True) and dfs_forest_enum append every
         solution to it as an (lb, ub) row and hand a node back with error 6 (SINK_FULL) when it is full; every other forest entry refuses to
         run (PCP_ERR_UNSUPPORTED).  The struct is copied; the buffers must outlive the attachment."""
         st = sink.struct() if isinstance(sink, SolutionSink) else sink
@@ -579,7 +580,8 @@ class Context:
     def dfs_forest(self, root_lb, root_ub, stop_on_solution: bool = False, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
                    max_launches: int = 1 << 30, node_budget: int = 0, want_solution: bool = False, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
                    sp0=None, hints: bool = True, formulas: bool = False, small: bool = False, _call=None, brancher: str = "split", val: str = "middle",
-                   root_excl=None, path_capacity: int = 64, max_path: int = 1 << 20, _obj=None, collect_solutions: bool = False, sink_capacity: int = 4096):
+                   root_excl=None, path_capacity: int = 64, max_path: int = 1 << 20, _obj=None, collect_solutions: bool = False, sink_capacity: int = 4096,
+                   _enum_entry=None):
         """pcp_dfs_forest_device: the reference's search loop (interval mode, all-XNeqY models) on many subtrees at once, one workgroup per
         tree, each exactly a pcp_dfs_device instance.  root_lb / root_ub: [n_trees, n_vars] int32 (numpy or CUDA tensors): the roots, not yet
         propagated.  Launches of steps_per_launch nodes per tree are repeated until every stack is empty, a tree stopped (solution with
@@ -600,6 +602,7 @@ class Context:
         one per root — the exclusions the root arrives with (None: no root has any); they are written into each tree's path.  A tree's path
         holds ``path_capacity`` entries and is doubled, up to ``max_path``, when a tree reports error 5, as its stack is on error 1.  ``info``
         also receives ``path_grown`` and ``path_capacity``.  The default ``brancher="split"`` issues exactly the calls it issued before.
+        (Enumerate over a store with formula units: dfs_forest_enum, which chooses the forest by what the store is.)
         ``collect_solutions`` (``formulas=True`` or ``small=True``, either brancher, one rank; otherwise a ValueError): every solution is
         returned, not only counted — a SolutionSink of ``sink_capacity`` rows is attached for the duration of the call, a tree that finds it
         full hands its node back (error 6), the loop drains the sink and resumes that tree, as it grows a stack on error 1; the counters
@@ -610,7 +613,8 @@ class Context:
         import torch
         if small and formulas:
             raise ValueError("dfs_forest: small=True and formulas=True name two different forests (a store has formula units or it has none)")
-        enum = _check_forest_brancher("dfs_forest", brancher, val, small, dist, root_excl)
+        # (_enum_entry: dfs_forest_enum's — the Enumerate entry of the forest the store belongs to, in place of the small-store one)
+        enum = _check_forest_brancher("dfs_forest", brancher, val, small or _enum_entry is not None, dist, root_excl)
         _check_collect("dfs_forest", collect_solutions, sink_capacity, small, formulas, dist, _call is not None or _obj is not None)
         dev = torch.device("cuda", self.device)
         V = self.n_vars
@@ -662,8 +666,8 @@ class Context:
 
         def launch():
             if enum:  # (_obj: dfs_forest_bnb's objective)
-                self._check(self._L.pcp_dfs_forest_device_small_enum(self._h, C.byref(box["st"]), T, C.byref(box["ex"]), C.byref(_obj) if _obj is not None else None,
-                                                                    int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit_per_tree), C.c_void_p(stream)))
+                self._check((_enum_entry or self._L.pcp_dfs_forest_device_small_enum)(self._h, C.byref(box["st"]), T, C.byref(box["ex"]), C.byref(_obj) if _obj is not None else None,
+                                                                                     int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit_per_tree), C.c_void_p(stream)))
             elif _call is not None:  # (dfs_forest_bnb: the same loop over another entry point)
                 self._check(_call(box["st"], T, stream))
             else:
@@ -700,7 +704,7 @@ class Context:
     def dfs_forest_bnb(self, root_lb, root_ub, objective, best0=None, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
                        max_launches: int = 1 << 30, node_budget: int = 0, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
                        sp0=None, small: bool = False, brancher: str = "split", val: str = "middle", root_excl=None, path_capacity: int = 64,
-                       max_path: int = 1 << 20, collect_solutions: bool = False):
+                       max_path: int = 1 << 20, collect_solutions: bool = False, _enum_entry=None):
         """pcp_dfs_forest_device_form_bnb: branch and bound (branch_and_bound.rs:64-84) in the forest over an Interval store with formula
         propagators — the loop, stacks, growth and refill of dfs_forest(formulas=True), every popped row entered with the forest's incumbent
         (one device word) folded into the objective's bounds.  ``objective`` = (var, "min" | "max").  ``best0``: a known bound to start from
@@ -709,10 +713,10 @@ class Context:
         "no solution yet" value).
         ``small``: the store is a small one of plain propagators (dfs_forest(small=True)): the same loop and result over
         pcp_dfs_forest_device_small_bnb.  ``brancher`` / ``val`` / ``root_excl`` / ``path_capacity`` / ``max_path``: as for dfs_forest
-        (Enumerate needs ``small=True``: pcp_dfs_forest_device_small_enum with the objective).  ``collect_solutions=True`` is a ValueError:
+        (Enumerate needs ``small=True``: pcp_dfs_forest_device_small_enum with the objective; dfs_forest_enum(objective=) runs it over either store).  ``collect_solutions=True`` is a ValueError:
         branch and bound keeps ``best_solution``, and its entries refuse a solution sink."""
         import torch
-        _check_forest_brancher("dfs_forest_bnb", brancher, val, small, dist, root_excl)
+        _check_forest_brancher("dfs_forest_bnb", brancher, val, small or _enum_entry is not None, dist, root_excl)
         _check_collect("dfs_forest_bnb", collect_solutions, 1, small, not small, None, bnb=True)
         var, mode = objective
         if mode not in OBJ_MODES:
@@ -731,7 +735,7 @@ class Context:
 
         out = self.dfs_forest(root_lb, root_ub, node_limit_per_tree=node_limit_per_tree, steps_per_launch=steps_per_launch, capacity=capacity, max_launches=max_launches,
                               node_budget=node_budget, rebalance=rebalance, info=info, dist=dist, max_capacity=max_capacity, sp0=sp0, formulas=not small, small=small, _call=call,
-                              **(dict(brancher=brancher, val=val, root_excl=root_excl, path_capacity=path_capacity, max_path=max_path, _obj=obj) if brancher != "split" else {}))
+                              **(dict(brancher=brancher, val=val, root_excl=root_excl, path_capacity=path_capacity, max_path=max_path, _obj=obj, _enum_entry=_enum_entry) if brancher != "split" else {}))
         tb = tree_best.cpu().numpy()
         found = tb != none
         out["tree_best"] = tb
@@ -739,6 +743,35 @@ class Context:
         winners = np.nonzero(found & (tb == int(d_best.item())))[0]
         out["best_solution"] = tree_row[int(winners[0])].cpu().numpy() if len(winners) else None
         return out
+
+    def dfs_forest_enum(self, root_lb, root_ub, val: str = "middle", objective=None, best0=None, root_excl=None, path_capacity: int = 64, max_path: int = 1 << 20,
+                        collect_solutions: bool = False, sink_capacity: int = 4096, stop_on_solution: bool = False, node_limit_per_tree: int = 0,
+                        steps_per_launch: int = 256, capacity: int = 2048, max_launches: int = 1 << 30, node_budget: int = 0, want_solution: bool = False,
+                        rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0):
+        """The Enumerate forest over this context's Interval store, chosen by what the store IS (as search.dfs_enumerate and DeviceSearch
+        dispatch): pcp_dfs_forest_device_form_enum when it holds formula units (``has_formulas`` — schedules, what Cumulative.join builds),
+        else pcp_dfs_forest_device_small_enum.  The trees run under Enumerate on MiddleVal (``val="middle"``) or MinVal (``"min"``); roots,
+        ``root_excl``, ``path_capacity`` / ``max_path``, ``collect_solutions`` / ``sink_capacity``, the loop keywords, stack and path growth,
+        steals and the result dict are those of dfs_forest(brancher="enumerate") — it is that loop.  ``objective`` = (var, "min" | "max"):
+        under branch and bound, ``best0`` a known bound to start from; the result then also holds the keys of dfs_forest_bnb (``best``,
+        ``best_solution``, ``tree_best``), and ``stop_on_solution`` / ``want_solution`` do not apply.  One rank: ``dist`` is a ValueError,
+        as are a ``val`` other than "middle" / "min", ``collect_solutions`` with an objective, and a ``root_excl`` whose length is not the
+        number of roots."""
+        if dist is not None:
+            raise ValueError("dfs_forest_enum: Enumerate does not run on several ranks (moving exclusion lists between ranks is not built)")
+        if val not in VAL_MODES:
+            raise ValueError(f"dfs_forest_enum: val must be 'middle' or 'min', not {val!r}")
+        if collect_solutions and objective is not None:
+            raise ValueError("dfs_forest_enum: collect_solutions does not go with an objective (branch and bound keeps best_solution; its entries refuse a solution sink)")
+        form = self.has_formulas
+        entry = self._L.pcp_dfs_forest_device_form_enum if form else self._L.pcp_dfs_forest_device_small_enum
+        kw = dict(node_limit_per_tree=node_limit_per_tree, steps_per_launch=steps_per_launch, capacity=capacity, max_launches=max_launches, node_budget=node_budget,
+                  rebalance=rebalance, info=info, max_capacity=max_capacity, small=not form, brancher="enumerate", val=val, root_excl=root_excl,
+                  path_capacity=path_capacity, max_path=max_path, _enum_entry=entry)
+        if objective is not None:
+            return self.dfs_forest_bnb(root_lb, root_ub, objective, best0=best0, **kw)
+        return self.dfs_forest(root_lb, root_ub, stop_on_solution=stop_on_solution, want_solution=want_solution, formulas=form,
+                               collect_solutions=collect_solutions, sink_capacity=sink_capacity, **kw)
 
     def dfs_forest_set(self, root_bits, stop_on_solution: bool = False, node_limit: int = 0, steps_per_launch: int = 256,
                        level_capacity: int = 0, trail_capacity: int = 0, max_launches: int = 1 << 30, want_solution: bool = True,
@@ -921,11 +954,12 @@ def _check_brancher(brancher, val):
 
 
 def _check_forest_brancher(who, brancher, val, small, dist, root_excl=None) -> bool:
-    """The distributor of an Interval forest: True under Enumerate.  Enumerate runs in the small-store forest alone, on one rank."""
+    """The distributor of an Interval forest: True under Enumerate.  Through ``small=True`` Enumerate runs in the small-store forest, on one
+    rank; Context.dfs_forest_enum / search_forest.forest_enumerate choose the forest by the store and reach the formula-store forest too."""
     _check_brancher(brancher, val)
     enum = brancher == "enumerate"
     if enum and not small:
-        raise ValueError(f"{who}: brancher='enumerate' runs in the small-store forest only (small=True); the all-XNeqY forest and the formula-store forest stay on BinarySplit")
+        raise ValueError(f"{who}: brancher='enumerate' needs small=True here (the small-store forest; the all-XNeqY forest stays on BinarySplit) — Context.dfs_forest_enum / search_forest.forest_enumerate run Enumerate over either Interval store, the formula-store forest included")
     if enum and dist is not None:
         raise ValueError(f"{who}: brancher='enumerate' does not run on several ranks (moving exclusion lists between ranks is not built)")
     if root_excl is not None and not enum:

@@ -421,7 +421,7 @@ STACK_BYTES_CAP = 64 << 30  # default ceiling of the forest's stack rows per GPU
 
 def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_per_launch: int = 512, rank: int = 0, world: int = 1, capacity: int = 0,
                   dist=None, info: dict | None = None, stack_bytes: int = STACK_BYTES_CAP, formulas: bool = False, small: bool = False, brancher: str = "split",
-                  val: str = "middle", collect_solutions: bool = False, sink_capacity: int = 4096) -> dict:
+                  val: str = "middle", collect_solutions: bool = False, sink_capacity: int = 4096, _by_store=None) -> dict:
     """Interval mode, all-XNeqY models: expansion + one in-kernel DFS per open node (pcp_dfs_forest_device).  formulas: the store holds
     formula propagators (what Cumulative.join builds): the trees run in pcp_dfs_forest_device_form, one per wavefront.  small: a small store of
     plain propagators of any kind (the Golomb network): pcp_dfs_forest_device_small, one tree per wavefront; with formulas=True a ValueError.  The node limit is checked
@@ -439,7 +439,8 @@ def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_
     if small and formulas:
         raise ValueError("forest_search: small=True and formulas=True name two different forests (a store has formula units or it has none)")
     from .engine import _check_collect, _check_forest_brancher
-    enum = _check_forest_brancher("forest_search", brancher, val, small, dist)
+    # (_by_store: forest_enumerate's — the trees run in Context.dfs_forest_enum, which chooses the forest by the store, with these further keywords)
+    enum = _check_forest_brancher("forest_search", brancher, val, small or _by_store is not None, dist)
     if enum and world > 1:
         raise ValueError("forest_search: brancher='enumerate' does not run on several ranks (moving exclusion lists between ranks is not built)")
     _check_collect("forest_search", collect_solutions, sink_capacity, small, formulas, dist if dist is not None else (True if world > 1 else None))
@@ -485,9 +486,11 @@ def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_
             import torch
             upfront = max(upfront, torch.cuda.mem_get_info(ml.device)[0] // 8)
         capacity = ceiling if (per_tree and not multi and ceiling * row_bytes <= upfront) else min(128, ceiling)
-    r = ctx.dfs_forest(ml, mu, node_limit_per_tree=0 if multi else per_tree, steps_per_launch=steps_per_launch, capacity=capacity, max_capacity=max(ceiling, capacity),
-                       node_budget=max(node_limit - st.num_nodes, 1) if multi else budget, dist=dist if multi else None, info=info, sp0=sp0, formulas=formulas, small=small,
-                       **(dict(brancher=brancher, val=val, root_excl=lists) if enum else {}),
+    r = (ctx.dfs_forest_enum if _by_store is not None else ctx.dfs_forest)(
+                       ml, mu, node_limit_per_tree=0 if multi else per_tree, steps_per_launch=steps_per_launch, capacity=capacity, max_capacity=max(ceiling, capacity),
+                       node_budget=max(node_limit - st.num_nodes, 1) if multi else budget, dist=dist if multi else None, info=info,
+                       **(dict(val=val, root_excl=lists, **_by_store) if _by_store is not None else dict(sp0=sp0, formulas=formulas, small=small)),
+                       **(dict(brancher=brancher, val=val, root_excl=lists) if enum and _by_store is None else {}),
                        **(dict(collect_solutions=True, sink_capacity=sink_capacity) if collect_solutions else {}))
     out["nodes"] += r["nodes"]; out["solutions"] += r["solutions"]; out["failed"] += r["failed"]
     out["error"] = r["error"]; out["launches"] = r["launches"]
@@ -499,7 +502,7 @@ def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_
 
 def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: int = 512, best0=None, capacity: int = 128, max_capacity: int = 1 << 16,
                info: dict | None = None, formulas: bool = True, small: bool = False, brancher: str = "split", val: str = "middle",
-               collect_solutions: bool = False) -> dict:
+               collect_solutions: bool = False, _by_store=None) -> dict:
     """Branch and bound over an Interval store with formula propagators (branch_and_bound.rs:64-84 around the loop of forest_search):
     minimize / maximize ``objective`` = (var, "min" | "max") below (lb0, ub0).  The root is expanded breadth-first under branch and bound
     (seed_roots_interval with DeviceSearch(objective=)) to at least ``n_trees`` open nodes; each becomes a tree of
@@ -515,7 +518,7 @@ def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: i
     if not formulas and not small:
         raise ValueError("forest_bnb searches stores with formula propagators (all-XNeqY stores have no objective to bound)")
     from .engine import _check_forest_brancher
-    enum = _check_forest_brancher("forest_bnb", brancher, val, small, None)
+    enum = _check_forest_brancher("forest_bnb", brancher, val, small or _by_store is not None, None)  # (_by_store: forest_enumerate's, see forest_search)
     var, mode = objective
     lists = None
     if enum:
@@ -529,6 +532,9 @@ def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: i
     if rl.shape[0] == 0:  # the expansion finished the tree
         out = {"nodes": 0, "solutions": 0, "failed": 0, "error": 0, "open": 0, "launches": 0, "trees": 0, "steals": 0, "tree_best": np.zeros(0, np.int32),
                "best": None, "best_solution": None}
+    elif _by_store is not None:
+        out = ctx.dfs_forest_enum(rl, ru, val=val, objective=(int(var), mode), best0=start, root_excl=lists, steps_per_launch=steps_per_launch, capacity=capacity,
+                                  max_capacity=max(max_capacity, capacity), info=info, **_by_store)
     else:
         out = ctx.dfs_forest_bnb(rl, ru, (int(var), mode), best0=start, steps_per_launch=steps_per_launch, capacity=capacity,
                                  max_capacity=max(max_capacity, capacity), info=info, small=small,
@@ -540,3 +546,30 @@ def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: i
     if out["best"] is None and seeded["best"] is not None and beats(seeded["best"], best0):
         out["best"], out["best_solution"] = seeded["best"], seeded["best_solution"]
     return out
+
+
+def forest_enumerate(ctx, lb0, ub0, val: str = "middle", objective=None, n_trees: int = 256, steps_per_launch: int = 512, best0=None, collect_solutions: bool = False,
+                     sink_capacity: int = 4096, info: dict | None = None, capacity: int = 128, max_capacity: int = 1 << 16, path_capacity: int = 64, rebalance: bool = True,
+                     dist=None) -> dict:
+    """Enumerate over the context's Interval store, whichever forest it belongs to — the formula-store forest (``ctx.has_formulas``:
+    schedules, what Cumulative.join builds) or the small-store one: the root is expanded breadth-first under
+    DeviceSearch(brancher="enumerate", val=, objective=) to at least ``n_trees`` open nodes (seed_roots_interval), each becomes a tree of
+    Context.dfs_forest_enum with the exclusion list the expansion gave it as its ``root_excl``, so that the expansion and the trees
+    together are one Enumerate tree.  Without ``objective`` it is forest_search(brancher="enumerate") and returns its dict
+    (``collect_solutions`` / ``sink_capacity``: every solution as a box, the expansion's first); with ``objective`` = (var, "min" | "max") it
+    is forest_bnb(brancher="enumerate") and returns its dict (``best0``: a known bound to start from).  ``capacity`` / ``max_capacity``: a tree's stack rows, at first and at most; ``path_capacity``: its
+    exclusion path at first (both grow on demand).  One rank: ``dist`` is a
+    ValueError, as are a ``val`` other than "middle" / "min" and ``collect_solutions`` with an objective."""
+    from .engine import VAL_MODES
+    if dist is not None:
+        raise ValueError("forest_enumerate: Enumerate does not run on several ranks (moving exclusion lists between ranks is not built)")
+    if val not in VAL_MODES:
+        raise ValueError(f"forest_enumerate: val must be 'middle' or 'min', not {val!r}")
+    if collect_solutions and objective is not None:
+        raise ValueError("forest_enumerate: collect_solutions does not go with an objective (branch and bound returns best_solution)")
+    form = ctx.has_formulas
+    if objective is not None:
+        return forest_bnb(ctx, lb0, ub0, objective, n_trees=n_trees, steps_per_launch=steps_per_launch, best0=best0, capacity=capacity, max_capacity=max_capacity,
+                          info=info, formulas=form, small=not form, brancher="enumerate", val=val, _by_store=dict(path_capacity=path_capacity, rebalance=rebalance))
+    return forest_search(ctx, lb0, ub0, n_trees=n_trees, steps_per_launch=steps_per_launch, capacity=capacity, info=info, formulas=form, small=not form,
+                         brancher="enumerate", val=val, collect_solutions=collect_solutions, sink_capacity=sink_capacity, _by_store=dict(path_capacity=path_capacity, rebalance=rebalance))
