@@ -25,7 +25,8 @@ extern "C" {
 #endif
 
 #define PCP_ABI_VERSION 8 /* (formula units over set-mode stores came without a new number: no symbol and no layout changed, calls that
-                             were refused with PCP_ERR_UNSUPPORTED now work) */
+                             were refused with PCP_ERR_UNSUPPORTED now work; so did the variable selector InputOrder, option "var_select":
+                             no symbol and no layout changed, the default selects what every entry selected before) */
 
 /* Operand encodings for pcp_prop.var[i]. */
 #define PCP_CONST 0xFFFFFFFFu /* operand is a term::Constant (term/constant.rs:43-68); off[i] = its value   */
@@ -257,6 +258,8 @@ int32_t pcp_pack_rows(pcp_ctx* ctx, uint32_t n_nodes, const int32_t* lb, const i
 int32_t pcp_unpack_rows(pcp_ctx* ctx, uint32_t n_nodes, const uint32_t* cells, int32_t* lb, int32_t* ub, void* hip_stream);
 /* pcp_branch_device_hint over rows of packed cells (implicit nodes): the same brancher, the same child order (option branch_reverse), the same
  * counts and hints; child_cells has room for 2 n_nodes rows.  A search whose open nodes stay cells between launches needs nothing else. */
+/* (This brancher selects FirstSmallestVar only: under option var_select = PCP_VAR_INPUT_ORDER it returns PCP_ERR_UNSUPPORTED and launches
+ * nothing; pcp_branch_device_hint on int32 rows honours the option.) */
 int32_t pcp_branch_device_cells(pcp_ctx* ctx, uint32_t n_nodes, const uint32_t* cells, const uint8_t* status, uint32_t* child_cells,
                                 uint32_t* child_dirty, uint32_t* counts, void* hip_stream);
 int32_t pcp_propagate_device(pcp_ctx* ctx, uint32_t n_nodes, const pcp_device_batch* batch, void* hip_stream);
@@ -382,7 +385,8 @@ int32_t pcp_propagate_device_form_excl(pcp_ctx* ctx, uint32_t n_nodes, const pcp
 /* ---- branching on the device (the caller side of the path) -------------------------------------
  * ≡ Brancher<FirstSmallestVar, MiddleVal, BinarySplit>::enter (search/branching/brancher.rs:52-71) applied to every
  * PCP_UNKNOWN node of a propagated batch:
- *   variable = first index among the variables of minimal size > 1   (first_smallest_var.rs:30-39)
+ *   variable = first index among the variables of minimal size > 1   (first_smallest_var.rs:30-39) or, under option var_select = PCP_VAR_INPUT_ORDER,
+ *              the first index with size > 1   (input_order.rs:30-39)
  *   value    = (lb + ub) / 2 truncated toward zero                   (middle_val.rs:25-27)
  *   children = `x <= value` then `x > value`                          (binary_split.rs:46-57), folded into the bounds
  * (a var-vs-constant XLessY narrows its variable on its first run and is then entailed and unlinked, x_less_y.rs:87-109).
@@ -404,7 +408,8 @@ int32_t pcp_branch_device_hint(pcp_ctx* ctx, uint32_t n_nodes, const int32_t* lb
                                const uint8_t* status, int32_t* child_lb, int32_t* child_ub, uint64_t* child_active,
                                uint32_t* child_dirty, uint32_t* counts, void* hip_stream);
 
-/* The same over FDSpace (set mode): FirstSmallestVar compares CARDINALITIES (first_smallest_var.rs:30-39: Domain::size()), MiddleVal
+/* The same over FDSpace (set mode): FirstSmallestVar compares CARDINALITIES (first_smallest_var.rs:30-39: Domain::size()) — under option
+ * var_select = PCP_VAR_INPUT_ORDER the variable is the first index with cardinality > 1 (input_order.rs:30-39) —, MiddleVal
  * is (lower + upper) / 2 of the set's bounds, the children keep the values <= value resp. > value of the variable's set.
  *   bits [n_nodes][n_vars][set_words], lb/ub [n_nodes][n_vars] = the outputs of pcp_propagate_device;
  *   child_bits [2*n_nodes][n_vars][set_words] (capacity); active / child_active as above (both NULL for implicit nodes). */
@@ -416,7 +421,8 @@ int32_t pcp_branch_device_set(pcp_ctx* ctx, uint32_t n_nodes, const uint64_t* bi
  * applied to every PCP_UNKNOWN node of a propagated set-mode batch.  On an IntervalSet XEqY(x, Constant v) intersects x with {v} and
  * XNeqY(x, Constant v) removes v wherever it sits, and both are then entailed: both children are folded into the variable's set, there are
  * no exclusion lists and the children are propagated like any other set-mode row.
- *   variable = first index among the variables of minimal CARDINALITY > 1   (first_smallest_var.rs:30-39 on Domain::size())
+ *   variable = first index among the variables of minimal CARDINALITY > 1   (first_smallest_var.rs:30-39 on Domain::size()) or, under option var_select = PCP_VAR_INPUT_ORDER,
+ *              the first index with cardinality > 1   (input_order.rs:30-39)
  *   value    = PCP_VAL_MIN: m = lb of the variable (min_val.rs:25-27: lower(), always a member);  PCP_VAL_MIDDLE: m = (lb + ub) / 2 on a 64-bit
  *              sum, truncated toward zero (middle_val.rs:25-27).  The value is the member of the set nearest to m, m - d before m + d: m
  *              itself when it is a member — the reference; when it is not, the reference's left child fails, its right child is the parent
@@ -437,7 +443,8 @@ int32_t pcp_branch_device_set_enum(pcp_ctx* ctx, uint32_t n_nodes, const uint64_
  * ≡ Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>::enter (search/branching/brancher.rs:52-71, search/branching/enumerate.rs:47-60)
  * applied to every PCP_UNKNOWN node of a propagated batch whose node i carries the entries excl[excl_off[i] .. excl_off[i + 1]) (excl_off NULL =
  * no node has any; excl_off[0] need not be 0: a batch may be a slice of a larger CSR):
- *   variable = first index among the variables of minimal size > 1, sizes in 64 bits   (first_smallest_var.rs:30-39)
+ *   variable = first index among the variables of minimal size > 1, sizes in 64 bits   (first_smallest_var.rs:30-39) or, under option var_select = PCP_VAR_INPUT_ORDER,
+ *              the first index with size > 1   (input_order.rs:30-39)
  *   value    = PCP_VAL_MIDDLE: (lb + ub) / 2 truncated toward zero (middle_val.rs:25-27);  PCP_VAL_MIN: lb (min_val.rs:25-27).  A value the
  *              node has excluded already (an entry on the chosen variable) is not chosen again — on Interval<i32> an interior x != v removes
  *              nothing, so MiddleVal would choose it for ever —: the nearest value of [lb, ub] without an entry is taken, v - d before v + d.
@@ -462,6 +469,20 @@ int32_t pcp_branch_device_set_enum(pcp_ctx* ctx, uint32_t n_nodes, const uint64_
  * All pointers are device pointers; everything is enqueued on hip_stream, nothing is synchronised, nothing is allocated in steady state. */
 #define PCP_VAL_MIDDLE 0u
 #define PCP_VAL_MIN 1u
+/* The variable selector, option "var_select" of the context (pcp_set_option), read by each entry when it is called:
+ *   PCP_VAR_FIRST_SMALLEST (the default): the first index among the variables of minimal size > 1   (first_smallest_var.rs:30-39)
+ *   PCP_VAR_INPUT_ORDER                 : the first index with size > 1                             (input_order.rs:30-39)
+ * (set mode: cardinality for size).  Value choice, children, the exclusion rule, child_dirty and the errors are the same under both; error 3 —
+ * an Unknown node with nothing to branch on — is the same case (the reference panics in both, input_order.rs:37).
+ * WHERE "variable = first index among the variables of minimal size > 1" BECOMES "or, under PCP_VAR_INPUT_ORDER, the first index with size > 1":
+ *   pcp_branch_device, _hint, _excl, _set, _set_enum;  pcp_dfs_device (on an all-XNeqY model it then takes its stepping path, as under
+ *   "neq_dfs" 0);  pcp_dfs_forest_device_set, _set_enum, _set_bnb, _setform, _setform_bnb;  pcp_dfs_forest_device_form, _form_bnb,
+ *   _form_enum, _small, _small_bnb, _small_enum, with and without a solution sink.  pcp_dfs_forest_split_set depends on levels, not on the
+ *   selector.
+ * WHERE IT DOES NOT RUN: under PCP_VAR_INPUT_ORDER pcp_dfs_forest_device (the all-XNeqY in-kernel forest) and pcp_branch_device_cells (the
+ *   packed-cell brancher) return PCP_ERR_UNSUPPORTED with a message naming the option and launch nothing. */
+#define PCP_VAR_FIRST_SMALLEST 0u
+#define PCP_VAR_INPUT_ORDER 1u
 int32_t pcp_branch_device_excl(pcp_ctx* ctx, uint32_t n_nodes, const int32_t* lb, const int32_t* ub, const uint8_t* status,
                                const uint32_t* excl_off, const pcp_excl* excl, uint32_t val, int32_t* child_lb, int32_t* child_ub,
                                uint32_t* child_dirty, uint32_t* child_excl_off, pcp_excl* child_excl, uint32_t child_excl_capacity,
@@ -501,6 +522,8 @@ typedef struct {
    * variable of the node.  A caller that moves rows between stacks moves their words along.  All-XNeqY in-kernel loop only. */
   uint32_t* dirty;
 } pcp_dfs_state;
+/* (Variable: the first index among the variables of minimal size > 1 or, under option var_select = PCP_VAR_INPUT_ORDER, the first index with
+ * size > 1 — input_order.rs:30-39; set mode: cardinality.  On an all-XNeqY model the option sends pcp_dfs_device down its stepping path, as "neq_dfs" 0 does) */
 int32_t pcp_dfs_device(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream);
 /* The same loop on n_trees independent stacks at once, one workgroup per tree (ABI v5): tree t is exactly a pcp_dfs_device instance on
  *   lb, ub [n_trees][capacity][n_vars] (tree t's rows start at t * capacity), sp / stop [n_trees], status [n_trees][capacity],
@@ -508,6 +531,9 @@ int32_t pcp_dfs_device(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_steps, 
  * The trees are the subtrees below the open nodes of a frontier (pcp_propagate_device + pcp_branch_device produce one); the caller adds
  * up the counters and decides when to stop launching (all sp == 0, any stop != 0, its node budget).  All-XNeqY models over implicit
  * nodes only (PCP_ERR_UNSUPPORTED otherwise: pcp_dfs_device runs any interval model, one tree). */
+/* (Variable: the first index among the variables of minimal size > 1 or, under option var_select = PCP_VAR_INPUT_ORDER, the first index with
+ * size > 1 — input_order.rs:30-39; set mode: cardinality.  THIS entry selects FirstSmallestVar only: under PCP_VAR_INPUT_ORDER it returns PCP_ERR_UNSUPPORTED and
+ * launches nothing; pcp_dfs_forest_device_small takes an all-XNeqY store within its limits) */
 int32_t pcp_dfs_forest_device(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream);
 /* The same forest for an Interval store WITH formula propagators (Boolean / BooleanNeg / pcp_model_push_formula units) — the stores
  * propagators::Cumulative::join builds (propagators/cumulative.rs:59-114: equivalences over Boolean, XEqYMulZ and Sum views, which set mode
@@ -521,6 +547,8 @@ int32_t pcp_dfs_forest_device(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_
  * Set-mode model, a null required buffer, n_trees == 0, capacity < 2: PCP_ERR_ARG.  A store without formula propagators:
  * PCP_ERR_UNSUPPORTED (all-XNeqY: pcp_dfs_forest_device; any other: pcp_dfs_device, one tree).  A node that does not fit one CU's LDS:
  * PCP_ERR_UNSUPPORTED.  n_steps == 0: PCP_OK, nothing is launched. */
+/* (Variable: the first index among the variables of minimal size > 1 or, under option var_select = PCP_VAR_INPUT_ORDER, the first index with
+ * size > 1 — input_order.rs:30-39; set mode: cardinality.) */
 int32_t pcp_dfs_forest_device_form(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, uint32_t n_steps, uint32_t stop_on_solution,
                                    uint64_t node_limit, void* hip_stream);
 
@@ -557,6 +585,8 @@ typedef struct {
   int32_t* first_solution;
   uint32_t* solution_flag;
 } pcp_forest_state;
+/* (Variable: the first index among the variables of minimal size > 1 or, under option var_select = PCP_VAR_INPUT_ORDER, the first index with
+ * size > 1 — input_order.rs:30-39; set mode: cardinality.) */
 int32_t pcp_dfs_forest_device_set(pcp_ctx* ctx, const pcp_forest_state* st, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream);
 /* The same loop under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate> (enumerate.rs:47-60): a level is `x = value, then x != value`
  * instead of `x <= value, then x > value`; variable and value as pcp_branch_device_set_enum chooses them (val: PCP_VAL_MIDDLE / PCP_VAL_MIN;
@@ -564,6 +594,8 @@ int32_t pcp_dfs_forest_device_set(pcp_ctx* ctx, const pcp_forest_state* st, uint
  * are those of pcp_dfs_forest_device_set; a level records its distributor (levels[..][3]: bit 0 = given away, bit 1 = Enumerate), so
  * pcp_dfs_forest_split_set hands over the right branch of either.  Roots expanded with pcp_branch_device_set_enum under the same val make
  * the union one Enumerate tree. */
+/* (Variable: the first index among the variables of minimal size > 1 or, under option var_select = PCP_VAR_INPUT_ORDER, the first index with
+ * size > 1 — input_order.rs:30-39; set mode: cardinality.) */
 int32_t pcp_dfs_forest_device_set_enum(pcp_ctx* ctx, const pcp_forest_state* st, uint32_t val, uint32_t n_steps, uint32_t stop_on_solution,
                                        uint64_t node_limit, void* hip_stream);
 /* Branch and bound around that loop — BranchAndBound<Propagation<Brancher<..>>> over FDSpace (search/branch_and_bound.rs:64-84; its test,
@@ -591,6 +623,8 @@ typedef struct {
   int32_t* tree_best;
   int32_t* tree_row;
 } pcp_forest_objective;
+/* (Variable: the first index among the variables of minimal size > 1 or, under option var_select = PCP_VAR_INPUT_ORDER, the first index with
+ * size > 1 — input_order.rs:30-39; set mode: cardinality.) */
 int32_t pcp_dfs_forest_device_set_bnb(pcp_ctx* ctx, const pcp_forest_state* st, const pcp_forest_objective* obj, uint32_t enumerate, uint32_t val,
                                       uint32_t n_steps, uint64_t node_limit, void* hip_stream);
 /* The same forest for a store WITH formula propagators (Boolean / BooleanNeg / pcp_model_push_formula units): the loop above under either
@@ -602,10 +636,14 @@ int32_t pcp_dfs_forest_device_set_bnb(pcp_ctx* ctx, const pcp_forest_state* st, 
  * start of a call set every unit live.  With n_trees = 1 the nodes are the reference's, one for one.
  * Interval-mode model, enumerate > 1, val > PCP_VAL_MIN: PCP_ERR_ARG.  A store without formula propagators: PCP_ERR_UNSUPPORTED (it is
  * searched by pcp_dfs_forest_device_set).  A node that does not fit one CU's LDS: PCP_ERR_UNSUPPORTED. */
+/* (Variable: the first index among the variables of minimal size > 1 or, under option var_select = PCP_VAR_INPUT_ORDER, the first index with
+ * size > 1 — input_order.rs:30-39; set mode: cardinality.) */
 int32_t pcp_dfs_forest_device_setform(pcp_ctx* ctx, const pcp_forest_state* st, uint32_t enumerate, uint32_t val, uint32_t n_steps,
                                       uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream);
 /* Branch and bound around it: pcp_dfs_forest_device_set_bnb for stores with formula propagators — the same objective struct, the same fold
  * of *best on entering a node, no stop on a solution.  Also PCP_ERR_ARG: var >= n_vars, mode > PCP_MAXIMIZE, a null best / tree_best. */
+/* (Variable: the first index among the variables of minimal size > 1 or, under option var_select = PCP_VAR_INPUT_ORDER, the first index with
+ * size > 1 — input_order.rs:30-39; set mode: cardinality.) */
 int32_t pcp_dfs_forest_device_setform_bnb(pcp_ctx* ctx, const pcp_forest_state* st, const pcp_forest_objective* obj, uint32_t enumerate,
                                           uint32_t val, uint32_t n_steps, uint64_t node_limit, void* hip_stream);
 /* Branch and bound around pcp_dfs_forest_device_form, the forest over Interval stores with formula propagators (above) —
@@ -616,6 +654,8 @@ int32_t pcp_dfs_forest_device_setform_bnb(pcp_ctx* ctx, const pcp_forest_state* 
  * tree_best[t] = lb[var], tree_row[t] = the node's lower bounds, then *best is lowered / raised atomically.  There is no stop on a solution,
  * and st->first_solution is ignored.  With n_trees = 1 the nodes are the reference's, one for one.
  * Also PCP_ERR_ARG: var >= n_vars, mode > PCP_MAXIMIZE, a null best / tree_best. */
+/* (Variable: the first index among the variables of minimal size > 1 or, under option var_select = PCP_VAR_INPUT_ORDER, the first index with
+ * size > 1 — input_order.rs:30-39; set mode: cardinality.) */
 int32_t pcp_dfs_forest_device_form_bnb(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_objective* obj,
                                        uint32_t n_steps, uint64_t node_limit, void* hip_stream);
 /* The same forest for a SMALL Interval store of plain propagators — no formula units, at most 128 slots (variables and interned constants)
@@ -629,11 +669,15 @@ int32_t pcp_dfs_forest_device_form_bnb(pcp_ctx* ctx, const pcp_dfs_state* st, ui
  * Set-mode model, a null required buffer, n_trees == 0, capacity < 2: PCP_ERR_ARG.  A store with formula propagators: PCP_ERR_UNSUPPORTED
  * (pcp_dfs_forest_device_form).  A store over the limits, or whose records and one node do not fit one CU's LDS: PCP_ERR_UNSUPPORTED
  * (pcp_dfs_device searches it, one tree).  n_steps == 0: PCP_OK, nothing is launched. */
+/* (Variable: the first index among the variables of minimal size > 1 or, under option var_select = PCP_VAR_INPUT_ORDER, the first index with
+ * size > 1 — input_order.rs:30-39; set mode: cardinality.) */
 int32_t pcp_dfs_forest_device_small(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, uint32_t n_steps, uint32_t stop_on_solution,
                                     uint64_t node_limit, void* hip_stream);
 /* Branch and bound around it, exactly as pcp_dfs_forest_device_form_bnb is around pcp_dfs_forest_device_form: one incumbent word *best for
  * the forest, folded into every popped row; tree_best / tree_row on a solution, then *best lowered / raised atomically; no stop on a
  * solution.  Also PCP_ERR_ARG: var >= n_vars, mode > PCP_MAXIMIZE, a null best / tree_best. */
+/* (Variable: the first index among the variables of minimal size > 1 or, under option var_select = PCP_VAR_INPUT_ORDER, the first index with
+ * size > 1 — input_order.rs:30-39; set mode: cardinality.) */
 int32_t pcp_dfs_forest_device_small_bnb(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_objective* obj,
                                         uint32_t n_steps, uint64_t node_limit, void* hip_stream);
 /* The same forest under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate> (search/branching/enumerate.rs:33-60), with (obj != NULL)
@@ -670,6 +714,8 @@ typedef struct {
   uint32_t path_capacity;
   uint32_t val;
 } pcp_forest_excl;
+/* (Variable: the first index among the variables of minimal size > 1 or, under option var_select = PCP_VAR_INPUT_ORDER, the first index with
+ * size > 1 — input_order.rs:30-39; set mode: cardinality.) */
 int32_t pcp_dfs_forest_device_small_enum(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex,
                                          const pcp_forest_objective* obj, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
                                          void* hip_stream);
@@ -683,6 +729,8 @@ int32_t pcp_dfs_forest_device_small_enum(pcp_ctx* ctx, const pcp_dfs_state* st, 
  * capacity < 2, a bad objective as for _form_bnb: PCP_ERR_ARG.  A store WITHOUT formula propagators (pcp_dfs_forest_device_small_enum
  * searches it), a node that does not fit one CU's LDS, obj != NULL with a sink attached: PCP_ERR_UNSUPPORTED.  n_steps == 0: PCP_OK,
  * nothing is launched. */
+/* (Variable: the first index among the variables of minimal size > 1 or, under option var_select = PCP_VAR_INPUT_ORDER, the first index with
+ * size > 1 — input_order.rs:30-39; set mode: cardinality.) */
 int32_t pcp_dfs_forest_device_form_enum(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex,
                                         const pcp_forest_objective* obj, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
                                         void* hip_stream);
@@ -782,7 +830,9 @@ int32_t pcp_last_plan(const pcp_ctx* ctx, pcp_plan* out);
  *   10-bit cells, "implicit_active" 0 = materialise rows for active_in NULL, "group_level" 0 = no group test, "packed" 0 = never use 16-bit cells,
  *   "word_level" 0 = never use the word-group sweep, "solo_cascade" 0 = a wake-up round with one changed variable is an ordinary round
  *   (1, the default: its records are re-run in place and a bound jumps over the values assigned neighbours forbid), "branch_reverse" 1 = pcp_branch_device writes child k of the batch
- *   to row n_children-1-k (a caller appending the rows to a LIFO stack then pops the first node's left child first).
+ *   to row n_children-1-k (a caller appending the rows to a LIFO stack then pops the first node's left child first), "var_select"
+ *   PCP_VAR_FIRST_SMALLEST (0, the default) / PCP_VAR_INPUT_ORDER (1): the variable selector of every brancher and search loop (above, at
+ *   the defines; any other value: PCP_ERR_ARG, the option keeps its value).
  * "time_kernels" 0 = no HIP events around the fixpoint launches: a call enqueues the kernel and nothing else, pcp_last_kernel_ms then has
  *   nothing to report (1, the default: two event records per launch, a few microseconds of queue time each), "small_path" 0 = small stores
  *   use the generic kernels too (1, the default: path 4; any option that asks for a geometry of the generic kernels — "nodes_per_block",

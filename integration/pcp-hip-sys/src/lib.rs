@@ -85,6 +85,10 @@ pub struct pcp_device_batch {
     pub cell_format: u32,
     pub reserved: u32,
 }
+// option "var_select" (pcp_set_option): the variable selector of every device brancher and search loop
+pub const PCP_VAR_FIRST_SMALLEST: u32 = 0; // FirstSmallestVar, the default
+pub const PCP_VAR_INPUT_ORDER: u32 = 1; //    InputOrder: the first variable in store order whose size is > 1
+
 pub const PCP_CELLS_I32: u32 = 0;
 pub const PCP_CELLS_PACKED16: u32 = 1;
 

@@ -89,6 +89,7 @@ struct pcp_ctx : HostModel, LoweredInfo {
   int64_t opt_solo = 1;             // 1 = single-variable rounds re-run in place with the forbidden-value jump (pcp_kernels.hip, rounds c0)
   int64_t opt_list_cap = 2048;
   int64_t opt_global_dom = 0;       // 1 = force the HBM-resident-domain variant (tests)
+  int64_t opt_var_select = PCP_VAR_FIRST_SMALLEST;  // the variable selector of every brancher and search loop: PCP_VAR_FIRST_SMALLEST / PCP_VAR_INPUT_ORDER
   int64_t opt_branch_reverse = 0;   // 1 = pcp_branch_device writes the children in reverse order (row n_children-1-k)
   int64_t opt_packed = 1;           // 1 = auto (16-bit packed tiles when the batch is large enough), 0 = never
   int64_t opt_word_level = 1;       // 1 = auto (word-group sweep with the level -1 range test on packed tiles), 0 = never
@@ -563,6 +564,9 @@ int32_t pcp_set_option(pcp_ctx* c, const char* key, int64_t value) {
   } else if (k == "global_dom") {
     if (value < 0 || value > 2) return fail(c, PCP_ERR_ARG, "global_dom must be 0, 1 (force the HBM-resident variant) or 2 (force it, 10-bit LDS cells allowed)");
     c->opt_global_dom = value;
+  } else if (k == "var_select") {
+    if (value != PCP_VAR_FIRST_SMALLEST && value != PCP_VAR_INPUT_ORDER) return fail(c, PCP_ERR_ARG, "var_select must be PCP_VAR_FIRST_SMALLEST (0) or PCP_VAR_INPUT_ORDER (1)");
+    c->opt_var_select = value;
   } else if (k == "branch_reverse") {
     if (value < 0 || value > 1) return fail(c, PCP_ERR_ARG, "branch_reverse must be 0 or 1");
     c->opt_branch_reverse = value;
@@ -999,7 +1003,8 @@ static int32_t dfs_enqueue_steps(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n
     if (rc == PCP_OK) {
       hipError_t e = launch_dfs_step(c->n_vars, st->lb, st->ub, st->status, st->capacity, st->sp, st->stop,
                                      reinterpret_cast<unsigned long long*>(st->counters), st->first_solution, stop_on_solution,
-                                     (unsigned long long)node_limit, c->dfs_team_words ? c->d_team : nullptr, (uint32_t)c->dfs_team_words, stream);
+                                     (unsigned long long)node_limit, c->dfs_team_words ? c->d_team : nullptr, (uint32_t)c->dfs_team_words, (uint32_t)c->opt_var_select,
+                                     stream);
       if (e != hipSuccess) rc = hip_fail(c, e, "launch_dfs_step");
     }
   }
@@ -1044,6 +1049,7 @@ static int32_t forest_set_args(pcp_ctx* c, const char* who, const pcp_forest_sta
   a.n_steps = n_steps; a.stop_on_solution = stop_on_solution; a.node_limit = node_limit;
   a.stats = c->d_stats;
   a.val_mode = val;
+  a.var_select = (uint32_t)c->opt_var_select;
   if (obj) {
     a.stop_on_solution = 0; a.first_solution = nullptr; a.solution_flag = nullptr;
     a.obj_var = obj->var; a.obj_mode = obj->mode; a.obj_best = obj->best; a.tree_best = obj->tree_best; a.tree_row = obj->tree_row;
@@ -1197,6 +1203,8 @@ int32_t pcp_dfs_forest_device(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_tr
   if (!c || !st) return PCP_ERR_ARG;
   if (c->sink.lb) return refuse_sink(c, "pcp_dfs_forest_device", "the all-XNeqY forest does not write into it (pcp_dfs_forest_device_small takes an all-XNeqY store within its limits)");
   if (c->set_words) return fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device runs interval-mode models (sets: pcp_dfs_forest_device_set)");
+  if (c->opt_var_select != PCP_VAR_FIRST_SMALLEST)
+    return fail(c, PCP_ERR_UNSUPPORTED, "pcp_dfs_forest_device: option var_select = PCP_VAR_INPUT_ORDER is not served by the all-XNeqY in-kernel search (pcp_dfs_forest_device_small takes an all-XNeqY store within its limits)");
   if (!n_trees || !st->lb || !st->ub || !st->sp || !st->stop || !st->status || !st->counters || st->capacity < 2) return fail(c, PCP_ERR_ARG, "null buffer / no tree / capacity < 2");
   HIP_TRY(c, hipSetDevice(c->device));
   { const int32_t rcf = finalize_model(c); if (rcf) return rcf; }
@@ -1249,6 +1257,7 @@ static void fill_row_args(ModelDev& m, RowDfsArgs& d, const pcp_ctx* c, const pc
   d.violation = c->d_retry + 1; d.stats = c->d_stats;
   if (obj) { d.obj_var = obj->var; d.obj_mode = obj->mode; d.obj_best = obj->best; d.tree_best = obj->tree_best; d.tree_row = obj->tree_row; }
   if (ex) { d.path = ex->path; d.row_base = ex->row_base; d.row_excl = ex->row_excl; d.path_capacity = ex->path_capacity; d.val = ex->val; }
+  d.var_select = (uint32_t)c->opt_var_select;
   d.sink = c->sink;
 }
 
@@ -1358,7 +1367,7 @@ int32_t pcp_dfs_device(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_steps, ui
   const int64_t keep_path = c->opt_force_path;
   HIP_TRY(c, hipSetDevice(c->device));
   { const int32_t rcf = finalize_model(c); if (rcf) return rcf; }
-  if (!keep_path) {
+  if (!keep_path && c->opt_var_select == PCP_VAR_FIRST_SMALLEST) {  // (the in-kernel loop selects FirstSmallestVar only: InputOrder steps)
     // an all-XNeqY model: the whole loop — pop, propagate, count, branch — runs in ONE workgroup, n_steps nodes per launch
     // (neqfix_kernel<.., DFS>); a node is the lists of its assigned variables, there is no sweep to share out over the chip
     const int32_t rcn = launch_neq_dfs(c, st, 1u, n_steps, stop_on_solution, node_limit, reinterpret_cast<hipStream_t>(hip_stream));
@@ -1609,7 +1618,7 @@ int32_t pcp_branch_device_hint(pcp_ctx* c, uint32_t n_nodes, const int32_t* lb, 
   int32_t rc = ensure(c, c->d_child_base, c->cap_child_base, std::max<uint32_t>(n_nodes, 1));
   if (rc) return rc;
   if (n_nodes == 0) { HIP_TRY(c, hipMemsetAsync(counts, 0, 20, stream)); return PCP_OK; }
-  HIP_TRY(c, launch_branch(n_nodes, c->n_vars, active ? words : 0u, lb, ub, active, status, child_lb, child_ub, child_active, child_dirty, c->d_child_base, counts, (uint32_t)c->opt_branch_reverse, stream));
+  HIP_TRY(c, launch_branch(n_nodes, c->n_vars, active ? words : 0u, lb, ub, active, status, child_lb, child_ub, child_active, child_dirty, c->d_child_base, counts, (uint32_t)c->opt_branch_reverse, (uint32_t)c->opt_var_select, stream));
   return PCP_OK;
 }
 
@@ -1617,6 +1626,8 @@ int32_t pcp_branch_device_cells(pcp_ctx* c, uint32_t n_nodes, const uint32_t* ce
                                 uint32_t* counts, void* hip_stream) {
   if (!c || !counts) return PCP_ERR_ARG;
   if (c->set_words) return fail(c, PCP_ERR_UNSUPPORTED, "pcp_branch_device_cells: interval mode only");
+  if (c->opt_var_select != PCP_VAR_FIRST_SMALLEST)
+    return fail(c, PCP_ERR_UNSUPPORTED, "pcp_branch_device_cells: option var_select = PCP_VAR_INPUT_ORDER is not served by the packed-cell brancher (pcp_branch_device_hint is)");
   hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
   HIP_TRY(c, hipSetDevice(c->device));
   if (n_nodes && (!status || (c->n_vars && (!cells || !child_cells)))) return fail(c, PCP_ERR_ARG, "null buffer");
@@ -1642,7 +1653,7 @@ int32_t pcp_branch_device_set(pcp_ctx* c, uint32_t n_nodes, const uint64_t* bits
   if (rc) return rc;
   if (n_nodes == 0) { HIP_TRY(c, hipMemsetAsync(counts, 0, 20, stream)); return PCP_OK; }
   HIP_TRY(c, launch_set_branch(n_nodes, c->n_vars, c->set_words, c->hull_lo, active ? words : 0u, bits, lb, ub, active, status, child_bits, child_active,
-                               c->d_child_base, counts, (uint32_t)c->opt_branch_reverse, stream));
+                               c->d_child_base, counts, (uint32_t)c->opt_branch_reverse, (uint32_t)c->opt_var_select, stream));
   return PCP_OK;
 }
 
@@ -1663,7 +1674,7 @@ int32_t pcp_branch_device_set_enum(pcp_ctx* c, uint32_t n_nodes, const uint64_t*
   HIP_TRY(c, hipMemsetAsync(counts, 0, 8 * sizeof(uint32_t), stream));
   if (n_nodes == 0) return PCP_OK;
   HIP_TRY(c, launch_set_branch_enum(n_nodes, c->n_vars, c->set_words, c->hull_lo, active ? words : 0u, bits, lb, ub, active, status, val, child_bits, child_active,
-                                    c->d_child_base, counts, (uint32_t)c->opt_branch_reverse, stream));
+                                    c->d_child_base, counts, (uint32_t)c->opt_branch_reverse, (uint32_t)c->opt_var_select, stream));
   return PCP_OK;
 }
 
@@ -1688,7 +1699,7 @@ int32_t pcp_branch_device_excl(pcp_ctx* c, uint32_t n_nodes, const int32_t* lb, 
   HIP_TRY(c, hipMemsetAsync(counts, 0, 8 * sizeof(uint32_t), stream));
   HIP_TRY(c, launch_branch_scan(n_nodes, status, c->d_child_base, counts, stream));
   HIP_TRY(c, launch_enum_branch(n_nodes, c->n_vars, lb, ub, c->d_child_base, excl_off, excl, val, c->d_enum_pick, c->d_enum_cnt, child_lb, child_ub,
-                                child_dirty, child_excl_off, child_excl, child_excl_capacity, counts, (uint32_t)c->opt_branch_reverse, stream));
+                                child_dirty, child_excl_off, child_excl, child_excl_capacity, counts, (uint32_t)c->opt_branch_reverse, (uint32_t)c->opt_var_select, stream));
   return PCP_OK;
 }
 

@@ -47,7 +47,7 @@ __device__ __forceinline__ int32_t enum_right_ub(int32_t lo, int32_t hi, int32_t
 __global__ void __launch_bounds__(kEnumBlock) enum_select_kernel(uint32_t n_vars, const int32_t* __restrict__ lb, const int32_t* __restrict__ ub,
                                                                  const uint32_t* __restrict__ child_base, const uint32_t* __restrict__ excl_off,
                                                                  const pcp_excl* __restrict__ excl, uint32_t val_mode, uint2* __restrict__ pick,
-                                                                 uint32_t* __restrict__ cnt, uint32_t* __restrict__ counts) {
+                                                                 uint32_t* __restrict__ cnt, uint32_t* __restrict__ counts, uint32_t var_select) {
   const uint32_t node = blockIdx.x, tid = threadIdx.x;
   const uint32_t slot = child_base[node];
   if (slot == kNoVar) return;  // not Unknown: nothing to branch on
@@ -56,11 +56,13 @@ __global__ void __launch_bounds__(kEnumBlock) enum_select_kernel(uint32_t n_vars
   __shared__ uint32_t shc[2][kEnumWaves];
   const int32_t* plb = lb + (size_t)node * n_vars;
   const int32_t* pub = ub + (size_t)node * n_vars;
-  // FirstSmallestVar: minimum of (size << 32 | index) over the variables of size > 1 (first index wins ties), sizes in 64 bits
+  // FirstSmallestVar: minimum of (size << 32 | index) over the variables of size > 1 (first index wins ties), sizes in 64 bits; InputOrder
+  // (input_order.rs:30-39): minimum of the index
+  const uint32_t size_mask = var_size_mask(var_select);
   unsigned long long key = ~0ull;
   for (uint32_t i = tid; i < n_vars; i += kEnumBlock) {
     const unsigned long long size = (unsigned long long)((long long)pub[i] - (long long)plb[i] + 1);
-    if (size > 1) key = min(key, (size << 32) | i);
+    if (size > 1) key = min(key, var_key(size, i, size_mask));
   }
   key = block_min_u64(key, sh64);
   if (key == ~0ull) {
@@ -239,8 +241,8 @@ __global__ void __launch_bounds__(kEnumBlock) enum_write_kernel(uint32_t n_vars,
 hipError_t launch_enum_branch(uint32_t n_nodes, uint32_t n_vars, const int32_t* lb, const int32_t* ub, const uint32_t* child_base, const uint32_t* excl_off,
                               const pcp_excl* excl, uint32_t val, uint2* pick, uint32_t* cnt, int32_t* child_lb, int32_t* child_ub, uint32_t* child_dirty,
                               uint32_t* child_excl_off, pcp_excl* child_excl, uint32_t child_excl_capacity, uint32_t* counts, uint32_t reverse,
-                              hipStream_t stream) {
-  hipLaunchKernelGGL(enum_select_kernel, dim3(n_nodes), dim3(kEnumBlock), 0, stream, n_vars, lb, ub, child_base, excl_off, excl, val, pick, cnt, counts);
+                              uint32_t var_select, hipStream_t stream) {
+  hipLaunchKernelGGL(enum_select_kernel, dim3(n_nodes), dim3(kEnumBlock), 0, stream, n_vars, lb, ub, child_base, excl_off, excl, val, pick, cnt, counts, var_select);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(enum_offsets_kernel, dim3(1), dim3(1024), 0, stream, cnt, child_excl_off, child_excl_capacity, reverse, counts);

@@ -131,6 +131,7 @@ struct SetDfsArgs {
   uint32_t* solution_flag;
   pcp_stats* stats;
   uint32_t val_mode;              // the Enumerate loop only: PCP_VAL_MIDDLE / PCP_VAL_MIN
+  uint32_t var_select;            // PCP_VAR_FIRST_SMALLEST / PCP_VAR_INPUT_ORDER (option "var_select")
   // branch and bound only (setdfs_kernel<.., true>, pcp_dfs_forest_device_set_bnb)
   uint32_t obj_var, obj_mode;     // the objective variable, PCP_MINIMIZE / PCP_MAXIMIZE
   int32_t* obj_best;              // device int32[1]: the forest's incumbent
@@ -147,27 +148,27 @@ hipError_t launch_setdfs(const SetDfsArgs& a, bool enumerate, bool bnb, hipStrea
 hipError_t launch_setdfs_split(const SetDfsArgs& a, uint32_t n_pairs, const uint32_t* pairs, uint32_t* done, hipStream_t stream);
 
 hipError_t launch_branch_scan(uint32_t n_nodes, const uint8_t* status, uint32_t* child_base, uint32_t* counts, hipStream_t stream);
-// Set-mode branching: FirstSmallestVar by CARDINALITY, MiddleVal on the bounds, BinarySplit on the sets.
+// Set-mode branching: FirstSmallestVar by CARDINALITY (or InputOrder: the first variable of cardinality > 1), MiddleVal on the bounds, BinarySplit on the sets.
 hipError_t launch_set_branch(uint32_t n_nodes, uint32_t n_vars, uint32_t set_words, int32_t base, uint32_t words, const uint64_t* bits, const int32_t* lb,
                              const int32_t* ub, const uint64_t* active, const uint8_t* status, uint64_t* child_bits, uint64_t* child_active,
-                             uint32_t* child_base, uint32_t* counts, uint32_t reverse, hipStream_t stream);
+                             uint32_t* child_base, uint32_t* counts, uint32_t reverse, uint32_t var_select, hipStream_t stream);
 
 // Set-mode branching under Enumerate (pcp_branch_device_set_enum): the same variable, the member of its set nearest to MiddleVal's / MinVal's
 // value, children x = v / x != v folded into the set.  counts[6] = error (3: an Unknown node without a variable of cardinality > 1).
 hipError_t launch_set_branch_enum(uint32_t n_nodes, uint32_t n_vars, uint32_t set_words, int32_t base, uint32_t words, const uint64_t* bits, const int32_t* lb,
                                   const int32_t* ub, const uint64_t* active, const uint8_t* status, uint32_t val, uint64_t* child_bits, uint64_t* child_active,
-                                  uint32_t* child_base, uint32_t* counts, uint32_t reverse, hipStream_t stream);
+                                  uint32_t* child_base, uint32_t* counts, uint32_t reverse, uint32_t var_select, hipStream_t stream);
 
 // One step of the device-side DFS after the fixpoint of the top node: count it, branch it in place (right child over the parent's
 // row, left child on top) or pop it, keep the first solution.
 hipError_t launch_dfs_step(uint32_t n_vars, int32_t* lb, int32_t* ub, const uint8_t* status, uint32_t capacity, uint32_t* sp, uint32_t* stop,
                            unsigned long long* counters, int32_t* first_solution, uint32_t stop_on_solution, unsigned long long node_limit,
-                           uint32_t* team_scratch, uint32_t team_words, hipStream_t stream);
+                           uint32_t* team_scratch, uint32_t team_words, uint32_t var_select, hipStream_t stream);
 
-// On-device branching (FirstSmallestVar / MiddleVal / BinarySplit): scan of the Unknown flags, then one block per node.
+// On-device branching (FirstSmallestVar | InputOrder / MiddleVal / BinarySplit): scan of the Unknown flags, then one block per node.
 hipError_t launch_branch(uint32_t n_nodes, uint32_t n_vars, uint32_t words, const int32_t* lb, const int32_t* ub, const uint64_t* active,
                          const uint8_t* status, int32_t* child_lb, int32_t* child_ub, uint64_t* child_active, uint32_t* child_dirty, uint32_t* child_base,
-                         uint32_t* counts, uint32_t reverse, hipStream_t stream);
+                         uint32_t* counts, uint32_t reverse, uint32_t var_select, hipStream_t stream);
 
 // Enumerate on the device (pcp_enum.hip, pcp_branch_device_excl), behind launch_branch_scan: per Unknown node the variable, the value and the
 // number of entries each child keeps (pick [n_nodes], cnt [2 n_nodes]: context scratch), the offsets of the child rows' lists, then the rows
@@ -175,7 +176,7 @@ hipError_t launch_branch(uint32_t n_nodes, uint32_t n_vars, uint32_t words, cons
 hipError_t launch_enum_branch(uint32_t n_nodes, uint32_t n_vars, const int32_t* lb, const int32_t* ub, const uint32_t* child_base, const uint32_t* excl_off,
                               const pcp_excl* excl, uint32_t val, uint2* pick, uint32_t* cnt, int32_t* child_lb, int32_t* child_ub, uint32_t* child_dirty,
                               uint32_t* child_excl_off, pcp_excl* child_excl, uint32_t child_excl_capacity, uint32_t* counts, uint32_t reverse,
-                              hipStream_t stream);
+                              uint32_t var_select, hipStream_t stream);
 
 // Branch and bound (pcp_bnb.hip, pcp_propagate_device_bnb): the incumbent folded into each node's objective domain before the fixpoint
 // (empty[i] = 1: the fold would empty node i, its row is left as it was), then the empty nodes forced to PCP_FALSE and the best PCP_TRUE node
@@ -185,5 +186,14 @@ hipError_t launch_bnb_fold(uint32_t n_nodes, uint32_t n_vars, uint32_t var, uint
 hipError_t launch_bnb_reduce(uint32_t n_nodes, uint32_t n_vars, uint32_t var, uint32_t mode, const uint8_t* empty, uint8_t* status, const int32_t* lb_out,
                              const int32_t* ub_out, const uint64_t* bits_out, uint32_t set_words, int32_t* best, int32_t* best_lb, int32_t* best_ub,
                              uint64_t* best_bits, uint32_t* improved, hipStream_t stream);
+
+// The variable selector's key for variable v of `size` > 1 values; the minimum over a node's variables is the choice, ~0 = none is open.
+// FirstSmallestVar (first_smallest_var.rs:30-39) orders by (size, index); InputOrder (input_order.rs:30-39) by the index alone: the size
+// is masked out of the key (option "var_select", wave-uniform: size_mask = var_size_mask(var_select), one 32-bit scalar — the key's upper
+// half is the size's lower 32 bits, as `size << 32` always made it).
+static __device__ __forceinline__ uint32_t var_size_mask(uint32_t var_select) { return var_select == PCP_VAR_INPUT_ORDER ? 0u : ~0u; }
+static __device__ __forceinline__ unsigned long long var_key(unsigned long long size, uint32_t v, uint32_t size_mask) {
+  return ((unsigned long long)((uint32_t)size & size_mask) << 32) | v;
+}
 
 }  // namespace pcp

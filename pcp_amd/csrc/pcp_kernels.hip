@@ -2499,7 +2499,8 @@ __global__ void __launch_bounds__(1024) branch_scan_kernel(const uint8_t* __rest
 __global__ void __launch_bounds__(256) branch_kernel(uint32_t n_vars, uint32_t words, const int32_t* __restrict__ lb, const int32_t* __restrict__ ub,
                                                      const uint64_t* __restrict__ active, const uint32_t* __restrict__ child_base,
                                                      int32_t* __restrict__ child_lb, int32_t* __restrict__ child_ub, uint64_t* __restrict__ child_active,
-                                                     uint32_t* __restrict__ child_dirty, const uint32_t* __restrict__ counts, uint32_t reverse) {
+                                                     uint32_t* __restrict__ child_dirty, const uint32_t* __restrict__ counts, uint32_t reverse,
+                                                     uint32_t var_select) {
   const uint32_t node = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
   const uint32_t slot = child_base[node];
   if (slot == 0xFFFFFFFFu) return;  // not Unknown: nothing to branch on
@@ -2510,11 +2511,12 @@ __global__ void __launch_bounds__(256) branch_kernel(uint32_t n_vars, uint32_t w
   __shared__ unsigned long long best[4];
   const int32_t* plb = lb + (size_t)node * n_vars;
   const int32_t* pub = ub + (size_t)node * n_vars;
-  // FirstSmallestVar: minimum of (size << 32 | index) over the variables of size > 1 (first index wins ties)
+  // FirstSmallestVar: minimum of (size << 32 | index) over the variables of size > 1 (first index wins ties); InputOrder: of the index
+  const uint32_t size_mask = var_size_mask(var_select);
   unsigned long long key = ~0ull;
   for (uint32_t v = tid; v < n_vars; v += nth) {
     const unsigned long long size = (unsigned long long)((long long)pub[v] - (long long)plb[v] + 1);
-    if (size > 1) key = min(key, (size << 32) | v);
+    if (size > 1) key = min(key, var_key(size, v, size_mask));
   }
   for (int o = 32; o > 0; o >>= 1) key = min(key, (unsigned long long)__shfl_down(key, o));
   if ((tid & 63) == 0) best[tid >> 6] = key;
@@ -2559,7 +2561,7 @@ __global__ void __launch_bounds__(256) dfs_step_kernel(uint32_t V, int32_t* __re
                                                        uint32_t capacity, uint32_t* __restrict__ sp_ptr, uint32_t* __restrict__ stop,
                                                        unsigned long long* __restrict__ counters, int32_t* __restrict__ first_solution,
                                                        uint32_t stop_on_solution, unsigned long long node_limit,
-                                                       uint32_t* __restrict__ team_scratch, uint32_t team_words) {
+                                                       uint32_t* __restrict__ team_scratch, uint32_t team_words, uint32_t var_select) {
   const uint32_t tid = threadIdx.x, nth = blockDim.x;
   // the team kernel's per-node scratch (tickets, merged masks, counters) is handed back zeroed for the next step's launch
   for (uint32_t i = tid; i < team_words; i += nth) team_scratch[i] = 0;
@@ -2572,10 +2574,11 @@ __global__ void __launch_bounds__(256) dfs_step_kernel(uint32_t V, int32_t* __re
   __shared__ unsigned long long best[4];
   uint32_t new_sp = sp - 1;
   if (st == PCP_UNKNOWN) {
+    const uint32_t size_mask = var_size_mask(var_select);  // (InputOrder: the first open variable, input_order.rs:30-39)
     unsigned long long key = ~0ull;
     for (uint32_t v = tid; v < V; v += nth) {
       const unsigned long long size = (unsigned long long)((long long)pub[v] - (long long)plb[v] + 1);
-      if (size > 1) key = min(key, (size << 32) | v);
+      if (size > 1) key = min(key, var_key(size, v, size_mask));
     }
     for (int o = 32; o > 0; o >>= 1) key = min(key, (unsigned long long)__shfl_down(key, o));
     if ((tid & 63) == 0) best[tid >> 6] = key;
@@ -2634,9 +2637,9 @@ __global__ void __launch_bounds__(256) dfs_step_kernel(uint32_t V, int32_t* __re
 }
 hipError_t launch_dfs_step(uint32_t n_vars, int32_t* lb, int32_t* ub, const uint8_t* status, uint32_t capacity, uint32_t* sp, uint32_t* stop,
                            unsigned long long* counters, int32_t* first_solution, uint32_t stop_on_solution, unsigned long long node_limit,
-                           uint32_t* team_scratch, uint32_t team_words, hipStream_t stream) {
+                           uint32_t* team_scratch, uint32_t team_words, uint32_t var_select, hipStream_t stream) {
   hipLaunchKernelGGL(dfs_step_kernel, dim3(1), dim3(256), 0, stream, n_vars, lb, ub, status, capacity, sp, stop, counters, first_solution,
-                     stop_on_solution, node_limit, team_scratch, team_words);
+                     stop_on_solution, node_limit, team_scratch, team_words, var_select);
   return hipGetLastError();
 }
 
@@ -2650,12 +2653,12 @@ hipError_t launch_branch_scan(uint32_t n_nodes, const uint8_t* status, uint32_t*
 
 hipError_t launch_branch(uint32_t n_nodes, uint32_t n_vars, uint32_t words, const int32_t* lb, const int32_t* ub, const uint64_t* active,
                          const uint8_t* status, int32_t* child_lb, int32_t* child_ub, uint64_t* child_active, uint32_t* child_dirty, uint32_t* child_base,
-                         uint32_t* counts, uint32_t reverse, hipStream_t stream) {
+                         uint32_t* counts, uint32_t reverse, uint32_t var_select, hipStream_t stream) {
   hipError_t e = hipMemsetAsync(counts, 0, 5 * sizeof(uint32_t), stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(branch_scan_kernel, dim3(1), dim3(1024), 0, stream, status, n_nodes, child_base, counts);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(branch_kernel, dim3(n_nodes), dim3(256), 0, stream, n_vars, words, lb, ub, active, child_base, child_lb, child_ub, child_active, child_dirty, counts, reverse);
+  hipLaunchKernelGGL(branch_kernel, dim3(n_nodes), dim3(256), 0, stream, n_vars, words, lb, ub, active, child_base, child_lb, child_ub, child_active, child_dirty, counts, reverse, var_select);
   return hipGetLastError();
 }
 

@@ -156,6 +156,9 @@ struct RowDfsArgs {
   pcp_excl* row_excl;            // [n_trees][capacity]: the entry appended when the row is popped (var 0xFFFFFFFF: none)
   uint32_t path_capacity, val;   // PCP_VAL_MIDDLE / PCP_VAL_MIN
   SinkDev sink;                  // the context's solution sink (row_dfs<false, .., true>); sink.lb == null: none
+  uint32_t var_select;           // PCP_VAR_FIRST_SMALLEST / PCP_VAR_INPUT_ORDER (option "var_select"): read by the launchers, which choose the
+                                 // instantiation by it (row_dfs<.., INPUT_ORDER>); the kernels do not read it.  The last member: the kernel
+                                 // arguments in front of it keep their offsets
 };
 
 // The search loop over such a store on the device: the node being run in its tree's LDS slice (pcp_formdfs.hip).

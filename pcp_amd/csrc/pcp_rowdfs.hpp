@@ -67,7 +67,7 @@ __device__ __forceinline__ void flush_node_stats(pcp_stats* stats, uint32_t lane
   if (nodes) atomicAdd((unsigned long long*)&stats->nodes, (unsigned long long)nodes);
 }
 
-template <bool BNB, bool ENUM, bool SINK, class Node>
+template <bool BNB, bool ENUM, bool SINK, bool INPUT_ORDER, class Node>
 __device__ __forceinline__ void row_dfs(const RowDfsArgs& d, const uint32_t t, Node& node) {
   static_assert(!(BNB && SINK), "branch and bound keeps tree_row; its entries refuse a sink");
   const uint32_t lane = node.lane;
@@ -207,14 +207,15 @@ __device__ __forceinline__ void row_dfs(const RowDfsArgs& d, const uint32_t t, N
     }
 
     // ---- Consistency::consistency (store.rs:250-256): False if a propagate failed, True if no subscription remains, else Unknown; and the
-    //      key of FirstSmallestVar (first_smallest_var.rs:30-39): the smallest size > 1, the lowest index on a tie -------------------------
+    //      key of FirstSmallestVar (first_smallest_var.rs:30-39): the smallest size > 1, the lowest index on a tie — or, under InputOrder
+    //      (input_order.rs:30-39; INPUT_ORDER), the lowest index of size > 1: the key without the size -----------------------------------------
     bool emptied = false;
     unsigned long long key = ~0ull;
     for (uint32_t v = lane; v < V; v += 64) {
       const int2 c = dom[v];
       emptied |= -c.x > c.y;
       const unsigned long long size = (unsigned long long)((long long)c.y + (long long)c.x + 1);
-      if (size > 1) key = min(key, (size << 32) | v);
+      if (size > 1) key = min(key, INPUT_ORDER ? (unsigned long long)v : (size << 32) | v);
     }
     failed = failed || __ballot(emptied) != 0;
     // (ENUM: an exclusion that is not entailed keeps the node Unknown even when every unit is entailed)

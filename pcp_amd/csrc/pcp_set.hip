@@ -599,7 +599,7 @@ struct RecordNode {
     const bool failed = misc[S_FAIL] != 0;
     key = ~0ull;
     if (!failed) {
-      key = first_smallest_var(team, bits, a.m.n_vars, a.set_words);
+      key = first_smallest_var(team, bits, a.m.n_vars, a.set_words, a.var_select);
       const DM dm = dom(nxt);
       if (key != ~0ull) {
         const uint32_t u = (uint32_t)key, o0 = adjo[u], o1 = adjo[u + 1];
@@ -744,15 +744,16 @@ hipError_t launch_setfix(const ModelDev& m, uint32_t n_nodes, uint32_t set_words
 }
 
 // ------------------------------------------------------------------------------------------------
-// Brancher<FirstSmallestVar, MiddleVal, BinarySplit>::enter over FDSpace (search/branching/brancher.rs:52-71): the variable of
-// minimal CARDINALITY > 1, first index (first_smallest_var.rs:30-39 uses Domain::size()), the value (lower + upper) / 2
+// Brancher<FirstSmallestVar | InputOrder, MiddleVal, BinarySplit>::enter over FDSpace (search/branching/brancher.rs:52-71): the variable of
+// minimal CARDINALITY > 1, first index (first_smallest_var.rs:30-39 uses Domain::size()) or, under var_select = PCP_VAR_INPUT_ORDER, the
+// first variable of cardinality > 1 (input_order.rs:30-39), the value (lower + upper) / 2
 // (middle_val.rs:25-27), children `x <= v` / `x > v` (binary_split.rs:46-57) folded into the variable's set.
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) set_branch_kernel(uint32_t V, uint32_t sw, int32_t base, uint32_t words, const uint64_t* __restrict__ bits,
                                                          const int32_t* __restrict__ lb, const int32_t* __restrict__ ub,
                                                          const uint64_t* __restrict__ active, const uint32_t* __restrict__ child_base,
                                                          uint64_t* __restrict__ child_bits, uint64_t* __restrict__ child_active,
-                                                         const uint32_t* __restrict__ counts, uint32_t reverse) {
+                                                         const uint32_t* __restrict__ counts, uint32_t reverse, uint32_t var_select) {
   const uint32_t node = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
   const uint32_t slot = child_base[node];
   if (slot == 0xFFFFFFFFu) return;
@@ -760,11 +761,12 @@ __global__ void __launch_bounds__(256) set_branch_kernel(uint32_t V, uint32_t sw
   const uint32_t rowR = reverse ? rowL - 1 : slot + 1;
   __shared__ unsigned long long best[4];
   const uint64_t* pb = bits + (size_t)node * V * sw;
+  const uint32_t size_mask = var_size_mask(var_select);  // (InputOrder: the first variable of cardinality > 1)
   unsigned long long key = ~0ull;
   for (uint32_t v = tid; v < V; v += nth) {
     unsigned long long size = 0;
     for (uint32_t k = 0; k < sw; ++k) size += (unsigned long long)__popcll(pb[(size_t)v * sw + k]);
-    if (size > 1) key = min(key, (size << 32) | v);
+    if (size > 1) key = min(key, var_key(size, v, size_mask));
   }
   for (int o = 32; o > 0; o >>= 1) key = min(key, (unsigned long long)__shfl_down(key, o));
   if ((tid & 63) == 0) best[tid >> 6] = key;
@@ -799,11 +801,11 @@ __global__ void __launch_bounds__(256) set_branch_kernel(uint32_t V, uint32_t sw
 
 hipError_t launch_set_branch(uint32_t n_nodes, uint32_t n_vars, uint32_t set_words, int32_t base, uint32_t words, const uint64_t* bits, const int32_t* lb,
                              const int32_t* ub, const uint64_t* active, const uint8_t* status, uint64_t* child_bits, uint64_t* child_active,
-                             uint32_t* child_base, uint32_t* counts, uint32_t reverse, hipStream_t stream) {
+                             uint32_t* child_base, uint32_t* counts, uint32_t reverse, uint32_t var_select, hipStream_t stream) {
   hipError_t e = launch_branch_scan(n_nodes, status, child_base, counts, stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(set_branch_kernel, dim3(n_nodes), dim3(256), 0, stream, n_vars, set_words, base, words, bits, lb, ub, active, child_base, child_bits,
-                     child_active, counts, reverse);
+                     child_active, counts, reverse, var_select);
   return hipGetLastError();
 }
 
@@ -817,7 +819,7 @@ __global__ void __launch_bounds__(256) set_branch_enum_kernel(uint32_t V, uint32
                                                               const int32_t* __restrict__ lb, const int32_t* __restrict__ ub,
                                                               const uint64_t* __restrict__ active, const uint32_t* __restrict__ child_base,
                                                               uint32_t val_mode, uint64_t* __restrict__ child_bits, uint64_t* __restrict__ child_active,
-                                                              uint32_t* __restrict__ counts, uint32_t reverse) {
+                                                              uint32_t* __restrict__ counts, uint32_t reverse, uint32_t var_select) {
   const uint32_t node = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
   const uint32_t slot = child_base[node];
   if (slot == 0xFFFFFFFFu) return;
@@ -825,11 +827,12 @@ __global__ void __launch_bounds__(256) set_branch_enum_kernel(uint32_t V, uint32
   const uint32_t rowR = reverse ? rowL - 1 : slot + 1;
   __shared__ unsigned long long best[4], near[4];
   const uint64_t* pb = bits + (size_t)node * V * sw;
+  const uint32_t size_mask = var_size_mask(var_select);  // (InputOrder: the first variable of cardinality > 1)
   unsigned long long key = ~0ull;
   for (uint32_t v = tid; v < V; v += nth) {
     unsigned long long size = 0;
     for (uint32_t k = 0; k < sw; ++k) size += (unsigned long long)__popcll(pb[(size_t)v * sw + k]);
-    if (size > 1) key = min(key, (size << 32) | v);
+    if (size > 1) key = min(key, var_key(size, v, size_mask));
   }
   for (int o = 32; o > 0; o >>= 1) key = min(key, (unsigned long long)__shfl_down(key, o));
   if ((tid & 63) == 0) best[tid >> 6] = key;
@@ -877,11 +880,11 @@ __global__ void __launch_bounds__(256) set_branch_enum_kernel(uint32_t V, uint32
 
 hipError_t launch_set_branch_enum(uint32_t n_nodes, uint32_t n_vars, uint32_t set_words, int32_t base, uint32_t words, const uint64_t* bits, const int32_t* lb,
                                   const int32_t* ub, const uint64_t* active, const uint8_t* status, uint32_t val, uint64_t* child_bits, uint64_t* child_active,
-                                  uint32_t* child_base, uint32_t* counts, uint32_t reverse, hipStream_t stream) {
+                                  uint32_t* child_base, uint32_t* counts, uint32_t reverse, uint32_t var_select, hipStream_t stream) {
   hipError_t e = launch_branch_scan(n_nodes, status, child_base, counts, stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(set_branch_enum_kernel, dim3(n_nodes), dim3(256), 0, stream, n_vars, set_words, base, words, bits, lb, ub, active, child_base, val,
-                     child_bits, child_active, counts, reverse);
+                     child_bits, child_active, counts, reverse, var_select);
   return hipGetLastError();
 }
 

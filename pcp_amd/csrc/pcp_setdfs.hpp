@@ -39,7 +39,7 @@
 //   load(gbits)            the tree's node into LDS, masks and misc zeroed, synchronised
 //   begin(pending)         launch start, after S_TRAILLEN is set and before the fold;  begun(): after the fold and its sync
 //   propagate(pending)     to the fixpoint or the failure; returns whether the rounds ran away
-//   status()               {failed, open} (store.rs:250-256), synchronised;  branch_key(): FirstSmallestVar's key for an open node
+//   status()               {failed, open} (store.rs:250-256), synchronised;  branch_key(): the variable selector's key for an open node
 //   backtracking()         before the trail and the levels are read back;
 //   backtracked()          after the bounds of the touched variables, before the synchronisation that precedes the right branch
 //   end_node()             before the synchronisation that ends a node
@@ -113,14 +113,16 @@ __device__ __forceinline__ void copy_node(const Team& team, unsigned long long* 
 }
 
 // FirstSmallestVar on sets: the variable of minimal CARDINALITY > 1, first index (first_smallest_var.rs:30-39 on Domain::size()) — a
-// popcount per variable, a minimum over the key size << 32 | v.  ~0: every variable is assigned.
+// popcount per variable, a minimum over the key size << 32 | v.  ~0: every variable is assigned.  Under InputOrder (var_select, wave-uniform;
+// input_order.rs:30-39) the first variable of cardinality > 1: the same minimum with the size masked out of the key.
 template <class Team>
-__device__ __forceinline__ unsigned long long first_smallest_var(const Team& team, const unsigned long long* bits, uint32_t V, uint32_t sw) {
+__device__ __forceinline__ unsigned long long first_smallest_var(const Team& team, const unsigned long long* bits, uint32_t V, uint32_t sw, uint32_t var_select) {
+  const uint32_t size_mask = var_size_mask(var_select);
   unsigned long long key = ~0ull;
   for (uint32_t v = team.rank; v < V; v += team.size) {
     unsigned long long size = 0;
     for (uint32_t k = 0; k < sw; ++k) size += (unsigned long long)__popcll(bits[(size_t)v * sw + k]);
-    if (size > 1) key = min(key, (size << 32) | v);
+    if (size > 1) key = min(key, var_key(size, v, size_mask));
   }
   for (int o = 32; o > 0; o >>= 1) key = min(key, (unsigned long long)__shfl_xor(key, o));
   return team.min_of_waves(key);
@@ -241,7 +243,7 @@ __device__ __forceinline__ void trail_dfs(const SetDfsArgs& a, const uint32_t t,
       }
       if (a.stop_on_solution && team.leader()) atomicExch(a.stop, 1u);
     } else {
-      // Brancher<FirstSmallestVar, MiddleVal | MinVal, BinarySplit | Enumerate>::enter on sets
+      // Brancher<FirstSmallestVar | InputOrder, MiddleVal | MinVal, BinarySplit | Enumerate>::enter on sets
       const unsigned long long key = node.branch_key();
       if (key == ~0ull) { c_err = 3; --c_nodes; if (team.leader()) atomicAdd(a.total_nodes, ~0ull); break; }  // Unknown, yet nothing to branch on: the reference panics
       if (n_levels >= a.level_cap) { c_err = 1; --c_nodes; pending = kDfsFull; if (team.leader()) atomicAdd(a.total_nodes, ~0ull); break; }

@@ -129,7 +129,7 @@ struct FormulaNode {
     return NodeStatus{failed, open};
   }
   // (a solution node does not pay for the key: only the branch asks for it)
-  __device__ __forceinline__ unsigned long long branch_key() const { return first_smallest_var(team, bits, fa.d.m.n_vars, fa.d.set_words); }
+  __device__ __forceinline__ unsigned long long branch_key() const { return first_smallest_var(team, bits, fa.d.m.n_vars, fa.d.set_words, fa.d.var_select); }
   __device__ __forceinline__ void backtracking() { team.sync(); }  // (this wavefront's trail and level entries, written by other lanes)
   __device__ __forceinline__ void backtracked() {
     clear_marks();     // (a failed node leaves marks behind; every narrowed variable is a touched one)

@@ -72,7 +72,7 @@ struct SmallNode {
   __device__ __forceinline__ void flush_stats(pcp_stats* stats) const { flush_node_stats(stats, lane, steps2, steps3, ctr.narrow, acc_rounds, acc_nodes); }
 };
 
-template <bool BNB, bool ENUM, bool SINK>
+template <bool BNB, bool ENUM, bool SINK, bool INPUT_ORDER>
 __global__ void __launch_bounds__(256) smalldfs_kernel(const SmallDfsArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwv = blockDim.x >> 6;
@@ -82,17 +82,26 @@ __global__ void __launch_bounds__(256) smalldfs_kernel(const SmallDfsArgs a) {
   __syncthreads();
   Ctr ctr;
   SmallNode node(a, sh, small_slice(smem, a.m.n_recs, a.m.n_slots, a.n_units, wv), ctr);
-  row_dfs<BNB, ENUM, SINK>(a.d, blockIdx.x * nwv + wv, node);
+  row_dfs<BNB, ENUM, SINK, INPUT_ORDER>(a.d, blockIdx.x * nwv + wv, node);
 }
 
-template <bool BNB, bool ENUM, bool SINK>
-hipError_t launch_smalldfs_as(const SmallDfsArgs& a, const LaunchPlan& p, hipStream_t stream) {
+template <bool BNB, bool ENUM, bool SINK, bool INPUT_ORDER>
+hipError_t launch_smalldfs_io(const SmallDfsArgs& a, const LaunchPlan& p, hipStream_t stream) {
   hipError_t e;
   if (p.lds_bytes > 64 * 1024 &&
-      (e = hipFuncSetAttribute(reinterpret_cast<const void*>(smalldfs_kernel<BNB, ENUM, SINK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes)) != hipSuccess)
+      (e = hipFuncSetAttribute(reinterpret_cast<const void*>(smalldfs_kernel<BNB, ENUM, SINK, INPUT_ORDER>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes)) != hipSuccess)
     return e;
-  hipLaunchKernelGGL((smalldfs_kernel<BNB, ENUM, SINK>), dim3(p.grid), dim3(p.block), p.lds_bytes, stream, a);
+  hipLaunchKernelGGL((smalldfs_kernel<BNB, ENUM, SINK, INPUT_ORDER>), dim3(p.grid), dim3(p.block), p.lds_bytes, stream, a);
   return hipGetLastError();
+}
+
+// The variable selector (option "var_select", a.d.var_select) is a template flag here, not a run-time mask on the key as in the other
+// branchers: these kernels have no scalar register to spare (over 100 SGPR spills each), and one more live scalar moved the default path's
+// spills — up to 2.5 % on the small-store forest (profiles/var_select_measured.jsonl).  FirstSmallestVar's instantiations are the code
+// they were.
+template <bool BNB, bool ENUM, bool SINK>
+hipError_t launch_smalldfs_as(const SmallDfsArgs& a, const LaunchPlan& p, hipStream_t stream) {
+  return a.d.var_select == PCP_VAR_INPUT_ORDER ? launch_smalldfs_io<BNB, ENUM, SINK, true>(a, p, stream) : launch_smalldfs_io<BNB, ENUM, SINK, false>(a, p, stream);
 }
 
 }  // namespace

@@ -7,7 +7,10 @@ PyTorch is used only as plumbing (device buffers, streams); the ABI itself takes
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import functools
+import inspect
 import os
 from typing import Optional
 
@@ -254,6 +257,61 @@ def _objective_struct(objective):
     return Objective(int(g("var")), int(OBJ_MODES.get(g("mode"), g("mode"))), _ptr(g("best")), _ptr(g("best_lb")), _ptr(g("best_ub")), _ptr(g("best_bits")),
                      _ptr(g("improved")), 0)
 
+VAR_SELECTS = {"first_smallest": 0, "input_order": 1}  # PCP_VAR_FIRST_SMALLEST / PCP_VAR_INPUT_ORDER: option "var_select" (Context.var_select)
+
+
+@contextlib.contextmanager
+def var_select_scope(ctx, var_select):
+    """``ctx.var_select = var_select`` for the duration of the block, the value before restored afterwards — also when the block raises.
+    None: the context is not touched at all (no attribute is read, no option set)."""
+    if var_select is None:
+        yield
+        return
+    if var_select not in VAR_SELECTS:
+        raise ValueError(f"var_select must be 'first_smallest' or 'input_order', not {var_select!r}")
+    before = ctx.var_select
+    ctx.var_select = var_select
+    try:
+        yield
+    finally:
+        ctx.var_select = before
+
+
+def scoped_var_select(refuse=None):
+    """A search driver whose first argument is the context gains the keyword ``var_select=None``: None leaves the context untouched; a name
+    of VAR_SELECTS is the context's variable selector for the call (var_select_scope).  ``refuse(arguments)``: a message when the call, as
+    bound to the driver's parameters, goes to an entry that selects FirstSmallestVar only — under "input_order" a ValueError."""
+    def deco(fn):
+        sig = inspect.signature(fn)
+
+        @functools.wraps(fn)
+        def driver(ctx, *args, var_select=None, **kw):
+            if var_select is None:
+                return fn(ctx, *args, **kw)
+            if var_select not in VAR_SELECTS:
+                raise ValueError(f"{fn.__name__}: var_select must be 'first_smallest' or 'input_order', not {var_select!r}")
+            if refuse is not None and var_select == "input_order":
+                bound = sig.bind(ctx, *args, **kw)
+                bound.apply_defaults()
+                why = refuse(bound.arguments)
+                if why:
+                    raise ValueError(f"{fn.__name__}: var_select='input_order' {why}")
+            with var_select_scope(ctx, var_select):
+                return fn(ctx, *args, **kw)
+        driver.__doc__ = (fn.__doc__ or "") + """
+        ``var_select`` (keyword; None = the context is left as it is): "first_smallest" or "input_order" — the context's variable selector
+        (Context.var_select, option "var_select") for this call, the value before restored afterwards, also when the call raises."""
+        return driver
+    return deco
+
+
+def _xneq_forest(a) -> str:
+    """The refusal of dfs_forest / forest_search under InputOrder: neither ``formulas`` nor ``small`` (nor the Enumerate forest chosen by the
+    store) is the all-XNeqY in-kernel forest, pcp_dfs_forest_device."""
+    if a.get("formulas") or a.get("small") or a.get("_call") is not None or a.get("_enum_entry") is not None or a.get("_by_store") is not None:
+        return ""
+    return "is not served by the all-XNeqY forest (pcp_dfs_forest_device selects FirstSmallestVar only): small=True runs an all-XNeqY store within the small-store limits"
+
 
 class Context:
     """One pcp_ctx == one constraint store (CStore) on one GPU."""
@@ -271,6 +329,7 @@ class Context:
         self.n_vars = 0
         self.n_units = 0
         self.set_words = 0
+        self._var_select = "first_smallest"
         self.supports_hints = True  # pcp_device_batch.dirty_var / pcp_branch_device_hint (ABI v7): search drivers keep a hint per open node
         self.supports_set_enumerate = True  # pcp_branch_device_set_enum / pcp_dfs_forest_device_set_enum: Enumerate over set-mode stores
         self._neq_flags = []  # per elementary filter pushed: an XNeqY outside a formula with a variable among its operands (all_neq)
@@ -369,6 +428,21 @@ class Context:
 
     def set_option(self, key: str, value: int):
         self._check(self._L.pcp_set_option(self._h, key.encode(), int(value)))
+        if key == "var_select":
+            self._var_select = next(k for k, v in VAR_SELECTS.items() if v == int(value))
+
+    @property
+    def var_select(self) -> str:
+        """The variable selector of every device brancher and search loop (option "var_select"): "first_smallest" (FirstSmallestVar, the
+        default) or "input_order" (InputOrder, input_order.rs:30-39: the first variable in store order whose size is > 1).  Under
+        "input_order" pcp_dfs_forest_device (the all-XNeqY in-kernel forest) and pcp_branch_device_cells (packed cells) refuse to run."""
+        return self._var_select
+
+    @var_select.setter
+    def var_select(self, name: str):
+        if name not in VAR_SELECTS:
+            raise ValueError(f"var_select must be 'first_smallest' or 'input_order', not {name!r}")
+        self.set_option("var_select", VAR_SELECTS[name])
 
     # ---- propagation, host buffers (pcp_propagate) ----------------------------------------------------------
     def propagate_set(self, bits, active: Optional[np.ndarray] = None, want_stats: bool = True):
@@ -577,6 +651,7 @@ class Context:
         st = sink.struct() if isinstance(sink, SolutionSink) else sink
         self._check(self._L.pcp_solution_sink_set(self._h, None if st is None else C.byref(st)))
 
+    @scoped_var_select(refuse=_xneq_forest)
     def dfs_forest(self, root_lb, root_ub, stop_on_solution: bool = False, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
                    max_launches: int = 1 << 30, node_budget: int = 0, want_solution: bool = False, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
                    sp0=None, hints: bool = True, formulas: bool = False, small: bool = False, _call=None, brancher: str = "split", val: str = "middle",
@@ -701,6 +776,7 @@ class Context:
             out["solutions_lb"], out["solutions_ub"], out["solution_tree"] = sink.rows()
         return out
 
+    @scoped_var_select()
     def dfs_forest_bnb(self, root_lb, root_ub, objective, best0=None, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
                        max_launches: int = 1 << 30, node_budget: int = 0, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
                        sp0=None, small: bool = False, brancher: str = "split", val: str = "middle", root_excl=None, path_capacity: int = 64,
@@ -744,6 +820,7 @@ class Context:
         out["best_solution"] = tree_row[int(winners[0])].cpu().numpy() if len(winners) else None
         return out
 
+    @scoped_var_select()
     def dfs_forest_enum(self, root_lb, root_ub, val: str = "middle", objective=None, best0=None, root_excl=None, path_capacity: int = 64, max_path: int = 1 << 20,
                         collect_solutions: bool = False, sink_capacity: int = 4096, stop_on_solution: bool = False, node_limit_per_tree: int = 0,
                         steps_per_launch: int = 256, capacity: int = 2048, max_launches: int = 1 << 30, node_budget: int = 0, want_solution: bool = False,
@@ -773,6 +850,7 @@ class Context:
         return self.dfs_forest(root_lb, root_ub, stop_on_solution=stop_on_solution, want_solution=want_solution, formulas=form,
                                collect_solutions=collect_solutions, sink_capacity=sink_capacity, **kw)
 
+    @scoped_var_select()
     def dfs_forest_set(self, root_bits, stop_on_solution: bool = False, node_limit: int = 0, steps_per_launch: int = 256,
                        level_capacity: int = 0, trail_capacity: int = 0, max_launches: int = 1 << 30, want_solution: bool = True,
                        info: dict | None = None, rebalance: bool = True, brancher: str = "split", val: str = "middle"):
@@ -792,6 +870,7 @@ class Context:
         return self._run_forest_set(root_bits, launch, node_limit=node_limit, steps_per_launch=steps_per_launch, level_capacity=level_capacity,
                                     trail_capacity=trail_capacity, max_launches=max_launches, want_solution=want_solution, info=info, rebalance=rebalance)
 
+    @scoped_var_select()
     def dfs_forest_setform(self, root_bits, stop_on_solution: bool = False, node_limit: int = 0, steps_per_launch: int = 256,
                            level_capacity: int = 0, trail_capacity: int = 0, max_launches: int = 1 << 30, want_solution: bool = True,
                            info: dict | None = None, rebalance: bool = True, brancher: str = "split", val: str = "middle"):
@@ -872,6 +951,7 @@ class Context:
                 "finished_trees": int((tree[:, 3] & 1).sum().item()), "splits": splits, "stopped": bool(g[1] & 0xFFFFFFFF), "launches": launches, "total_nodes": int(g[0]),
                 "first_solution": sol.cpu().numpy() if (want_solution and (g[2] & 0xFFFFFFFF)) else None, "per_tree": cn}
 
+    @scoped_var_select()
     def dfs_forest_set_bnb(self, root_bits, objective, live=None, best0=None, brancher: str = "split", val: str = "middle", steps_per_launch: int = 256,
                            node_limit: int = 0, level_capacity: int = 0, trail_capacity: int = 0, rebalance: bool = True, info: dict | None = None,
                            ramp_steps: int = 0, max_launches: int = 1 << 30, _entry: str = "pcp_dfs_forest_device_set_bnb"):
@@ -911,6 +991,7 @@ class Context:
         out["best_solution"] = tree_row[int(winners[0])].cpu().numpy() if len(winners) else None
         return out
 
+    @scoped_var_select()
     def dfs_forest_setform_bnb(self, root_bits, objective, **kw):
         """pcp_dfs_forest_device_setform_bnb: dfs_forest_set_bnb for a store WITH formula propagators (see dfs_forest_setform) — the same
         arguments and result dict."""

@@ -605,3 +605,28 @@ def golomb_ruler(m: int = 10, length: int = 80):
     objective variable, the last mark (index m - 1), to be minimised (search.dfs / DeviceSearch with objective=(var, "min"))."""
     vs, cs = golomb(m, length)
     return vs, cs, m - 1
+
+
+def robot_scheduling(num_robot: int, max_time: int):
+    """example/src/robot.rs:108-169 with Interval<i32> domains: per robot five task starts (Loading, Take, Wait, Put, End) in [1, max_time]
+    and four durations (10-15, 25-35, 240-250, 25-35), start[t + 1] >= start[t] + duration[t]; the first robot's first start is 1; ONE
+    Cumulative over the Loading and Put tasks of every robot with Constant(1) resources and capacity 1 (the pipetting station takes one
+    task at a time).  Variable allocation order is the reference's — per robot the starts, then the durations, and behind all robots what
+    Cumulative.join allocates: the reference searches this model under Brancher<InputOrder, MinVal, Enumerate> (robot.rs:176), which makes
+    the order part of the model.  Returns (vstore, cstore, starts, durations): the index lists, robot-major (starts[5 i + t],
+    durations[4 i + t])."""
+    tasks, dtasks, cumul_tasks = 5, 4, (0, 3)  # L, T, W, P, E; Loading and Put use the pipetting station
+    dur = [(10, 15), (25, 35), (240, 250), (25, 35)]
+    vs, cs = VStore(), CStore()
+    start, duration, p_start, p_duration = [], [], [], []
+    for i in range(num_robot):
+        start += [vs.alloc((1, max_time)) for _ in range(tasks)]
+        duration += [vs.alloc(dur[t]) for t in range(dtasks)]
+        for t in cumul_tasks:
+            p_start.append(start[i * tasks + t])
+            p_duration.append(duration[i * dtasks + t])
+        for t in range(dtasks):  # every task starts after the end of the one before: S' >= S + D
+            cs.alloc(x_geq_y_plus_z(start[i * tasks + t + 1], start[i * tasks + t], duration[i * dtasks + t]))
+    cs.alloc(XEqY(start[0], Constant(1)))  # the first robot starts first
+    Cumulative(p_start, p_duration, [Constant(1)] * (2 * num_robot), Constant(1)).join(vs, cs)
+    return vs, cs, [v.idx for v in start], [v.idx for v in duration]

@@ -42,16 +42,55 @@ def first_smallest_var(lb: np.ndarray, ub: np.ndarray) -> np.ndarray:
     return np.where(none, -1, idx)
 
 
+def input_order(lb: np.ndarray, ub: np.ndarray) -> np.ndarray:
+    """Row-wise InputOrder (search/branching/input_order.rs:30-39): the first variable in store order whose size is > 1.  Rows where every
+    variable is assigned return -1 (the reference panics, input_order.rs:37)."""
+    return _first_open(ub.astype(np.int64) - lb.astype(np.int64) + 1)
+
+
+def input_order_set(bits: np.ndarray) -> np.ndarray:
+    """InputOrder on sets (bits: [n, V, set_words]): the first variable of CARDINALITY > 1; -1 where there is none."""
+    return _first_open(_popcount64(bits).sum(axis=2))
+
+
+def _first_open(size: np.ndarray) -> np.ndarray:
+    size = size.reshape(1, -1) if size.ndim == 1 else size
+    open_ = size > 1
+    return np.where(open_.any(axis=1), open_.argmax(axis=1), -1)  # argmax: the FIRST True
+
+
+VAR_SELECTORS = ("first_smallest", "input_order")
+
+
+def _check_var_select(var_select: str) -> str:
+    if var_select not in VAR_SELECTORS:
+        raise ValueError(f"var_select must be 'first_smallest' or 'input_order', not {var_select!r}")
+    return var_select
+
+
+def select_var(lb: np.ndarray, ub: np.ndarray, var_select: str = "first_smallest") -> np.ndarray:
+    """The variable selector by name on Interval rows: first_smallest_var or input_order."""
+    return (input_order if _check_var_select(var_select) == "input_order" else first_smallest_var)(lb, ub)
+
+
+def select_var_set(bits: np.ndarray, var_select: str = "first_smallest") -> np.ndarray:
+    """The variable selector by name on set-mode rows, sizes being cardinalities; -1 where every variable is assigned."""
+    if _check_var_select(var_select) == "input_order":
+        return input_order_set(bits)
+    size = _popcount64(bits).sum(axis=2)
+    return first_smallest_var(np.ones_like(size), size)  # (FirstSmallestVar on sizes: ub - lb + 1 = the cardinality)
+
+
 def middle_val(lb: np.ndarray, ub: np.ndarray) -> np.ndarray:
     s = lb.astype(np.int64) + ub.astype(np.int64)
     return (np.sign(s) * (np.abs(s) // 2)).astype(np.int32)  # Rust `/` truncates toward zero
 
 
-def branch(lb: np.ndarray, ub: np.ndarray, active: Optional[np.ndarray]):
+def branch(lb: np.ndarray, ub: np.ndarray, active: Optional[np.ndarray], var_select: str = "first_smallest"):
     """BinarySplit children of each (Unknown) row, folded: returns (lb2, ub2, active2) with 2 rows per input row,
-    ordered left child then right child."""
+    ordered left child then right child.  ``var_select``: FirstSmallestVar's variable or InputOrder's."""
     n = lb.shape[0]
-    var = first_smallest_var(lb, ub)
+    var = select_var(lb, ub, var_select)
     if (var < 0).any():
         raise RuntimeError("Cannot select a variable in a space where all variables are assigned.")
     rows = np.arange(n)
@@ -184,8 +223,8 @@ def _search(kind, root, all_solutions: bool, node_limit: int, batch: int, obj=No
 class _IntervalRows:
     """A node is (lb, ub, active).  The incumbent is folded into the bounds; a node with lb > ub is failed without a launch."""
 
-    def __init__(self, ctx):
-        self.ctx = ctx
+    def __init__(self, ctx, var_select="first_smallest"):
+        self.ctx, self.var_select = ctx, _check_var_select(var_select)
 
     def propagate(self, st, take, obj):
         L, U, A = (np.stack(c) for c in zip(*take))
@@ -203,18 +242,21 @@ class _IntervalRows:
         return L, status, (L, U, A)
 
     def branch(self, done_batch, unk):
-        return list(zip(*branch(*(a[unk] for a in done_batch))))
+        return list(zip(*branch(*(a[unk] for a in done_batch), var_select=self.var_select)))
 
 
-def dfs(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = False, node_limit: int = 0, batch: int = 1, objective=None) -> SearchStats:
+def dfs(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = False, node_limit: int = 0, batch: int = 1, objective=None,
+        var_select: str = "first_smallest") -> SearchStats:
     """Depth-first search with a LIFO stack of open nodes (gcollections::VectorStack in the reference).  With
     ``batch=1`` the node order is exactly the reference's left-first DFS (one_solution.rs:46-51, 92-105); with
     ``batch>1`` the top ``batch`` open nodes are propagated in one launch (batched subtree propagation).
     ``objective=(var, "min" | "max")``: branch and bound on that variable (module docstring); the search runs to the end
-    whatever ``all_solutions`` says, and ``best`` / ``best_solution`` / ``incumbents`` of the result report it."""
+    whatever ``all_solutions`` says, and ``best`` / ``best_solution`` / ``incumbents`` of the result report it.
+    ``var_select="input_order"``: InputOrder instead of FirstSmallestVar (the host specification of option var_select of the device)."""
+    _check_var_select(var_select)
     obj = _objective(objective)
     root = (np.ascontiguousarray(lb0, np.int32), np.ascontiguousarray(ub0, np.int32), full_active(1, ctx.n_units)[0])
-    return _search(_IntervalRows(ctx), root, all_solutions, node_limit, batch, obj)
+    return _search(_IntervalRows(ctx, var_select), root, all_solutions, node_limit, batch, obj)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -292,8 +334,9 @@ class _ExclRows:
     The children of branch_enumerate are never empty; with an objective the incumbent is folded into the bounds here, as _IntervalRows does,
     and a node the fold empties is failed without a launch."""
 
-    def __init__(self, ctx, val, record, hints, small=False):
+    def __init__(self, ctx, val, record, hints, small=False, var_select="first_smallest"):
         import torch
+        self.var_select = _check_var_select(var_select)
         self.torch, self.ctx, self.val, self.record, self.hints, self.small = torch, ctx, val, record, hints, small
         self.form = bool(getattr(ctx, "has_formulas", False))  # a store with formula units: ctx.propagate_device_form_excl, whatever `small` says
         on_gpu = getattr(ctx, "device", 0) != "cpu"  # (the CPU tests drive this class with an oracle-backed stand-in context)
@@ -344,12 +387,13 @@ class _ExclRows:
         poff = np.zeros(len(unk) + 1, np.int64)
         poff[1:] = np.cumsum([len(take[u][2]) for u in unk])
         pex = np.concatenate([take[u][2] for u in unk]).reshape(-1, 2)
-        cl, cu, coff, cex, cd = branch_enumerate(lb[unk], ub[unk], poff, pex, val=self.val)
+        x = None if self.var_select == "first_smallest" else input_order(lb[unk], ub[unk])  # (-1: branch_enumerate raises)
+        cl, cu, coff, cex, cd = branch_enumerate(lb[unk], ub[unk], poff, pex, val=self.val, var=x)
         return [(cl[c], cu[c], cex[coff[c]:coff[c + 1]].copy(), int(cd[c])) for c in range(len(cl))]
 
 
 def dfs_enumerate(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = False, node_limit: int = 0, batch: int = 1, val: str = "middle",
-                  record: Optional[list] = None, hints: bool = True, objective=None) -> SearchStats:
+                  record: Optional[list] = None, hints: bool = True, objective=None, var_select: str = "first_smallest") -> SearchStats:
     """The batched host-stepped depth-first search of ``dfs`` under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>: the top
     ``batch`` open nodes go through ``ctx.propagate_device_excl`` in one launch, each with its own exclusions (and, with ``hints``, the
     variable it was branched on as its dirty-variable hint).  ``record``: a list that receives, per node in the order propagated,
@@ -360,10 +404,11 @@ def dfs_enumerate(ctx, lb0: np.ndarray, ub0: np.ndarray, all_solutions: bool = F
     with formula units, a schedule): then every launch is ``ctx.propagate_device_form_excl``.  The bound is folded into a node's bounds before
     its propagation exactly as under BinarySplit; this is the host specification of DeviceSearch(brancher="enumerate", objective=), so a
     batch is taken in the order of DeviceSearch's rows (``rows_up`` of _search): the same nodes, solutions, failures and incumbents at every
-    batch size."""
+    batch size.  ``var_select="input_order"``: Brancher<InputOrder, ..> — the brancher of the reference's scheduling examples with ``val="min"``."""
+    _check_var_select(var_select)
     obj = _objective(objective)
     small = obj is not None or not getattr(ctx, "all_neq", True)
-    kind, V = _ExclRows(ctx, val, record, hints, small), ctx.n_vars
+    kind, V = _ExclRows(ctx, val, record, hints, small, var_select), ctx.n_vars
     steps0 = ctx.stats_read(kind.stream)
     root = (np.ascontiguousarray(lb0, np.int32).reshape(V), np.ascontiguousarray(ub0, np.int32).reshape(V), np.zeros((0, 2), np.int32), -1)
     st = _search(kind, root, all_solutions, node_limit, batch, obj, rows_up=obj is not None)
@@ -386,17 +431,14 @@ def _popcount64(a: np.ndarray) -> np.ndarray:
     return ((a * np.uint64(0x0101010101010101)) >> np.uint64(56)).astype(np.int64)
 
 
-def branch_set(bits: np.ndarray, lb: np.ndarray, ub: np.ndarray, base: int, active: Optional[np.ndarray]):
+def branch_set(bits: np.ndarray, lb: np.ndarray, ub: np.ndarray, base: int, active: Optional[np.ndarray], var_select: str = "first_smallest"):
     """BinarySplit children of each (Unknown) set-mode row, folded into the sets: returns (bits2, active2), 2 rows per input
     row (left `x <= v`, then right `x > v`).  bits: [n, V, set_words]; lb/ub: the sets' bounds."""
     from .model import interval_bits
     n, V, sw = bits.shape
-    size = _popcount64(bits).sum(axis=2)
-    big = np.iinfo(np.int64).max
-    key = np.where(size > 1, size, big)
-    var = key.argmin(axis=1)
+    var = select_var_set(bits, var_select)
     rows = np.arange(n)
-    if (key[rows, var] == big).any():
+    if (var < 0).any():
         raise RuntimeError("Cannot select a variable in a space where all variables are assigned.")
     v = middle_val(lb[rows, var], ub[rows, var]).astype(np.int64)
     B = np.repeat(bits, 2, axis=0)
@@ -411,8 +453,8 @@ def branch_set(bits: np.ndarray, lb: np.ndarray, ub: np.ndarray, base: int, acti
 class _Sets:
     """A node is (bits, active or None).  The incumbent is folded through interval_bits; a node with an emptied set is failed without a launch."""
 
-    def __init__(self, ctx, base, implicit):
-        self.ctx, self.base, self.implicit = ctx, base, implicit
+    def __init__(self, ctx, base, implicit, var_select="first_smallest"):
+        self.ctx, self.base, self.implicit, self.var_select = ctx, base, implicit, _check_var_select(var_select)
 
     def propagate(self, st, take, obj):
         sw, base = self.ctx.set_words, self.base
@@ -435,18 +477,19 @@ class _Sets:
 
     def branch(self, done_batch, unk):
         Bt, lb, ub, A = done_batch
-        cb, ca = branch_set(Bt[unk], lb[unk], ub[unk], self.base, None if A is None else A[unk])
+        cb, ca = branch_set(Bt[unk], lb[unk], ub[unk], self.base, None if A is None else A[unk], var_select=self.var_select)
         return [(cb[c], None if ca is None else ca[c]) for c in range(len(cb))]
 
 
 def dfs_set(ctx, lb0: np.ndarray, ub0: np.ndarray, base: int, all_solutions: bool = False, node_limit: int = 0, batch: int = 1,
-            implicit: bool = True, objective=None) -> SearchStats:
+            implicit: bool = True, objective=None, var_select: str = "first_smallest") -> SearchStats:
     """Depth-first search over set-mode nodes (FDSpace): the variables are allocated as IntervalSet::new(lb0, ub0)
     (example/src/nqueens.rs:32-35); with batch = 1 the node order is the reference's left-first DFS.  ``objective``: as in dfs;
-    the bound clears the objective's values >= best (min) or <= best (max) from its set."""
+    the bound clears the objective's values >= best (min) or <= best (max) from its set.  ``var_select``: as in dfs, on cardinalities."""
+    _check_var_select(var_select)
     obj = _objective(objective)
     root = (interval_bits(np.asarray(lb0), np.asarray(ub0), ctx.set_words, base), None if implicit else full_active(1, ctx.n_units)[0])
-    return _search(_Sets(ctx, base, implicit), root, all_solutions, node_limit, batch, obj)
+    return _search(_Sets(ctx, base, implicit, var_select), root, all_solutions, node_limit, batch, obj)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -515,24 +558,28 @@ def branch_enumerate_set(bits: np.ndarray, lb: np.ndarray, ub: np.ndarray, base:
 class _SetsEnumerate(_Sets):
     """_Sets under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>."""
 
-    def __init__(self, ctx, base, implicit, val):
-        super().__init__(ctx, base, implicit)
+    def __init__(self, ctx, base, implicit, val, var_select="first_smallest"):
+        super().__init__(ctx, base, implicit, var_select)
         self.val = val
 
     def branch(self, done_batch, unk):
         Bt, lb, ub, A = done_batch
-        cb, ca = branch_enumerate_set(Bt[unk], lb[unk], ub[unk], self.base, None if A is None else A[unk], val=self.val)
+        x = None if self.var_select == "first_smallest" else input_order_set(Bt[unk])
+        if x is not None and (x < 0).any():
+            raise RuntimeError("Cannot select a variable in a space where all variables are assigned.")
+        cb, ca = branch_enumerate_set(Bt[unk], lb[unk], ub[unk], self.base, None if A is None else A[unk], val=self.val, var=x)
         return [(cb[c], None if ca is None else ca[c]) for c in range(len(cb))]
 
 
 def dfs_enumerate_set(ctx, lb0: np.ndarray, ub0: np.ndarray, base: int, all_solutions: bool = False, node_limit: int = 0, batch: int = 1,
-                      val: str = "middle", implicit: bool = True, objective=None) -> SearchStats:
+                      val: str = "middle", implicit: bool = True, objective=None, var_select: str = "first_smallest") -> SearchStats:
     """dfs_set under Enumerate: the same nodes, propagated by the same ``ctx.propagate_set``, branched by branch_enumerate_set.  With
     batch = 1 the node order is the reference's left-first DFS under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>.
     ``objective``: as in dfs_set — BranchAndBound wraps any brancher (branch_and_bound.rs:64-84), so the bound is folded into a node's
     set before its propagation exactly as under BinarySplit; this is the host specification of pcp_dfs_forest_device_set_bnb's Enumerate loop."""
     if val not in ("middle", "min"):
         raise ValueError(f"val must be 'middle' or 'min', not {val!r}")
+    _check_var_select(var_select)
     obj = _objective(objective)
     root = (interval_bits(np.asarray(lb0), np.asarray(ub0), ctx.set_words, base), None if implicit else full_active(1, ctx.n_units)[0])
-    return _search(_SetsEnumerate(ctx, base, implicit, val), root, all_solutions, node_limit, batch, obj)
+    return _search(_SetsEnumerate(ctx, base, implicit, val, var_select), root, all_solutions, node_limit, batch, obj)

@@ -211,9 +211,16 @@ class DeviceSearch:
     parents leave a hole below the new segment; it is reclaimed when that segment is used up (LIFO)."""
 
     def __init__(self, ctx, batch: int = 1024, capacity: int = 0, device=None, implicit: bool = False, hints=None, cells: bool = False, objective=None,
-                 brancher: str = "split", val: str = "middle", excl_capacity: int = 0):
+                 brancher: str = "split", val: str = "middle", excl_capacity: int = 0, var_select=None):
         import torch
         self.torch, self.ctx, self.batch = torch, ctx, int(batch)
+        # var_select: None leaves the context's variable selector as it is; "first_smallest" / "input_order" is the context's selector (option
+        # "var_select") while advance() runs, the value before restored afterwards.  (The selector is not a brancher: brancher= names the distributor.)
+        if var_select is not None and var_select not in ("first_smallest", "input_order"):
+            raise ValueError(f"var_select must be 'first_smallest' or 'input_order', not {var_select!r}")
+        if cells and var_select == "input_order":
+            raise ValueError("var_select='input_order' is not served by the packed-cell brancher (pcp_branch_device_cells selects FirstSmallestVar only): cells=True is refused")
+        self.var_select = var_select
         # brancher="enumerate": children x = v / x != v instead of BinarySplit's x <= v / x > v; val: MiddleVal or MinVal (Enumerate only)
         if brancher not in ("split", "enumerate"):
             raise ValueError(f"brancher must be 'split' or 'enumerate', not {brancher!r}")
@@ -390,7 +397,13 @@ class DeviceSearch:
         between two exchanges of parallel_search_device): every node's status counts.
         With an objective, ``all_solutions`` is ignored: branch and bound runs to the end of the search.
         ``keep_bounds`` (int32 rows only): every solution kept in ``stats.solutions`` also leaves its upper bounds in ``self.solutions_ub``, row
-        for row (a True node of an interval store is a box; ``stats.solutions`` holds its lower corner, and the stats keep their fields)."""
+        for row (a True node of an interval store is a box; ``stats.solutions`` holds its lower corner, and the stats keep their fields).
+        A DeviceSearch built with ``var_select=`` runs them under that variable selector (engine.var_select_scope)."""
+        from .engine import var_select_scope
+        with var_select_scope(self.ctx, self.var_select):
+            return self._advance(all_solutions, node_limit, max_rounds, keep_solutions, batch, stop_at, keep_bounds)
+
+    def _advance(self, all_solutions, node_limit, max_rounds, keep_solutions, batch, stop_at, keep_bounds) -> bool:
         torch, ctx, st, kind = self.torch, self.ctx, self.stats, self.kind
         bnb = self.objective is not None
         all_solutions = all_solutions or bnb

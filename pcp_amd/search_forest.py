@@ -12,6 +12,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from .engine import _xneq_forest, scoped_var_select
+
 
 def share_of_budget(node_limit: int, seeded_nodes: int, rank: int, world: int) -> int:
     """This rank's part of what is left of `node_limit` after the expansion: the shares differ by at most one and add up exactly."""
@@ -41,6 +43,7 @@ def trail_bound(ctx) -> int:
     return int(ctx.n_vars) * int(ctx.set_words) * 64 + 16
 
 
+@scoped_var_select()
 def forest_search_set(ctx, lb0, ub0, base: int = 0, node_limit: int = 0, n_trees: int = 512, steps_per_launch: int = 2048, rank: int = 0, world: int = 1,
                       trail_capacity: int = 0, level_capacity: int = 0, info: dict | None = None, brancher: str = "split", val: str = "middle",
                       formulas: bool = False, rebalance: bool = True) -> dict:
@@ -76,6 +79,7 @@ def forest_search_set(ctx, lb0, ub0, base: int = 0, node_limit: int = 0, n_trees
     return out
 
 
+@scoped_var_select()
 def forest_bnb_set(ctx, lb0, ub0, base: int, objective, n_trees: int = 256, ramp_steps: int = 16, steps_per_launch: int = 2048, brancher: str = "split",
                    val: str = "middle", best0=None, node_limit: int = 0, trail_capacity: int = 0, level_capacity: int = 0, info: dict | None = None,
                    formulas: bool = False) -> dict:
@@ -419,6 +423,7 @@ def seed_roots_interval(ctx, lb0, ub0, want: int, objective=None, brancher: str 
 STACK_BYTES_CAP = 64 << 30  # default ceiling of the forest's stack rows per GPU (both bound arrays together); rows are allocated as trees get deep
 
 
+@scoped_var_select(refuse=_xneq_forest)
 def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_per_launch: int = 512, rank: int = 0, world: int = 1, capacity: int = 0,
                   dist=None, info: dict | None = None, stack_bytes: int = STACK_BYTES_CAP, formulas: bool = False, small: bool = False, brancher: str = "split",
                   val: str = "middle", collect_solutions: bool = False, sink_capacity: int = 4096, _by_store=None) -> dict:
@@ -500,6 +505,7 @@ def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_
     return out
 
 
+@scoped_var_select()
 def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: int = 512, best0=None, capacity: int = 128, max_capacity: int = 1 << 16,
                info: dict | None = None, formulas: bool = True, small: bool = False, brancher: str = "split", val: str = "middle",
                collect_solutions: bool = False, _by_store=None) -> dict:
@@ -548,6 +554,7 @@ def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: i
     return out
 
 
+@scoped_var_select()
 def forest_enumerate(ctx, lb0, ub0, val: str = "middle", objective=None, n_trees: int = 256, steps_per_launch: int = 512, best0=None, collect_solutions: bool = False,
                      sink_capacity: int = 4096, info: dict | None = None, capacity: int = 128, max_capacity: int = 1 << 16, path_capacity: int = 64, rebalance: bool = True,
                      dist=None) -> dict:
