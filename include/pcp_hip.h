@@ -755,7 +755,8 @@ int32_t pcp_dfs_forest_device_form_enum(pcp_ctx* ctx, const pcp_dfs_state* st, u
  * lost or written twice.  Rows are in ticket order, which between trees is an order in time.
  * With a sink attached the branch-and-bound entries (pcp_dfs_forest_device_form_bnb, _small_bnb, _small_enum and _form_enum with obj != NULL: they keep
  * tree_row), the all-XNeqY forest pcp_dfs_forest_device and every set-mode forest entry (pcp_dfs_forest_device_set, _set_enum, _set_bnb,
- * _setform, _setform_bnb) return PCP_ERR_UNSUPPORTED and launch nothing; with none attached every entry does what it did before.
+ * _setform, _setform_bnb) return PCP_ERR_UNSUPPORTED and launch nothing; with none attached every entry does what it did before.  (THIS
+ * sink, of (lb, ub) rows, is meant: the set-mode forests write into a sink of their own, pcp_set_solution_sink below.)
  * A null lb, ub or count, capacity == 0, reserved != 0: PCP_ERR_ARG, and the sink attached before stays. */
 typedef struct {
   int32_t* lb;
@@ -766,6 +767,44 @@ typedef struct {
   uint32_t reserved;
 } pcp_solution_sink;
 int32_t pcp_solution_sink_set(pcp_ctx* ctx, const pcp_solution_sink* sink);
+/* TWO SINKS.  pcp_solution_sink, above, is the Interval forests': rows of (lb, ub).  While it is attached every set-mode forest entry
+ * returns PCP_ERR_UNSUPPORTED, as said there — its rows cannot hold a set.  pcp_set_solution_sink, here, is the set-mode forests': every
+ * solution of pcp_dfs_forest_device_set, _set_enum and _setform (both distributors), not only their number and the first one's lower
+ * bounds.  A True node over IntervalSet domains is a PRODUCT OF SETS — every unit is entailed while a set may still hold several values and
+ * may have holes — and every point of the product is a solution; neither the count nor first_solution says which points those are.  A row is
+ * therefore the whole node, n_vars x set_words 64-bit words in the layout of a pcp_forest_state.bits row (bit b of word w of variable v:
+ * the value hull_lo + 64 w + b).
+ *   bits     : [capacity][n_vars][set_words] device uint64: row i = the i-th solution appended
+ *   tree     : [capacity] device uint32 or NULL: the tree that wrote row i
+ *   count    : device uint32: tickets drawn since the caller last zeroed it.  It may exceed capacity: the valid rows are min(*count, capacity)
+ *   capacity : rows (> 0);  reserved : 0
+ * It belongs to the context: the struct is copied at the call, the buffers stay the caller's, NULL detaches; the caller reads and zeroes
+ * *count between launches, never during one.  pcp_model_reset DETACHES it, because the row width changes with the model.  (The Interval
+ * sink survives pcp_model_reset: its attachment is left as it was, and its caller re-attaches after a reset that changes n_vars.)  It can
+ * be attached to a set-mode context only (pcp_model_reset with set_words > 0), so the Interval entries never see one.
+ * THE PROTOCOL is that of the Interval sink.  A node found to be a solution (not the StopNode limit node, which is none and draws no
+ * ticket) draws slot = (*count)++ BEFORE it is counted.  slot < capacity: the node's sets go to row slot, tree[slot] = t, and the step goes
+ * on as without a sink — counted, the forest's first solution kept, stop raised under stop_on_solution.  slot >= capacity: error 6, "sink
+ * full", in counters[t][3] — nothing is counted, the node the tree reserved goes back to *total_nodes, the tree keeps the node as its
+ * current node AT ITS FIXPOINT with tree[t][2] = PCP_DFS_FULL, trail and levels untouched, and *stop is raised (one word for all trees of
+ * these forests): the contract of error 1 in this loop.  Errors 1, 3, 4 and 5 keep their meaning here.  A caller that copies the rows
+ * out, zeroes *count, clears that tree's error word and *stop and calls again runs the node again — propagating a fixpoint narrows nothing
+ * and trails nothing — and it is counted and appended then.  No counter of any tree differs from a run whose sink never fills: the
+ * handed-back node was not counted and its reservation was returned; its second run leaves sets, trail and levels as the first did, so the
+ * tree goes on from the state it would have had; the other trees see *stop between nodes only, as at any launch end, and a tree's nodes do
+ * not depend on when they run.  No solution is lost or written twice; rows are in ticket order.  A tree stopped by error 6 is an ordinary
+ * donor for pcp_dfs_forest_split_set.
+ * pcp_dfs_forest_device_set_bnb and pcp_dfs_forest_device_setform_bnb return PCP_ERR_UNSUPPORTED and launch nothing while a set sink is
+ * attached (branch and bound keeps tree_row); with none attached every entry launches exactly what it launched before.
+ * A null bits or count, capacity == 0, reserved != 0, an interval-mode context: PCP_ERR_ARG, and the sink attached before stays. */
+typedef struct {
+  uint64_t* bits;
+  uint32_t* tree;
+  uint32_t* count;
+  uint32_t capacity;
+  uint32_t reserved;
+} pcp_set_solution_sink;
+int32_t pcp_set_solution_sink_set(pcp_ctx* ctx, const pcp_set_solution_sink* sink);
 /* Between two calls of pcp_dfs_forest_device_set* / _setform*: finished trees take over work from trees that still have some.  pairs = n_pairs x
  * (donor, receiver) tree indices (device uint32).  For every pair whose receiver is finished and whose donor has an open right branch
  * left, the donor's OLDEST open right branch (the subtree nearest its root) becomes the receiver's new root — built from the donor's

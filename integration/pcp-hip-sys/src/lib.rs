@@ -192,6 +192,19 @@ pub struct pcp_solution_sink {
     pub reserved: u32,    // 0
 }
 
+/// The set solution sink of a context (`pcp_set_solution_sink_set`): the append buffer of whole nodes — n_vars x set_words words, the layout
+/// of a `pcp_forest_state.bits` row — the set-mode forests write every solution into; error 6 of a tree = the sink was full, the node stays
+/// the tree's current node, at its fixpoint and uncounted (include/pcp_hip.h).  `pcp_model_reset` detaches it.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct pcp_set_solution_sink {
+    pub bits: *mut u64,   // [capacity][n_vars][set_words] device
+    pub tree: *mut u32,   // [capacity] device or null: the tree that wrote the row
+    pub count: *mut u32,  // device u32: tickets drawn since the caller last zeroed it; valid rows = min(*count, capacity)
+    pub capacity: u32,
+    pub reserved: u32,    // 0
+}
+
 /// The objective of `pcp_propagate_device_small_excl` (and of the header's `pcp_propagate_device_bnb`): branch and bound around a batch.
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -293,6 +306,7 @@ extern "C" {
     pub fn pcp_dfs_forest_split_set(ctx: *mut pcp_ctx, st: *const pcp_forest_state, n_pairs: u32, pairs: *const u32, done: *mut u32,
                                     hip_stream: *mut c_void) -> i32; // pairs = n_pairs x (donor, receiver), device memory
     pub fn pcp_solution_sink_set(ctx: *mut pcp_ctx, sink: *const pcp_solution_sink) -> i32; // null detaches; honoured by _form, _small, _small_enum and _form_enum (obj null)
+    pub fn pcp_set_solution_sink_set(ctx: *mut pcp_ctx, sink: *const pcp_set_solution_sink) -> i32; // null detaches; set-mode contexts only; honoured by _set, _set_enum and _setform, refused by their _bnb entries
     pub fn pcp_dfs_device(ctx: *mut pcp_ctx, st: *const pcp_dfs_state, n_steps: u32, stop_on_solution: u32, node_limit: u64,
                           hip_stream: *mut c_void) -> i32; // OneSolution/AllSolution<Propagation<Brancher<..>>> under StopNode, n_steps nodes
     pub fn pcp_stats_reset(ctx: *mut pcp_ctx, hip_stream: *mut c_void) -> i32;

@@ -73,6 +73,7 @@ struct pcp_ctx : HostModel, LoweredInfo {
   void* d_stage = nullptr; size_t cap_stage = 0;
 
   SinkDev sink{};         // pcp_solution_sink_set: the solution sink of the Interval forests (sink.lb == null: none attached)
+  SetSinkDev set_sink{};  // pcp_set_solution_sink_set: the solution sink of the set-mode forests (set_sink.bits == null: none attached); pcp_model_reset detaches it
   pcp_plan last_plan{};   // geometry of the last launch (pcp_last_plan)
   const uint32_t* dfs_sp = nullptr;    // set by pcp_dfs_device around its launches: LaunchArgs::sp_ptr / stop_ptr
   size_t dfs_team_words = 0;           // words of d_team the step kernel zeroes after each step (0: the launch clears them itself)
@@ -137,8 +138,12 @@ int32_t hip_fail(pcp_ctx* c, hipError_t e, const char* what) {
 
 // A forest entry that cannot write into the context's solution sink refuses to run while one is attached (pcp_solution_sink_set): a caller
 // that asked for every solution never gets a count without them.
-int32_t refuse_sink(pcp_ctx* c, const std::string& who, const char* why) {
-  return fail(c, PCP_ERR_UNSUPPORTED, who + ": a solution sink is attached (pcp_solution_sink_set) and " + why + "; detach it with pcp_solution_sink_set(ctx, NULL)");
+int32_t refuse_sink(pcp_ctx* c, const std::string& who, const char* why, const char* setter = "pcp_solution_sink_set", const char* what = "a solution sink") {
+  return fail(c, PCP_ERR_UNSUPPORTED, who + ": " + what + " is attached (" + setter + ") and " + why + "; detach it with " + setter + "(ctx, NULL)");
+}
+// (the set solution sink, pcp_set_solution_sink_set: the branch-and-bound entries of the set-mode forests)
+int32_t refuse_set_sink(pcp_ctx* c, const std::string& who, const char* why) {
+  return refuse_sink(c, who, why, "pcp_set_solution_sink_set", "a set solution sink");
 }
 
 template <class T>
@@ -450,6 +455,7 @@ int32_t pcp_model_reset(pcp_ctx* c, uint32_t n_vars, uint32_t set_words) {
   c->has_groups = false;
   c->hull_set = false;
   c->dirty = true;
+  c->set_sink = SetSinkDev{};  // its rows are n_vars x set_words words of the model that was
   return PCP_OK;
 }
 
@@ -1073,6 +1079,7 @@ static int32_t dfs_forest_set(pcp_ctx* c, const pcp_forest_state* st, const pcp_
   if (!c || !st) return PCP_ERR_ARG;
   const char* const who = obj ? "pcp_dfs_forest_device_set_bnb" : (enumerate ? "pcp_dfs_forest_device_set_enum" : "pcp_dfs_forest_device_set");
   if (c->sink.lb) return refuse_sink(c, who, "the set-mode forests do not write into it");
+  if (obj && c->set_sink.bits) return refuse_set_sink(c, who, "branch and bound keeps tree_row instead");
   SetDfsArgs a;
   const int32_t rc = forest_set_args(c, who, st, obj, val,
                                      c->has_formulas ? ": pcp_dfs_forest_device_set evaluates records, not formula trees: a store with formula propagators (Boolean / pcp_model_push_formula) is searched by pcp_dfs_forest_device_setform" : nullptr,
@@ -1088,7 +1095,7 @@ static int32_t dfs_forest_set(pcp_ctx* c, const pcp_forest_state* st, const pcp_
   if (!n_steps) return PCP_OK;
   c->last_plan = pcp_plan{1u, 1u, 0u, 0u, 0u, 0u, 1u, 1u, st->n_trees, 1024u, (uint32_t)lds, cap, 0u};
   hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
-  return forest_launch(c, stream, [&] { return launch_setdfs(a, enumerate, obj != nullptr, stream); });
+  return forest_launch(c, stream, [&] { return launch_setdfs(a, c->set_sink, enumerate, obj != nullptr, stream); });  // (never a sink with obj: refused above)
 }
 
 int32_t pcp_dfs_forest_device_set(pcp_ctx* c, const pcp_forest_state* st, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
@@ -1115,6 +1122,7 @@ static int32_t dfs_forest_setform(pcp_ctx* c, const pcp_forest_state* st, const 
                                   uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
   const char* const who = obj ? "pcp_dfs_forest_device_setform_bnb" : "pcp_dfs_forest_device_setform";
   if (c->sink.lb) return refuse_sink(c, who, "the set-mode forests do not write into it");
+  if (obj && c->set_sink.bits) return refuse_set_sink(c, who, "branch and bound keeps tree_row instead");
   if (enumerate > 1) return fail(c, PCP_ERR_ARG, std::string(who) + ": enumerate must be 0 or 1");
   SetFormDfsArgs fa;
   memset(&fa, 0, sizeof(fa));
@@ -1135,7 +1143,7 @@ static int32_t dfs_forest_setform(pcp_ctx* c, const pcp_forest_state* st, const 
   plan.block = 64 * waves; plan.lds_bytes = lds; plan.grid = (st->n_trees + waves - 1) / waves;
   c->last_plan = pcp_plan{waves, 1u, 0u, 0u, 0u, 0u, 1u, 1u, plan.grid, plan.block, (uint32_t)lds, 0u, 3u};
   hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
-  return forest_launch(c, stream, [&] { return launch_setformdfs(fa, enumerate != 0, obj != nullptr, plan, stream); });
+  return forest_launch(c, stream, [&] { return launch_setformdfs(fa, c->set_sink, enumerate != 0, obj != nullptr, plan, stream); });  // (never a sink with obj: refused above)
 }
 
 int32_t pcp_dfs_forest_device_setform(pcp_ctx* c, const pcp_forest_state* st, uint32_t enumerate, uint32_t val, uint32_t n_steps, uint32_t stop_on_solution,
@@ -1354,6 +1362,17 @@ int32_t pcp_solution_sink_set(pcp_ctx* c, const pcp_solution_sink* sink) {
   if (!sink->capacity) return fail(c, PCP_ERR_ARG, "pcp_solution_sink_set: capacity must be at least one row");
   if (sink->reserved) return fail(c, PCP_ERR_ARG, "pcp_solution_sink_set: reserved must be 0");
   c->sink = SinkDev{sink->lb, sink->ub, sink->tree, sink->count, sink->capacity};
+  return PCP_OK;
+}
+
+int32_t pcp_set_solution_sink_set(pcp_ctx* c, const pcp_set_solution_sink* sink) {
+  if (!c) return PCP_ERR_ARG;
+  if (!sink) { c->set_sink = SetSinkDev{}; return PCP_OK; }
+  if (!c->set_words) return fail(c, PCP_ERR_ARG, "pcp_set_solution_sink_set needs a set-mode model (pcp_model_reset with set_words > 0): the Interval forests write into pcp_solution_sink_set's");
+  if (!sink->bits || !sink->count) return fail(c, PCP_ERR_ARG, "pcp_set_solution_sink_set: bits and count are required");
+  if (!sink->capacity) return fail(c, PCP_ERR_ARG, "pcp_set_solution_sink_set: capacity must be at least one row");
+  if (sink->reserved) return fail(c, PCP_ERR_ARG, "pcp_set_solution_sink_set: reserved must be 0");
+  c->set_sink = SetSinkDev{sink->bits, sink->tree, sink->count, sink->capacity};
   return PCP_OK;
 }
 

@@ -113,6 +113,21 @@ hipError_t launch_setfix(const ModelDev& m, uint32_t n_nodes, uint32_t set_words
                          uint64_t* bits_out, int32_t* lb_out, int32_t* ub_out, const uint64_t* live_in, uint64_t* live, uint8_t* status,
                          pcp_stats* stats, uint64_t* derive_into, hipStream_t stream);
 
+// The set solution sink of a context (pcp_set_solution_sink_set): an append buffer of whole nodes — n_vars x set_words 64-bit words, the
+// layout of a pcp_forest_state.bits row — every tree of a set-mode forest writes its solutions into.  A solution draws a ticket from *count
+// BEFORE it is counted; a ticket >= capacity hands the node back to the caller (error kSetDfsSinkFull, the contract of error 1 in
+// trail_dfs).  The SINK = false instantiations never read the struct.  It is a kernel argument OF ITS OWN behind SetDfsArgs /
+// SetFormDfsArgs, not a member of SetDfsArgs: that struct is the first member of SetFormDfsArgs, and growing it moved the formula fields
+// behind it, which changed the SGPR spill counts of setformdfs_kernel's existing branch-and-bound instantiations; appended behind both
+// structs, every argument that existed keeps its offset and every existing instantiation its figures (profiles/set_forest_sink_resource_usage.txt).
+struct SetSinkDev {
+  uint64_t* bits;     // [capacity][n_vars][set_words]
+  uint32_t* tree;     // [capacity] or null: the tree that wrote the row
+  uint32_t* count;    // tickets drawn since the caller last zeroed it
+  uint32_t capacity;
+};
+constexpr uint32_t kSetDfsSinkFull = 6;  // counters[t][3]: the sink was full — the node stays the tree's current node, at its fixpoint and uncounted
+
 // Set mode, the search loop on the device: one tree per workgroup, the current node in LDS, an undo trail in HBM (pcp_set.hip).
 struct SetDfsArgs {
   ModelDev m;
@@ -144,7 +159,8 @@ constexpr uint32_t kLevelGiven = 1u, kLevelEnum = 2u;
 constexpr uint32_t kDfsFull = 0xFFFFFFFFu;  // tree[..][2]: the current node has not been propagated at all (PCP_DFS_FULL)
 constexpr uint32_t kDfsChunk = 8;            // nodes a tree reserves from the forest's counter at a time
 size_t lds_bytes_set_dfs(uint32_t n_vars, uint32_t n_slots, uint32_t set_words, uint32_t list_cap);
-hipError_t launch_setdfs(const SetDfsArgs& a, bool enumerate, bool bnb, hipStream_t stream);
+// (sink.bits != null: the instantiation that appends every solution to the set sink; never together with bnb)
+hipError_t launch_setdfs(const SetDfsArgs& a, const SetSinkDev& sink, bool enumerate, bool bnb, hipStream_t stream);
 hipError_t launch_setdfs_split(const SetDfsArgs& a, uint32_t n_pairs, const uint32_t* pairs, uint32_t* done, hipStream_t stream);
 
 hipError_t launch_branch_scan(uint32_t n_nodes, const uint8_t* status, uint32_t* child_base, uint32_t* counts, hipStream_t stream);

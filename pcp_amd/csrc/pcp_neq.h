@@ -204,7 +204,8 @@ struct SetFormDfsArgs {
   uint32_t n_units;
 };
 size_t lds_bytes_setformdfs(uint32_t n_vars, uint32_t set_words, uint32_t n_units, uint32_t waves);  // one slice per tree; 0 = beyond a CU's LDS
-hipError_t launch_setformdfs(const SetFormDfsArgs& a, bool enumerate, bool bnb, const LaunchPlan& p, hipStream_t stream);
+// (sink.bits != null: the instantiation that appends every solution to the set sink, SetSinkDev of pcp_internal.h; never together with bnb)
+hipError_t launch_setformdfs(const SetFormDfsArgs& a, const SetSinkDev& sink, bool enumerate, bool bnb, const LaunchPlan& p, hipStream_t stream);
 
 // Small stores — a few dozen variables, up to a few thousand filters — over explicit `active` rows or implicit nodes: one wavefront per node
 // (pcp_small.hip).

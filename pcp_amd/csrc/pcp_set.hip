@@ -643,14 +643,15 @@ struct RecordNode {
   }
 };
 
-// ENUM, BNB: see trail_dfs.  The BNB = false instantiations carry no branch-and-bound code, the ENUM = false ones no value selector.
-template <bool ENUM, bool BNB>
-__global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a) {
+// ENUM, BNB, SINK: see trail_dfs.  The BNB = false instantiations carry no branch-and-bound code, the ENUM = false ones no value selector,
+// the SINK = false ones no set solution sink.
+template <bool ENUM, bool BNB, bool SINK>
+__global__ void __launch_bounds__(kSetThreads) setdfs_kernel(const SetDfsArgs a, const SetSinkDev sink) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const SetDfsCarve dcv = set_dfs_carve(a.m.n_vars, a.m.n_slots, a.set_words, a.list_cap);
   const WorkgroupTeam team(reinterpret_cast<uint32_t*>(smem + dcv.c.misc), reinterpret_cast<unsigned long long*>(smem + dcv.c.list_off));
   RecordNode<BNB> node(a, team, smem, dcv, blockIdx.x);
-  trail_dfs<ENUM, BNB>(a, blockIdx.x, team, node);
+  trail_dfs<ENUM, BNB, SINK>(a, sink, blockIdx.x, team, node);
 }
 
 // A finished tree takes over the OLDEST open right branch of a tree that still has some (the subtree nearest the donor's root: the
@@ -701,18 +702,22 @@ size_t lds_bytes_set_dfs(uint32_t n_vars, uint32_t n_slots, uint32_t set_words, 
   return c.total <= 160 * 1024 ? c.total : 0;
 }
 
-template <bool ENUM, bool BNB>
-static hipError_t launch_setdfs_as(const SetDfsArgs& a, size_t lds, hipStream_t stream) {
+template <bool ENUM, bool BNB, bool SINK>
+static hipError_t launch_setdfs_as(const SetDfsArgs& a, const SetSinkDev& sink, size_t lds, hipStream_t stream) {
   hipError_t e;
-  if (lds > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void*>(setdfs_kernel<ENUM, BNB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
-  hipLaunchKernelGGL((setdfs_kernel<ENUM, BNB>), dim3(a.n_trees), dim3(kSetThreads), lds, stream, a);
+  if (lds > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void*>(setdfs_kernel<ENUM, BNB, SINK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
+  hipLaunchKernelGGL((setdfs_kernel<ENUM, BNB, SINK>), dim3(a.n_trees), dim3(kSetThreads), lds, stream, a, sink);
   return hipGetLastError();
 }
 
-hipError_t launch_setdfs(const SetDfsArgs& a, bool enumerate, bool bnb, hipStream_t stream) {
+hipError_t launch_setdfs(const SetDfsArgs& a, const SetSinkDev& sk, bool enumerate, bool bnb, hipStream_t stream) {
   const size_t lds = set_dfs_carve(a.m.n_vars, a.m.n_slots, a.set_words, a.list_cap).total;
-  if (bnb) return enumerate ? launch_setdfs_as<true, true>(a, lds, stream) : launch_setdfs_as<false, true>(a, lds, stream);
-  return enumerate ? launch_setdfs_as<true, false>(a, lds, stream) : launch_setdfs_as<false, false>(a, lds, stream);
+  // the context's set solution sink (pcp_set_solution_sink_set); the branch-and-bound entry refuses it
+  const bool sink = sk.bits != nullptr;
+  if (sink && (bnb || !sk.count || !sk.capacity)) return hipErrorInvalidValue;
+  if (bnb) return enumerate ? launch_setdfs_as<true, true, false>(a, sk, lds, stream) : launch_setdfs_as<false, true, false>(a, sk, lds, stream);
+  if (sink) return enumerate ? launch_setdfs_as<true, false, true>(a, sk, lds, stream) : launch_setdfs_as<false, false, true>(a, sk, lds, stream);
+  return enumerate ? launch_setdfs_as<true, false, false>(a, sk, lds, stream) : launch_setdfs_as<false, false, false>(a, sk, lds, stream);
 }
 
 hipError_t launch_setdfs_split(const SetDfsArgs& a, uint32_t n_pairs, const uint32_t* pairs, uint32_t* done, hipStream_t stream) {

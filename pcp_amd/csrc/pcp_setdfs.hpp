@@ -31,8 +31,23 @@
 // — another tree may hold a better one already, so the winner's row is chosen on the host among the trees whose value equals the final
 // incumbent.  There is no stop-on-solution and no first solution: branch and bound runs to the end (or to the node limit).
 //
+// SINK = true (never with BNB): every solution is appended to the context's set solution sink (SetSinkDev, pcp_internal.h) as the WHOLE
+// node, V x set_words words — a True node over sets is a product of sets, not a point.  A template flag, so that the instantiations without
+// a sink are the code they were.  A solution (never the limit node, which is none) draws a ticket BEFORE it is counted: the leader's
+// atomicAdd on *count at agent scope, made uniform by team.broadcast_ticket before any lane uses it as an address.  slot < capacity: the
+// node goes from LDS to row `slot` (copy_node: plain vector stores, 16 bytes at a time where the row allows it), tree[slot] = t, and the
+// step goes on as without a sink.  slot >= capacity: error 6, "sink full", the contract of error 1 — nothing is counted, the reserved node
+// goes back to the forest's counter, pending = kDfsFull, and the final persist writes the node, AT ITS FIXPOINT, with the trail and the
+// levels untouched.  A relaunch loads it and propagates everything, which at a fixpoint narrows nothing and appends nothing to the trail
+// (in setformdfs_kernel every unit is live at launch start anyway), finds the same status, draws a ticket that fits and counts and appends
+// the node once.  Why no counter of any tree differs from a run whose sink never fills: the handed-back node was not counted (c_nodes,
+// c_sols untouched, its reservation returned), its second run leaves the sets, the trail and the levels as the first did, so the tree goes
+// on from exactly the state it would have had; other trees see the raised stop word only between nodes, as on any launch end, and their
+// nodes do not depend on when they run.  A tree stopped by error 6 is an ordinary donor for setdfs_split_kernel: its levels and trail
+// describe its current node, as after any launch.
+//
 // A Team gives: rank, size, lane; leader() (one thread); wave_wide() (the one wavefront that does the single-variable, wave-wide steps:
-// restriction, fold, value); sync(); broadcast() of one or two words from the leader; min_of_waves().  Values every thread of a team reads
+// restriction, fold, value); sync(); broadcast() of one or two words from the leader, broadcast_ticket() of the sink's slot; min_of_waves().  Values every thread of a team reads
 // from the same address (tree[], a level) are held once per wavefront (uniform()).
 // A Node owns the pointers into its kernel's LDS carve — bits, bnd, misc, touched (mask_words words), mark_mask(): the mask a restriction
 // marks — and the per-thread `narrow`, and supplies
@@ -78,6 +93,12 @@ struct WorkgroupTeam {
     sync();
     x = ctl[0]; y = ctl[2];
   }
+  // (a word of its own: the first-solution broadcast may follow with no barrier between, and must not overwrite a slot still being read)
+  __device__ __forceinline__ uint32_t broadcast_ticket(uint32_t x) const {
+    if (leader()) ctl[3] = x;
+    sync();
+    return uniform(ctl[3]);
+  }
   __device__ __forceinline__ unsigned long long min_of_waves(unsigned long long key) const {  // key: each wavefront's own minimum
     if (lane == 0) wave_min[wave] = key;
     sync();
@@ -97,6 +118,7 @@ struct WavefrontTeam {
   __device__ __forceinline__ void sync() const { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); }
   __device__ __forceinline__ uint32_t broadcast(uint32_t x) const { return __shfl(x, 0); }
   __device__ __forceinline__ void broadcast(uint32_t& x, uint32_t& y) const { x = __shfl(x, 0); y = __shfl(y, 0); }
+  __device__ __forceinline__ uint32_t broadcast_ticket(uint32_t x) const { return uniform(x); }  // (lane 0 is the leader and is active)
   __device__ __forceinline__ unsigned long long min_of_waves(unsigned long long key) const { return key; }
 };
 
@@ -130,8 +152,9 @@ __device__ __forceinline__ unsigned long long first_smallest_var(const Team& tea
 
 struct NodeStatus { bool failed, open; };
 
-template <bool ENUM, bool BNB, class Team, class Node>
-__device__ __forceinline__ void trail_dfs(const SetDfsArgs& a, const uint32_t t, const Team team, Node& node) {
+template <bool ENUM, bool BNB, bool SINK, class Team, class Node>
+__device__ __forceinline__ void trail_dfs(const SetDfsArgs& a, const SetSinkDev& sink, const uint32_t t, const Team team, Node& node) {
+  static_assert(!(BNB && SINK), "branch and bound keeps tree_row; its entries refuse a set sink");
   uint32_t* const tree = a.tree + (size_t)t * 4;
   if (uniform(tree[3]) & 1u) return;  // this tree is finished
   uint32_t n_levels = uniform(tree[0]), pending = uniform(tree[2]);
@@ -221,6 +244,17 @@ __device__ __forceinline__ void trail_dfs(const SetDfsArgs& a, const uint32_t t,
       if (!last) ++c_fail;
     } else if (!st.open && last) {
     } else if (!st.open) {  // a solution (monitor.rs:19-68)
+      if constexpr (SINK) {
+        // the ticket comes first: a node that finds the sink full is handed back uncounted, at its fixpoint (the contract of error 1)
+        uint32_t slot = 0;
+        if (team.leader()) slot = __hip_atomic_fetch_add(sink.count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        slot = team.broadcast_ticket(slot);
+        if (slot >= sink.capacity) { c_err = kSetDfsSinkFull; --c_nodes; pending = kDfsFull; if (team.leader()) atomicAdd(a.total_nodes, ~0ull); break; }
+        copy_node(team, reinterpret_cast<unsigned long long*>(sink.bits) + (size_t)slot * V * sw, bits, V * sw);
+        if (team.leader() && sink.tree) sink.tree[slot] = t;
+        // (the backtrack below writes `bits`; with first_solution the barrier of its broadcast stands between the copy and those writes)
+        if (!a.first_solution) team.sync();
+      }
       ++c_sols;
       if constexpr (BNB) {
         // the incumbent is var.lower() in both modes (branch_and_bound.rs:73-77): the tree keeps the value and the row, then lowers / raises

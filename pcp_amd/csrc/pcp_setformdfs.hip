@@ -149,8 +149,8 @@ struct FormulaNode {
   }
 };
 
-template <bool ENUM, bool BNB>
-__global__ void __launch_bounds__(256) setformdfs_kernel(const SetFormDfsArgs fa) {
+template <bool ENUM, bool BNB, bool SINK>
+__global__ void __launch_bounds__(256) setformdfs_kernel(const SetFormDfsArgs fa, const SetSinkDev sink) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwv = blockDim.x >> 6;
   const uint32_t t = blockIdx.x * nwv + wv;
@@ -158,16 +158,16 @@ __global__ void __launch_bounds__(256) setformdfs_kernel(const SetFormDfsArgs fa
   const SetFormDfsCarve dcv = setformdfs_carve(fa.d.m.n_vars, fa.d.set_words, fa.n_units);
   const WavefrontTeam team;
   FormulaNode node(fa, team, smem + (size_t)wv * dcv.total, dcv, t);
-  trail_dfs<ENUM, BNB>(fa.d, t, team, node);
+  trail_dfs<ENUM, BNB, SINK>(fa.d, sink, t, team, node);
 }
 
-template <bool ENUM, bool BNB>
-hipError_t launch_setformdfs_as(const SetFormDfsArgs& a, const LaunchPlan& p, hipStream_t stream) {
+template <bool ENUM, bool BNB, bool SINK>
+hipError_t launch_setformdfs_as(const SetFormDfsArgs& a, const SetSinkDev& sink, const LaunchPlan& p, hipStream_t stream) {
   hipError_t e;
   if (p.lds_bytes > 64 * 1024 &&
-      (e = hipFuncSetAttribute(reinterpret_cast<const void*>(setformdfs_kernel<ENUM, BNB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes)) != hipSuccess)
+      (e = hipFuncSetAttribute(reinterpret_cast<const void*>(setformdfs_kernel<ENUM, BNB, SINK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes)) != hipSuccess)
     return e;
-  hipLaunchKernelGGL((setformdfs_kernel<ENUM, BNB>), dim3(p.grid), dim3(p.block), p.lds_bytes, stream, a);
+  hipLaunchKernelGGL((setformdfs_kernel<ENUM, BNB, SINK>), dim3(p.grid), dim3(p.block), p.lds_bytes, stream, a, sink);
   return hipGetLastError();
 }
 
@@ -179,9 +179,13 @@ size_t lds_bytes_setformdfs(uint32_t n_vars, uint32_t set_words, uint32_t n_unit
 }
 
 // p.block = 64 x the trees of a workgroup, p.grid = ceil(n_trees / those), p.lds_bytes = lds_bytes_setformdfs of them
-hipError_t launch_setformdfs(const SetFormDfsArgs& a, bool enumerate, bool bnb, const LaunchPlan& p, hipStream_t stream) {
-  if (bnb) return enumerate ? launch_setformdfs_as<true, true>(a, p, stream) : launch_setformdfs_as<false, true>(a, p, stream);
-  return enumerate ? launch_setformdfs_as<true, false>(a, p, stream) : launch_setformdfs_as<false, false>(a, p, stream);
+hipError_t launch_setformdfs(const SetFormDfsArgs& a, const SetSinkDev& sk, bool enumerate, bool bnb, const LaunchPlan& p, hipStream_t stream) {
+  // the context's set solution sink (pcp_set_solution_sink_set); the branch-and-bound entry refuses it
+  const bool sink = sk.bits != nullptr;
+  if (sink && (bnb || !sk.count || !sk.capacity)) return hipErrorInvalidValue;
+  if (bnb) return enumerate ? launch_setformdfs_as<true, true, false>(a, sk, p, stream) : launch_setformdfs_as<false, true, false>(a, sk, p, stream);
+  if (sink) return enumerate ? launch_setformdfs_as<true, false, true>(a, sk, p, stream) : launch_setformdfs_as<false, false, true>(a, sk, p, stream);
+  return enumerate ? launch_setformdfs_as<true, false, false>(a, sk, p, stream) : launch_setformdfs_as<false, false, false>(a, sk, p, stream);
 }
 
 }  // namespace pcp

@@ -28,7 +28,7 @@ ERRORS = {-1: "PCP_ERR_ARG", -2: "PCP_ERR_CONTRACT", -3: "PCP_ERR_HIP", -4: "PCP
 ABI_SYMBOLS = [
     "pcp_ctx_create", "pcp_ctx_destroy", "pcp_last_error", "pcp_strerror", "pcp_abi_version",
     "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull",
-    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_form_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
+    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_form_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_set_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
 ]
 
 
@@ -143,6 +143,53 @@ class SolutionSink:
         return cat(self._lb, (0, self.n_vars)), cat(self._ub, (0, self.n_vars)), cat(self._tree, (0,))
 
 
+class PcpSetSolutionSink(C.Structure):
+    """pcp_set_solution_sink: the append buffer of whole nodes (n_vars x set_words words) the set-mode forests write every solution into
+    (pcp_set_solution_sink_set)."""
+    _fields_ = [("bits", C.c_void_p), ("tree", C.c_void_p), ("count", C.c_void_p), ("capacity", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SetSolutionSink:
+    """The buffers of a pcp_set_solution_sink and the host's side of its protocol, as SolutionSink is for the Interval one: ``bits``
+    [capacity, n_vars, set_words] int64 (the words of uint64 sets), ``tree`` [capacity] int32, ``count`` [1] int32 (torch tensors on ``device``;
+    a CPU device serves the bookkeeping's tests).  ``drain()`` copies the min(count, capacity) valid rows to the host — in ticket order,
+    behind what earlier drains brought — and zeroes the count.  ``rows()`` is everything drained so far."""
+
+    def __init__(self, capacity: int, n_vars: int, set_words: int, device):
+        import torch
+        if int(capacity) < 1:
+            raise ValueError(f"SetSolutionSink: capacity must be at least 1, not {capacity}")
+        if int(set_words) < 1:
+            raise ValueError(f"SetSolutionSink: set_words must be at least 1, not {set_words} (interval-mode stores write into a SolutionSink)")
+        self.capacity, self.n_vars, self.set_words = int(capacity), int(n_vars), int(set_words)
+        self.bits = torch.zeros((self.capacity, self.n_vars, self.set_words), dtype=torch.int64, device=device)
+        self.tree = torch.zeros(self.capacity, dtype=torch.int32, device=device)
+        self.count = torch.zeros(1, dtype=torch.int32, device=device)
+        self.drains = 0     # drain() calls
+        self.overdrawn = 0  # tickets beyond the capacity, over all drains: the nodes that were handed back
+        self._bits, self._tree = [], []
+
+    def struct(self) -> PcpSetSolutionSink:
+        return PcpSetSolutionSink(self.bits.data_ptr(), self.tree.data_ptr(), self.count.data_ptr(), self.capacity, 0)
+
+    def drain(self) -> int:
+        """Move the valid rows to the host and zero the count.  Returns the number of rows moved."""
+        drawn = int(self.count.item()) & 0xFFFFFFFF  # (synchronises: the launches before it have ended)
+        n = min(drawn, self.capacity)
+        if n:
+            self._bits.append(self.bits[:n].cpu().numpy().view(np.uint64).copy())
+            self._tree.append(self.tree[:n].cpu().numpy().copy())
+        self.drains += 1
+        self.overdrawn += drawn - n
+        self.count.zero_()
+        return n
+
+    def rows(self):
+        """(bits [n, n_vars, set_words] uint64, tree [n] int32) of every row drained so far, numpy arrays."""
+        bits = np.concatenate(self._bits) if self._bits else np.zeros((0, self.n_vars, self.set_words), np.uint64)
+        return bits, (np.concatenate(self._tree) if self._tree else np.zeros((0,), np.int32))
+
+
 DFS_FULL = 0xFFFFFFFF
 
 
@@ -223,6 +270,7 @@ def load_library():
     L.pcp_dfs_forest_device_small_enum.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestExcl), C.POINTER(ForestObjective), u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_form_enum.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestExcl), C.POINTER(ForestObjective), u32, u32, C.c_uint64, vp]
     L.pcp_solution_sink_set.argtypes = [vp, C.POINTER(PcpSolutionSink)]
+    L.pcp_set_solution_sink_set.argtypes = [vp, C.POINTER(PcpSetSolutionSink)]
     L.pcp_stats_reset.argtypes = [vp, vp]
     L.pcp_stats_read.argtypes = [vp, C.POINTER(PcpStats), vp]
     L.pcp_debug_counters.argtypes = [vp, C.POINTER(C.c_uint64), u32, vp]
@@ -230,7 +278,7 @@ def load_library():
     L.pcp_last_plan.argtypes = [vp, C.POINTER(PcpPlan)]
     L.pcp_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
     for f in ("pcp_ctx_create", "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull", "pcp_model_set_hull",
-              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_form_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
+              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_form_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_set_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
         getattr(L, f).restype = i32
     _lib = L
     return L
@@ -651,6 +699,14 @@ class Context:
         st = sink.struct() if isinstance(sink, SolutionSink) else sink
         self._check(self._L.pcp_solution_sink_set(self._h, None if st is None else C.byref(st)))
 
+    def set_solution_sink_set(self, sink=None):
+        """pcp_set_solution_sink_set: attach a set solution sink — a SetSolutionSink or a PcpSetSolutionSink over device buffers — to this
+        (set-mode) context, or detach the one attached (None).  While one is attached dfs_forest_set and dfs_forest_setform append every
+        solution to it as a whole node and hand a node back with error 6 (SINK_FULL) when it is full; their _bnb drivers' entries refuse to
+        run (PCP_ERR_UNSUPPORTED).  The struct is copied; the buffers must outlive the attachment.  set_model (pcp_model_reset) detaches it."""
+        st = sink.struct() if isinstance(sink, SetSolutionSink) else sink
+        self._check(self._L.pcp_set_solution_sink_set(self._h, None if st is None else C.byref(st)))
+
     @scoped_var_select(refuse=_xneq_forest)
     def dfs_forest(self, root_lb, root_ub, stop_on_solution: bool = False, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
                    max_launches: int = 1 << 30, node_budget: int = 0, want_solution: bool = False, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
@@ -853,14 +909,22 @@ class Context:
     @scoped_var_select()
     def dfs_forest_set(self, root_bits, stop_on_solution: bool = False, node_limit: int = 0, steps_per_launch: int = 256,
                        level_capacity: int = 0, trail_capacity: int = 0, max_launches: int = 1 << 30, want_solution: bool = True,
-                       info: dict | None = None, rebalance: bool = True, brancher: str = "split", val: str = "middle"):
+                       info: dict | None = None, rebalance: bool = True, brancher: str = "split", val: str = "middle",
+                       collect_solutions: bool = False, sink_capacity: int = 4096):
         """pcp_dfs_forest_device_set: the reference's search loop over FDSpace on the device, one tree per workgroup, the current
         node in LDS, an undo trail in HBM.  brancher="enumerate": the same loop under Enumerate on MiddleVal (val="middle") or MinVal ("min"),
         pcp_dfs_forest_device_set_enum; val is ignored under "split" (BinarySplit on MiddleVal).  root_bits: [n_trees, n_vars, set_words] uint64 (numpy or a CUDA int64 tensor): the roots,
         not yet propagated.  Launches of steps_per_launch nodes per tree are repeated until every tree is finished, the forest
         stopped (solution / node limit / error) or max_launches is reached.
-        Returns dict(nodes, solutions, failed, error, finished_trees, stopped, launches, first_solution, per_tree=[n_trees, 4])."""
+        Returns dict(nodes, solutions, failed, error, finished_trees, stopped, launches, first_solution, per_tree=[n_trees, 4]).
+        ``collect_solutions``: every solution is returned, not only counted — a SetSolutionSink of ``sink_capacity`` rows is attached for the
+        duration of the call, a tree that finds it full hands its node back (error 6), the loop drains the sink and resumes; the counters
+        are those of the same call without it.  The result then also holds ``solutions_bits`` ([n, n_vars, set_words] uint64: a solution is
+        a product of sets — every point of it satisfies the model; ``first_solution`` keeps lower bounds only) and ``solution_tree`` ([n]:
+        the tree that wrote each row); ``info`` receives ``drains`` and ``handed_back``.  With the default False the calls issued and the
+        keys returned are those of before."""
         _check_brancher(brancher, val)
+        _check_collect_set("dfs_forest_set", collect_solutions, sink_capacity)
 
         def launch(st, steps, stream):
             if brancher == "enumerate":
@@ -868,36 +932,58 @@ class Context:
             return self._L.pcp_dfs_forest_device_set(self._h, C.byref(st), steps, int(bool(stop_on_solution)), int(node_limit), C.c_void_p(stream))
 
         return self._run_forest_set(root_bits, launch, node_limit=node_limit, steps_per_launch=steps_per_launch, level_capacity=level_capacity,
-                                    trail_capacity=trail_capacity, max_launches=max_launches, want_solution=want_solution, info=info, rebalance=rebalance)
+                                    trail_capacity=trail_capacity, max_launches=max_launches, want_solution=want_solution, info=info, rebalance=rebalance,
+                                    **(dict(collect=int(sink_capacity), stop_on_solution=stop_on_solution) if collect_solutions else {}))
 
     @scoped_var_select()
     def dfs_forest_setform(self, root_bits, stop_on_solution: bool = False, node_limit: int = 0, steps_per_launch: int = 256,
                            level_capacity: int = 0, trail_capacity: int = 0, max_launches: int = 1 << 30, want_solution: bool = True,
-                           info: dict | None = None, rebalance: bool = True, brancher: str = "split", val: str = "middle"):
+                           info: dict | None = None, rebalance: bool = True, brancher: str = "split", val: str = "middle",
+                           collect_solutions: bool = False, sink_capacity: int = 4096):
         """pcp_dfs_forest_device_setform: dfs_forest_set for a store WITH formula propagators (Boolean / formula units) — the same loop, state
         and result dict, one tree per wavefront with its node in a slice of a CU's LDS (last_plan: block = 64 x trees per workgroup, path 3).
-        A store without formula propagators raises PCP_ERR_UNSUPPORTED (dfs_forest_set searches it), as dfs_forest_set does for one with."""
+        A store without formula propagators raises PCP_ERR_UNSUPPORTED (dfs_forest_set searches it), as dfs_forest_set does for one with.
+        ``collect_solutions`` / ``sink_capacity``: as for dfs_forest_set."""
         _check_brancher(brancher, val)
+        _check_collect_set("dfs_forest_setform", collect_solutions, sink_capacity)
 
         def launch(st, steps, stream):
             return self._L.pcp_dfs_forest_device_setform(self._h, C.byref(st), 1 if brancher == "enumerate" else 0, VAL_MODES.get(val, VAL_MIDDLE), steps,
                                                          int(bool(stop_on_solution)), int(node_limit), C.c_void_p(stream))
 
         return self._run_forest_set(root_bits, launch, node_limit=node_limit, steps_per_launch=steps_per_launch, level_capacity=level_capacity,
-                                    trail_capacity=trail_capacity, max_launches=max_launches, want_solution=want_solution, info=info, rebalance=rebalance)
+                                    trail_capacity=trail_capacity, max_launches=max_launches, want_solution=want_solution, info=info, rebalance=rebalance,
+                                    **(dict(collect=int(sink_capacity), stop_on_solution=stop_on_solution) if collect_solutions else {}))
 
     def _run_forest_set(self, root_bits, launch, node_limit: int = 0, steps_per_launch: int = 256, level_capacity: int = 0, trail_capacity: int = 0,
                         max_launches: int = 1 << 30, want_solution: bool = False, info: dict | None = None, rebalance: bool = True, live=None,
-                        ramp_steps: int = 0):
+                        ramp_steps: int = 0, collect: int = 0, stop_on_solution: bool = False, _sink=None):
         """The host side of the set-mode forest, shared by dfs_forest_set and dfs_forest_set_bnb: the forest's buffers, then launches of
         ``launch(st, steps, stream)`` (a pcp_dfs_forest_device_set* call, its return code) until every tree is finished, the forest stopped or
         max_launches is reached; between launches finished trees take work through pcp_dfs_forest_split_set.  ``live`` ([n_trees] bool or
         None = all): the trees that start with a root; the others start finished and only receive work.  ``ramp_steps`` > 0: launches of that
         many nodes while trees are still idle at the start, so that the splits fill them (at most 2 log2(n_trees) + 4 such launches).
-        Returns the result dict of dfs_forest_set."""
+        ``collect`` > 0 (with the caller's ``stop_on_solution``): a SetSolutionSink of that many rows is attached for the loop and detached
+        on every way out.  In this forest ``stop`` is ONE word for all trees, so after a launch the trees with error 6 are handed back — the
+        sink drained, their error word zeroed — and the stop word is cleared and the loop resumes only when error 6 is the SOLE cause of the
+        stop: no tree holds another error, the node limit is not reached, and no solution was counted under stop_on_solution.  Otherwise the
+        search ends as it would have, the handed-back nodes being uncounted open nodes of a stopped forest, and ``error`` reports the other
+        cause, or 0.  Returns the result dict of dfs_forest_set."""
         import torch
         dev = torch.device("cuda", self.device)
         V, sw = self.n_vars, self.set_words
+        if collect:
+            sink = SetSolutionSink(collect, V, sw, dev)
+            self.set_solution_sink_set(sink)
+            try:
+                out = self._run_forest_set(root_bits, launch, node_limit=node_limit, steps_per_launch=steps_per_launch, level_capacity=level_capacity,
+                                           trail_capacity=trail_capacity, max_launches=max_launches, want_solution=want_solution, info=info,
+                                           rebalance=rebalance, live=live, ramp_steps=ramp_steps, stop_on_solution=stop_on_solution, _sink=sink)
+                sink.drain()
+            finally:
+                self.set_solution_sink_set(None)
+            out["solutions_bits"], out["solution_tree"] = sink.rows()
+            return out
         # 0 = the model's own bound: a trail entry takes at least one value out of a set and is popped before the value can return, so a
         # tree never holds more entries (or open levels) than the root has values
         bound = V * sw * 64 + 16
@@ -921,7 +1007,7 @@ class Context:
         st = ForestState(T, level_capacity, trail_capacity, 0, bits.data_ptr(), tree.data_ptr(), levels.data_ptr(), trail.data_ptr(), counters.data_ptr(),
                          glob.data_ptr(), glob.data_ptr() + 8, sol.data_ptr() if want_solution else None, glob.data_ptr() + 16 if want_solution else None)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        launches = splits = 0
+        launches = splits = handed_back = 0
         ramp_left = (2 * max(T - 1, 1).bit_length() + 4) if ramp_steps else 0
         while launches < max_launches:
             self._check(launch(st, int(ramp_steps) if ramp_left else int(steps_per_launch), stream))
@@ -929,6 +1015,18 @@ class Context:
             g = glob.cpu().tolist()  # (the launch's only synchronisation)
             ts = tree.cpu().numpy()
             fin = (ts[:, 3] & 1) != 0
+            if _sink is not None and (g[1] & 0xFFFFFFFF):
+                cn = counters.cpu().numpy()
+                full = cn[:, 3] == SINK_FULL
+                if full.any():
+                    # hand the nodes back: the rows out, those trees' error word zeroed; resume only if nothing else stopped the forest
+                    _sink.drain()
+                    handed_back += int(full.sum())
+                    counters[torch.from_numpy(full).to(dev), 3] = 0
+                    other = (cn[~full, 3] != 0).any() or (node_limit and g[0] >= node_limit) or (stop_on_solution and cn[:, 1].sum() > 0)
+                    if not other:
+                        glob[1] = 0
+                        g[1] = 0
             if (g[1] & 0xFFFFFFFF) or (node_limit and g[0] >= node_limit) or fin.all():
                 break
             ramp_left = ramp_left - 1 if (ramp_left and fin.any()) else 0
@@ -947,6 +1045,8 @@ class Context:
         g = glob.cpu().tolist()
         if info is not None:
             info.update(trail_max=int(tree[:, 1].max().item()), levels_max=int(tree[:, 0].max().item()), trees=T, splits=splits)
+            if _sink is not None:
+                info.update(drains=_sink.drains, handed_back=handed_back, overdrawn=_sink.overdrawn)  # (equal: a ticket beyond the capacity is a node handed back)
         return {"nodes": int(cn[:, 0].sum()), "solutions": int(cn[:, 1].sum()), "failed": int(cn[:, 2].sum()), "error": int(cn[:, 3].max()),
                 "finished_trees": int((tree[:, 3] & 1).sum().item()), "splits": splits, "stopped": bool(g[1] & 0xFFFFFFFF), "launches": launches, "total_nodes": int(g[0]),
                 "first_solution": sol.cpu().numpy() if (want_solution and (g[2] & 0xFFFFFFFF)) else None, "per_tree": cn}
@@ -954,16 +1054,18 @@ class Context:
     @scoped_var_select()
     def dfs_forest_set_bnb(self, root_bits, objective, live=None, best0=None, brancher: str = "split", val: str = "middle", steps_per_launch: int = 256,
                            node_limit: int = 0, level_capacity: int = 0, trail_capacity: int = 0, rebalance: bool = True, info: dict | None = None,
-                           ramp_steps: int = 0, max_launches: int = 1 << 30, _entry: str = "pcp_dfs_forest_device_set_bnb"):
+                           ramp_steps: int = 0, max_launches: int = 1 << 30, collect_solutions: bool = False, _entry: str = "pcp_dfs_forest_device_set_bnb"):
         """pcp_dfs_forest_device_set_bnb: branch and bound (branch_and_bound.rs:64-84) in the set-mode forest — the loop of dfs_forest_set under
         either ``brancher``, every node entered with the forest's incumbent (one device word) folded into the set of the objective variable.
         ``objective`` = (var, "min" | "max").  ``live``: which trees start with a root ([n_trees] bool; None: all); the others start finished
         and receive work through pcp_dfs_forest_split_set.  ``best0``: a known bound to start from (only solutions that beat it are found).
         ``ramp_steps``: see _run_forest_set.  Returns the counters of dfs_forest_set (first_solution: None) plus ``best`` (None: no solution and
         no ``best0``), ``best_solution`` (the row of the lowest tree whose value is ``best``; None when no tree found one) and ``tree_best`` ([n_trees], a tree
-        without a solution: the "no solution yet" value)."""
+        without a solution: the "no solution yet" value).  ``collect_solutions=True`` is a ValueError: branch and bound keeps
+        ``best_solution``, and its entries refuse a set solution sink."""
         import torch
         _check_brancher(brancher, val)
+        _check_collect_set("dfs_forest_setform_bnb" if _entry.endswith("setform_bnb") else "dfs_forest_set_bnb", collect_solutions, 1, bnb=True)
         var, mode = objective
         if mode not in OBJ_MODES:
             raise ValueError(f"objective mode must be 'min' or 'max', not {mode!r}")
@@ -1046,6 +1148,16 @@ def _check_forest_brancher(who, brancher, val, small, dist, root_excl=None) -> b
     if root_excl is not None and not enum:
         raise ValueError(f"{who}: root_excl needs brancher='enumerate'")
     return enum
+
+
+def _check_collect_set(who, collect_solutions, sink_capacity, bnb=False):
+    """collect_solutions of a set-mode forest: both write into a set solution sink; branch and bound does not."""
+    if not collect_solutions:
+        return
+    if bnb:
+        raise ValueError(f"{who}: collect_solutions does not go with branch and bound (it keeps best_solution; the entries refuse a set solution sink)")
+    if int(sink_capacity) < 1:
+        raise ValueError(f"{who}: sink_capacity must be at least 1, not {sink_capacity}")
 
 
 def _check_collect(who, collect_solutions, sink_capacity, small, formulas, dist, bnb=False):

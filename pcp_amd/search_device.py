@@ -367,6 +367,7 @@ class DeviceSearch:
         from .engine import full_active, no_incumbent
         from .model import interval_bits
         self.solutions_ub = []  # advance(keep_bounds=True): the upper bounds of stats.solutions, row for row
+        self.solutions_bits = []  # advance(keep_bits=True): the sets of stats.solutions, row for row ([V, set_words] uint64 each)
         if self.bits is not None:
             self.base = int(base)
             self.bits[0] = torch.from_numpy(interval_bits(np.asarray(lb0), np.asarray(ub0), self.set_words, self.base).view(np.int64)).to(self.dev)
@@ -389,7 +390,7 @@ class DeviceSearch:
         ctx.stats_reset(self._stream())
 
     def advance(self, all_solutions: bool = True, node_limit: int = 0, max_rounds: int = 0, keep_solutions: int = 0, batch: int = 0, stop_at: int = 0,
-                keep_bounds: bool = False) -> bool:
+                keep_bounds: bool = False, keep_bits: bool = False) -> bool:
         """Run rounds on the current stack until it is empty, a limit is hit, or (not all_solutions) a solution is
         found.  Returns True when the search is over (stack empty or solution found).
         ``node_limit`` is the search's StopNode limit (stop_node.rs:47-62): the node that reaches it is counted as a node and as nothing
@@ -398,12 +399,14 @@ class DeviceSearch:
         With an objective, ``all_solutions`` is ignored: branch and bound runs to the end of the search.
         ``keep_bounds`` (int32 rows only): every solution kept in ``stats.solutions`` also leaves its upper bounds in ``self.solutions_ub``, row
         for row (a True node of an interval store is a box; ``stats.solutions`` holds its lower corner, and the stats keep their fields).
+        ``keep_bits`` (set mode only): the same for IntervalSet stores — a True node is a product of sets, and every solution kept also leaves
+        its sets in ``self.solutions_bits``.
         A DeviceSearch built with ``var_select=`` runs them under that variable selector (engine.var_select_scope)."""
         from .engine import var_select_scope
         with var_select_scope(self.ctx, self.var_select):
-            return self._advance(all_solutions, node_limit, max_rounds, keep_solutions, batch, stop_at, keep_bounds)
+            return self._advance(all_solutions, node_limit, max_rounds, keep_solutions, batch, stop_at, keep_bounds, keep_bits)
 
-    def _advance(self, all_solutions, node_limit, max_rounds, keep_solutions, batch, stop_at, keep_bounds) -> bool:
+    def _advance(self, all_solutions, node_limit, max_rounds, keep_solutions, batch, stop_at, keep_bounds, keep_bits=False) -> bool:
         torch, ctx, st, kind = self.torch, self.ctx, self.stats, self.kind
         bnb = self.objective is not None
         all_solutions = all_solutions or bnb
@@ -463,6 +466,10 @@ class DeviceSearch:
                     if self.ub is None or self.set_words:
                         raise ValueError("keep_bounds needs int32 (lb, ub) rows of an interval store")
                     self.solutions_ub += list(self.ub[lo:top][rows].cpu().numpy())
+                if keep_bits:
+                    if self.bits is None:
+                        raise ValueError("keep_bits needs the sets of a set-mode store")
+                    self.solutions_bits += list(self.bits[lo:top][rows].cpu().numpy().view(np.uint64))
             # pop the parents; the children, already in left-first order (branch_reverse), become the new top segment
             self.segs[-1][1] = length - n
             kind.pop(buf, length == n)

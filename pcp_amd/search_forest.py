@@ -21,20 +21,28 @@ def share_of_budget(node_limit: int, seeded_nodes: int, rank: int, world: int) -
     return left // world + (1 if rank < left % world else 0)
 
 
-def seed_roots(ctx, lb0, ub0, base: int, want: int, brancher: str = "split", val: str = "middle"):
+def seed_roots(ctx, lb0, ub0, base: int, want: int, brancher: str = "split", val: str = "middle", collect_solutions: bool = False):
     """Breadth-first expansion of the root to at least `want` open nodes (or until the tree is exhausted) under the distributor
     ``brancher`` ("split": BinarySplit on MiddleVal; "enumerate": Enumerate on ``val``, "middle" or "min").
-    Returns (roots [k, V, set_words] int64 CUDA tensor, stats of the expansion)."""
+    Returns (roots [k, V, set_words] int64 CUDA tensor, stats of the expansion).
+    ``collect_solutions``: a third value is returned, the solutions the expansion found as products of sets: [n, V, set_words] uint64 numpy
+    (the stats' ``solutions`` hold the lower bounds only)."""
     from .search_device import DeviceSearch
     ds = DeviceSearch(ctx, batch=max(want, 1), capacity=4 * max(want, 1) + 64, implicit=True, brancher=brancher, val=val)
     ds.reset(lb0, ub0, base)
     while 0 < ds.size < want:
-        if ds.advance(all_solutions=True, max_rounds=1, keep_solutions=0):
+        if collect_solutions:
+            if ds.advance(all_solutions=True, max_rounds=1, keep_solutions=1 << 62, keep_bits=True):
+                break
+        elif ds.advance(all_solutions=True, max_rounds=1, keep_solutions=0):
             break
     ds.compact()
     k = ds.size
     roots = ds.bits[:k].clone()
     st = ds.stats
+    if collect_solutions:
+        shape = (int(ds.bits.shape[1]), int(ds.bits.shape[2]))
+        return roots, st, (np.stack(ds.solutions_bits).reshape((-1,) + shape) if ds.solutions_bits else np.zeros((0,) + shape, np.uint64))
     return roots, st
 
 
@@ -46,7 +54,7 @@ def trail_bound(ctx) -> int:
 @scoped_var_select()
 def forest_search_set(ctx, lb0, ub0, base: int = 0, node_limit: int = 0, n_trees: int = 512, steps_per_launch: int = 2048, rank: int = 0, world: int = 1,
                       trail_capacity: int = 0, level_capacity: int = 0, info: dict | None = None, brancher: str = "split", val: str = "middle",
-                      formulas: bool = False, rebalance: bool = True) -> dict:
+                      formulas: bool = False, rebalance: bool = True, collect_solutions: bool = False, sink_capacity: int = 4096) -> dict:
     """All solutions of the space below (lb0, ub0) — or the first `node_limit` nodes of this rank's share of it.
     brancher / val: the distributor of the expansion AND of the trees ("enumerate": Enumerate on MiddleVal or MinVal), so that their union is
     one tree of that distributor.
@@ -57,12 +65,22 @@ def forest_search_set(ctx, lb0, ub0, base: int = 0, node_limit: int = 0, n_trees
     n_vars * set_words * 64 at most.  (N-queens-1000: 1 024 000 entries = 16 MB per tree; a 100-variable model: 100 KB.)
     rebalance: between launches finished trees take work from the others (pcp_dfs_forest_split_set).
     Returns dict(nodes, solutions, failed, error, seeded_nodes, trees, launches, finished_trees, splits); with world > 1 the expansion's counters are
-    reported by rank 0 only, so that a sum over the ranks counts every node once."""
-    roots, st = seed_roots(ctx, lb0, ub0, base, n_trees * world, brancher=brancher, val=val)
+    reported by rank 0 only, so that a sum over the ranks counts every node once.
+    collect_solutions / sink_capacity (one rank; ``world`` > 1 is a ValueError): as for Context.dfs_forest_set — the result also holds
+    ``solutions_bits`` ([n, n_vars, set_words] uint64, every solution as a product of sets) and ``solution_tree`` ([n]; -1: a solution the
+    expansion found, they come first), and ``seeded_solutions`` counts those."""
+    if collect_solutions:
+        from .engine import _check_collect_set
+        _check_collect_set("forest_search_set", collect_solutions, sink_capacity)
+        if world > 1:
+            raise ValueError("forest_search_set: collect_solutions does not run on several ranks (gathering the sinks is not built)")
+    roots, st, *found = seed_roots(ctx, lb0, ub0, base, n_trees * world, brancher=brancher, val=val, **(dict(collect_solutions=True) if collect_solutions else {}))
     mine = roots[rank::world].contiguous()
     out = {"seeded_nodes": st.num_nodes if rank == 0 else 0, "trees": int(mine.shape[0]), "launches": 0,
            "nodes": st.num_nodes if rank == 0 else 0, "solutions": st.num_solution if rank == 0 else 0, "failed": st.num_failed_node if rank == 0 else 0,
            "error": 0, "finished_trees": 0, "splits": 0}
+    if collect_solutions:
+        out["solutions_bits"], out["solution_tree"], out["seeded_solutions"] = found[0], np.full(len(found[0]), -1, np.int32), len(found[0])
     budget = 0
     if node_limit:
         budget = share_of_budget(node_limit, st.num_nodes, rank, world)
@@ -73,9 +91,13 @@ def forest_search_set(ctx, lb0, ub0, base: int = 0, node_limit: int = 0, n_trees
     bound = trail_bound(ctx)
     run = ctx.dfs_forest_setform if formulas else ctx.dfs_forest_set
     r = run(mine, node_limit=budget, steps_per_launch=steps_per_launch, trail_capacity=trail_capacity or bound, level_capacity=level_capacity or min(bound, 1 << 14),
-            want_solution=False, info=info, brancher=brancher, val=val, rebalance=rebalance)
+            want_solution=False, info=info, brancher=brancher, val=val, rebalance=rebalance,
+            **(dict(collect_solutions=True, sink_capacity=sink_capacity) if collect_solutions else {}))
     out["nodes"] += r["nodes"]; out["solutions"] += r["solutions"]; out["failed"] += r["failed"]
     out["error"] = r["error"]; out["launches"] = r["launches"]; out["finished_trees"] = r["finished_trees"]; out["splits"] = r["splits"]
+    if collect_solutions:
+        for k in ("solutions_bits", "solution_tree"):
+            out[k] = np.concatenate([out[k], r[k]])
     return out
 
 
