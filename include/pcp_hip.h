@@ -152,7 +152,7 @@ uint32_t pcp_abi_version(void);
  *     formula trees, and return PCP_ERR_UNSUPPORTED for a store with formula propagators; pcp_dfs_forest_device_setform and _setform_bnb
  *     search exactly those stores and return it for a store without one.  pcp_dfs_forest_split_set serves both.
  *   THE SEARCH FORESTS, one row per kind of store:
- *     all-XNeqY, Interval            pcp_dfs_forest_device
+ *     all-XNeqY, Interval            pcp_dfs_forest_device, pcp_dfs_forest_device_neq_enum (any size the in-kernel search takes: N-queens-1000)
  *     formula units, Interval        pcp_dfs_forest_device_form, _form_bnb, _form_enum (what Cumulative::join builds: XEqYMulZ and Sum keep it here)
  *     records, IntervalSet           pcp_dfs_forest_device_set, _set_enum, _set_bnb
  *     formula units, IntervalSet     pcp_dfs_forest_device_setform, _setform_bnb
@@ -479,8 +479,8 @@ int32_t pcp_branch_device_set_enum(pcp_ctx* ctx, uint32_t n_nodes, const uint64_
  *   "neq_dfs" 0);  pcp_dfs_forest_device_set, _set_enum, _set_bnb, _setform, _setform_bnb;  pcp_dfs_forest_device_form, _form_bnb,
  *   _form_enum, _small, _small_bnb, _small_enum, with and without a solution sink.  pcp_dfs_forest_split_set depends on levels, not on the
  *   selector.
- * WHERE IT DOES NOT RUN: under PCP_VAR_INPUT_ORDER pcp_dfs_forest_device (the all-XNeqY in-kernel forest) and pcp_branch_device_cells (the
- *   packed-cell brancher) return PCP_ERR_UNSUPPORTED with a message naming the option and launch nothing. */
+ * WHERE IT DOES NOT RUN: under PCP_VAR_INPUT_ORDER pcp_dfs_forest_device and pcp_dfs_forest_device_neq_enum (the all-XNeqY in-kernel forest) and
+ *   pcp_branch_device_cells (the packed-cell brancher) return PCP_ERR_UNSUPPORTED with a message naming the option and launch nothing. */
 #define PCP_VAR_FIRST_SMALLEST 0u
 #define PCP_VAR_INPUT_ORDER 1u
 int32_t pcp_branch_device_excl(pcp_ctx* ctx, uint32_t n_nodes, const int32_t* lb, const int32_t* ub, const uint8_t* status,
@@ -734,6 +734,40 @@ int32_t pcp_dfs_forest_device_small_enum(pcp_ctx* ctx, const pcp_dfs_state* st, 
 int32_t pcp_dfs_forest_device_form_enum(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex,
                                         const pcp_forest_objective* obj, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
                                         void* hip_stream);
+/* Enumerate in the all-XNeqY forest of pcp_dfs_forest_device — Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>
+ * (search/branching/enumerate.rs:33-60, search/branching/brancher.rs:52-71) inside the assignment-driven kernel, one WORKGROUP per tree: the
+ * parameter list of pcp_dfs_forest_device_small_enum, for stores of any size pcp_dfs_forest_device accepts (N-queens-1000).
+ * STORES: those of pcp_dfs_forest_device — all-XNeqY, interval mode, implicit nodes, a variable store that fits the in-kernel search.
+ * TREES: tree t is slice t of `st`, laid out as for pcp_dfs_forest_device, `dirty` included (nullable; honoured under option "neq_hint").
+ * EXCLUSION STATE: `ex` exactly as pcp_dfs_forest_device_small_enum documents it — path[t][path_capacity], row_base[t][capacity],
+ *   row_excl[t][capacity], val in {PCP_VAL_MIDDLE, PCP_VAL_MIN}.  Node r of tree t is the row's bounds under path[t][0 .. row_base[t][r]) plus
+ *   row_excl[t][r]; row_base does not decrease with r; a root is row 0 with its list in path[t][0 .. k), row_base = k and no entry; entries are
+ *   never filtered out of the path.  A caller that moves a tree's bottom row to another tree moves its two words, its `dirty` word and the
+ *   first row_base[0] path entries along (the donor's path stays).
+ * NODE ORDER: the children are x = v, then x != v; the variable is FirstSmallestVar's; v is MiddleVal's or MinVal's value, or, when the node's
+ *   list already holds (x, v), the nearest value of [lb, ub] without an entry on x, m - k tried before m + k.  x != v at a bound is folded into
+ *   that bound; an interior one becomes the row's row_excl and joins the path when the row is popped.  With n_trees = 1 the nodes are those of
+ *   search.dfs_enumerate at batch 1, one for one, and between two calls sp, the rows [0, sp), row_base, row_excl, the path prefix of the top
+ *   row, the counters and stop are what pcp_dfs_forest_device_small_enum leaves after the same number of steps.  Both children carry
+ *   dirty = x: also an interior right child, which differs from its parent's fixpoint by one entry that narrows nothing.
+ * NODE STATUS: the node's entries are swept at the top of every round of its fixpoint (a value is removed only at a bound); an entry whose
+ *   value lies inside [lb, ub] keeps the node PCP_UNKNOWN; x assigned to an excluded value fails the node.
+ * Counters, StopNode (the limit node is a node, neither a solution nor a failure), first_solution and stop_on_solution are those of
+ * pcp_dfs_forest_device.  pcp_last_plan: as for pcp_dfs_forest_device (path 1, grid = n_trees).
+ * ERRORS (counters[t][3]): 1 — stack full: the node stays on the stack, propagated and uncounted (its row_base names its list, no entry);
+ *   3 — as in pcp_dfs_forest_device; 5 — a popped row has an entry and row_base == path_capacity: nothing is changed, the row stays on the
+ *   stack uncounted, stop is raised, and a caller that resumes with a larger path runs it then; 2 — a node the engine refused, also a path or
+ *   row entry with var >= n_vars or a row_base beyond path_capacity (never used as an index): the node is counted and popped, the tree stops
+ *   and the sticky violation flag is set.
+ * REFUSALS (nothing is launched; pcp_last_error names the reason).  PCP_ERR_ARG: a set-mode model; val > PCP_VAL_MIN; a null st, ex, row_base
+ *   or row_excl, a null stack buffer; a null path with path_capacity > 0; n_trees == 0; capacity < 2.  PCP_ERR_UNSUPPORTED: a store that is
+ *   not all-XNeqY (formula units: pcp_dfs_forest_device_form_enum; any other small store: pcp_dfs_forest_device_small_enum); explicit-active
+ *   nodes (option "implicit_active" 0); obj != NULL — there is no branch and bound in this forest (pcp_dfs_forest_device_small_enum); an
+ *   Interval solution sink attached; option var_select = PCP_VAR_INPUT_ORDER (both as pcp_dfs_forest_device refuses them).
+ *   n_steps == 0: PCP_OK, nothing is launched. */
+int32_t pcp_dfs_forest_device_neq_enum(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex,
+                                       const pcp_forest_objective* obj, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
+                                       void* hip_stream);
 /* The solution sink: every solution of an Interval forest, not only their number.  A device-side append buffer of (lb, ub) rows that every
  * tree of pcp_dfs_forest_device_form, pcp_dfs_forest_device_small, pcp_dfs_forest_device_small_enum and pcp_dfs_forest_device_form_enum
  * (the last two with obj == NULL) writes its solutions into — the visitor of AllSolution (search/engine/all_solution.rs), resp. OneSolution called in a loop (one_solution.rs:92-105).  A row is
@@ -754,7 +788,7 @@ int32_t pcp_dfs_forest_device_form_enum(pcp_ctx* ctx, const pcp_dfs_state* st, u
  * after any number of such hand-backs nodes / solutions / failed of every tree are what a sink that never fills leaves, and no solution is
  * lost or written twice.  Rows are in ticket order, which between trees is an order in time.
  * With a sink attached the branch-and-bound entries (pcp_dfs_forest_device_form_bnb, _small_bnb, _small_enum and _form_enum with obj != NULL: they keep
- * tree_row), the all-XNeqY forest pcp_dfs_forest_device and every set-mode forest entry (pcp_dfs_forest_device_set, _set_enum, _set_bnb,
+ * tree_row), the all-XNeqY forest pcp_dfs_forest_device / pcp_dfs_forest_device_neq_enum and every set-mode forest entry (pcp_dfs_forest_device_set, _set_enum, _set_bnb,
  * _setform, _setform_bnb) return PCP_ERR_UNSUPPORTED and launch nothing; with none attached every entry does what it did before.  (THIS
  * sink, of (lb, ub) rows, is meant: the set-mode forests write into a sink of their own, pcp_set_solution_sink below.)
  * A null lb, ub or count, capacity == 0, reserved != 0: PCP_ERR_ARG, and the sink attached before stays. */

@@ -1171,7 +1171,9 @@ int32_t pcp_dfs_forest_split_set(pcp_ctx* c, const pcp_forest_state* st, uint32_
 
 // The search loop of an all-XNeqY model inside the kernel (neqfix_kernel<.., DFS>): workgroup t runs tree t, n_steps nodes per launch.
 // Returns 1 when launched, 0 when this model / store cannot take the path, < 0 on error.
-static int32_t launch_neq_dfs(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, hipStream_t stream) {
+// ex != nullptr: under Enumerate (pcp_dfs_forest_device_neq_enum: neqfix_kernel<.., DFS, .., EXCL>), each tree with its exclusion path.
+static int32_t launch_neq_dfs(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, hipStream_t stream,
+                              const pcp_forest_excl* ex = nullptr) {
   if (!(c->neq_model && c->opt_neq_path && c->opt_neq_dfs)) return 0;
   const uint32_t S = c->n_slots, V = c->n_vars;
   // 32-bit cells: a one-node tile has LDS to spare, and the 16-bit-cell instantiation of the search loop needs 147 VGPRs — one
@@ -1197,6 +1199,7 @@ static int32_t launch_neq_dfs(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_tr
   a.dfs.sp = st->sp; a.dfs.stop = st->stop; a.dfs.counters = reinterpret_cast<unsigned long long*>(st->counters); a.dfs.first_solution = st->first_solution;
   a.dfs.dirty = c->opt_neq_hint ? st->dirty : nullptr;
   a.dfs.capacity = st->capacity; a.dfs.n_steps = n_steps; a.dfs.stop_on_solution = stop_on_solution; a.dfs.node_limit = node_limit;
+  if (ex) { a.en.path = ex->path; a.en.row_base = ex->row_base; a.en.row_excl = ex->row_excl; a.en.path_capacity = ex->path_capacity; a.en.val = ex->val; }
   LaunchPlan plan;
   plan.grid = n_trees; plan.block = c->opt_neq_dfs_block ? (uint32_t)c->opt_neq_dfs_block : (n_trees > 1 ? (many ? 128u : 256u) : 512u); plan.lds_bytes = lds;
   c->last_plan = pcp_plan{1u, 1u, packed ? 1u : 0u, 0u, 0u, 0u, 1u, 0u, n_trees, plan.block, (uint32_t)plan.lds_bytes, S, 1u};
@@ -1220,6 +1223,33 @@ int32_t pcp_dfs_forest_device(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_tr
   const int32_t rc = launch_neq_dfs(c, st, n_trees, n_steps, stop_on_solution, node_limit, reinterpret_cast<hipStream_t>(hip_stream));
   if (rc < 0) return rc;
   if (rc == 0 && n_steps) return fail(c, PCP_ERR_UNSUPPORTED, "pcp_dfs_forest_device needs an all-XNeqY model whose variable store fits the in-kernel search (pcp_dfs_device runs any model, one tree)");
+  return PCP_OK;
+}
+
+// Enumerate in the all-XNeqY forest (enumerate.rs:33-60, brancher.rs:52-71): the checks of pcp_dfs_forest_device and of the exclusion
+// state, then launch_neq_dfs with the trees' paths.  A store of another kind is named its entry.
+int32_t pcp_dfs_forest_device_neq_enum(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex, const pcp_forest_objective* obj,
+                                       uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
+  if (!c || !st || !ex) return c ? fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_neq_enum: null state / exclusions") : PCP_ERR_ARG;
+  const std::string who = "pcp_dfs_forest_device_neq_enum";
+  if (c->sink.lb) return refuse_sink(c, who, "the all-XNeqY forest does not write into it (pcp_dfs_forest_device_small_enum takes an all-XNeqY store within its limits)");
+  if (c->set_words) return fail(c, PCP_ERR_ARG, who + " runs interval-mode models (sets: pcp_dfs_forest_device_set_enum)");
+  if (obj) return fail(c, PCP_ERR_UNSUPPORTED, who + ": there is no branch and bound in the all-XNeqY forest (pcp_dfs_forest_device_small_enum runs one over a store within its limits)");
+  if (c->opt_var_select != PCP_VAR_FIRST_SMALLEST)
+    return fail(c, PCP_ERR_UNSUPPORTED, who + ": option var_select = PCP_VAR_INPUT_ORDER is not served by the all-XNeqY in-kernel search (pcp_dfs_forest_device_small_enum takes an all-XNeqY store within its limits)");
+  if (!n_trees || !st->lb || !st->ub || !st->sp || !st->stop || !st->status || !st->counters || st->capacity < 2)
+    return fail(c, PCP_ERR_ARG, who + ": null buffer / no tree / capacity < 2");
+  if (ex->val > PCP_VAL_MIN) return fail(c, PCP_ERR_ARG, who + ": val must be PCP_VAL_MIDDLE or PCP_VAL_MIN");
+  if (!ex->row_base || !ex->row_excl || (ex->path_capacity && !ex->path)) return fail(c, PCP_ERR_ARG, who + ": null row_base / row_excl / path");
+  HIP_TRY(c, hipSetDevice(c->device));
+  { const int32_t rcf = finalize_model(c); if (rcf) return rcf; }
+  if (c->has_formulas) return fail(c, PCP_ERR_UNSUPPORTED, who + " searches all-XNeqY stores: a store with formula propagators is searched by pcp_dfs_forest_device_form_enum");
+  if (!c->neq_model) return fail(c, PCP_ERR_UNSUPPORTED, who + " searches all-XNeqY stores: a small store of plain propagators of other kinds is searched by pcp_dfs_forest_device_small_enum");
+  if (!c->opt_implicit) return fail(c, PCP_ERR_UNSUPPORTED, who + " searches implicit nodes: explicit-active nodes (option implicit_active 0) are not served by the in-kernel search");
+  if (c->opt_force_path) return fail(c, PCP_ERR_UNSUPPORTED, who + ": force_path is set");
+  const int32_t rc = launch_neq_dfs(c, st, n_trees, n_steps, stop_on_solution, node_limit, reinterpret_cast<hipStream_t>(hip_stream), ex);
+  if (rc < 0) return rc;
+  if (rc == 0 && n_steps) return fail(c, PCP_ERR_UNSUPPORTED, who + " needs an all-XNeqY model whose variable store fits the in-kernel search (options neq_path / neq_dfs on)");
   return PCP_OK;
 }
 

@@ -45,6 +45,13 @@ struct NeqArgs {
   pcp_stats* stats;
   const uint32_t* excl_off;     // pcp_propagate_device_excl: [n_nodes + 1] CSR offsets into excl, or null (then the EXCL kernels are not launched)
   const pcp_excl* excl;         //   the nodes' own value exclusions x(var) != value (Enumerate's right branches), 8 bytes each
+  struct {                      // dfs.n_steps > 0 and row_base != null: the search loop runs under Enumerate (pcp_dfs_forest_device_neq_enum, the DFS && EXCL kernels)
+    pcp_excl* path;             //   [trees][path_capacity]: the exclusions along each tree's current path — the current node's list is path[t][0 .. n)
+    uint32_t* row_base;         //   [trees][dfs.capacity]: the path entries a stack row inherits
+    pcp_excl* row_excl;         //   [trees][dfs.capacity]: the entry appended when the row is popped (var 0xFFFFFFFF: none)
+    uint32_t path_capacity;
+    uint32_t val;               //   PCP_VAL_MIDDLE / PCP_VAL_MIN
+  } en;                         // (the last member: the kernel arguments in front of it keep their offsets)
 };
 size_t lds_bytes_neq(uint32_t n_slots, uint32_t n_vars, uint32_t nodes_per_block, bool packed, uint32_t wgs = 2);
 hipError_t launch_neqfix(const NeqArgs& a, const LaunchPlan& p, hipStream_t stream);

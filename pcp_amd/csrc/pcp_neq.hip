@@ -545,13 +545,18 @@ __device__ __forceinline__ uint32_t neq_write_back(const Tile& tl, const int32_t
 // step (ctr.ev); the first pass of the first sweep stands for the initial schedule (ev0).  An entry with var >= n_vars refuses its node.
 // Packed cells: a value outside +-kPackedMax is in no domain.  int2 cells: staging refuses a node with a bound beyond +-kBoundMax (2^29 - 1), so
 // a value that equals a bound is within that range and lb + 1 / ub - 1 cannot overflow.
-template <bool PACKED, class Tile>
-__device__ __forceinline__ void neq_excl_sweep(const Tile& tl, const NeqArgs& a, Ctr& ctr, uint32_t& ev0, const bool first) {
+// TREE (the search loop under Enumerate, DFS && EXCL): the tile's one node is the tree's current node and its list is the tree's path,
+// a.excl[0 .. n_tree) — no offsets are read.
+template <bool PACKED, bool TREE, class Tile>
+__device__ __forceinline__ void neq_excl_sweep(const Tile& tl, const NeqArgs& a, Ctr& ctr, uint32_t& ev0, const bool first, const uint32_t n_tree = 0) {
   const uint32_t inert = tl.misc[N_FAIL] | tl.misc[N_OOB];
   for (uint32_t b = tl.wv; b < tl.nb; b += tl.nwv) {
     if ((inert >> b) & 1u) continue;  // (wave-uniform)
-    const uint32_t nid = tl.misc[N_NID + b];
-    const uint32_t e0 = (uint32_t)__builtin_amdgcn_readfirstlane(a.excl_off[nid]), e1 = (uint32_t)__builtin_amdgcn_readfirstlane(a.excl_off[nid + 1]);
+    uint32_t e0 = 0, e1 = n_tree;
+    if constexpr (!TREE) {
+      const uint32_t nid = tl.misc[N_NID + b];
+      e0 = (uint32_t)__builtin_amdgcn_readfirstlane(a.excl_off[nid]); e1 = (uint32_t)__builtin_amdgcn_readfirstlane(a.excl_off[nid + 1]);
+    }
     const auto dm = tl.dom_of(b, &ctr);
     for (uint32_t pass = 0;; ++pass) {
       bool moved = false, malformed = false;
@@ -577,13 +582,16 @@ __device__ __forceinline__ void neq_excl_sweep(const Tile& tl, const NeqArgs& a,
 }
 // ... and their part of the status (store.rs:250-256): x != value is entailed iff value lies outside [lb, ub] (x_neq_y.rs:71-73); at a
 // fixpoint that did not fail a value inside is strictly inside.  One wavefront per node that is neither failed nor refused.
-template <bool PACKED, class Tile>
-__device__ __forceinline__ void neq_excl_status(const Tile& tl, const NeqArgs& a) {
+template <bool PACKED, bool TREE, class Tile>
+__device__ __forceinline__ void neq_excl_status(const Tile& tl, const NeqArgs& a, const uint32_t n_tree = 0) {
   const uint32_t inert = tl.misc[N_FAIL] | tl.misc[N_OOB];
   for (uint32_t b = tl.wv; b < tl.nb; b += tl.nwv) {
     if ((inert >> b) & 1u) continue;
-    const uint32_t nid = tl.misc[N_NID + b];
-    const uint32_t e0 = (uint32_t)__builtin_amdgcn_readfirstlane(a.excl_off[nid]), e1 = (uint32_t)__builtin_amdgcn_readfirstlane(a.excl_off[nid + 1]);
+    uint32_t e0 = 0, e1 = n_tree;
+    if constexpr (!TREE) {
+      const uint32_t nid = tl.misc[N_NID + b];
+      e0 = (uint32_t)__builtin_amdgcn_readfirstlane(a.excl_off[nid]); e1 = (uint32_t)__builtin_amdgcn_readfirstlane(a.excl_off[nid + 1]);
+    }
     bool open = false;
     for (uint32_t i = e0 + tl.lane; i < e1; i += 64u) {
       const pcp_excl x = a.excl[i];
@@ -637,13 +645,61 @@ struct NeqDfsRegs {
   uint32_t sp, stop, resume_var, hint, err;
   unsigned long long nodes, sols, fail;
   uint32_t stale;  // the node on top of the stack is in LDS only (a left child whose row was not pushed): its write-back writes the whole row
+  uint32_t n;      // Enumerate (DFS && EXCL): the entries of the current node's list, path[0 .. n) — re-derived from the top row at every pop
 };
 
 // ---- the search step on the node the tile has just propagated: OneSolution / AllSolution over Propagation<Brancher<FirstSmallestVar,
 // MiddleVal, BinarySplit>> (one_solution.rs:92-105, brancher.rs:52-71) under StopNode (stop_node.rs:47-62).  `a` points at the node's
 // row (lb_out / ub_out: row sp - 1 of the tree's stack).  Count it; failed / solution: pop; Unknown: the right child x > v over the
 // parent's row, the left child x <= v on top and — its domains being in LDS already — marked as the node to continue with.
-template <bool PACKED, class Tile>
+constexpr uint32_t kNeqNoExcl = 0xFFFFFFFFu;  // row_excl[r].var: the row appends nothing when it is popped
+
+// Enumerate's value on `var` = [lo, hi] of a node whose list is path[0 .. n) (enumerate.rs:47-60; the rule of row_dfs, pcp_rowdfs.hpp, for a
+// workgroup-wide tree): MinVal's value is lo (min_val.rs:25-27) — a bound, and at a fixpoint no bound is excluded: the sweep would have
+// removed it — so no scan runs; MiddleVal's (middle_val.rs:25-27) is kept unless the list already holds (var, it): then the nearest value of
+// [lo, hi] without an entry on `var`, m - k before m + k.  Every thread strides the path, a wavefront votes by ballot and the workgroup by
+// one word per wavefront in the idle round list (as the key reduction does).  n, lo, hi, the candidates and the votes are workgroup-uniform,
+// so every barrier is reached by all threads.  Every candidate inside [lo, hi] that is not free uses up an entry of its own: at most n + 1
+// scans of n entries, whatever the width of the domain.
+template <class Tile>
+__device__ __forceinline__ int neq_enum_value(const Tile& tl, const NeqArgs& a, const uint32_t n, const uint32_t var, const int lo, const int hi) {
+  if (a.en.val == PCP_VAL_MIN) return lo;
+  const int mid = (int)(((long long)lo + (long long)hi) / 2);  // `/` truncates toward zero like Rust's
+  if (!n) return mid;
+  uint32_t* const vote = reinterpret_cast<uint32_t*>(tl.list);
+  // bit 0: the list holds (var, c0); bit 1: it holds (var, c1)
+  auto held = [&](const int c0, const int c1) -> uint32_t {
+    bool h0 = false, h1 = false;
+    for (uint32_t i = tl.tid; i < n; i += tl.nth) {
+      const pcp_excl e = a.excl[i];
+      h0 |= e.var == var && e.value == c0;
+      h1 |= e.var == var && e.value == c1;
+    }
+    const uint32_t mine = (__ballot(h0) ? 1u : 0u) | (__ballot(h1) ? 2u : 0u);
+    if (tl.lane == 0) vote[tl.wv] = mine;
+    __syncthreads();
+    uint32_t all = vote[0];
+    for (uint32_t w = 1; w < tl.nwv; ++w) all |= vote[w];
+    __syncthreads();
+    return all;
+  };
+  if (!(held(mid, mid) & 1u)) return mid;
+  for (int k = 1;; ++k) {
+    const int c0 = mid - k, c1 = mid + k;
+    const bool in0 = c0 >= lo, in1 = c1 <= hi;
+    if (!in0 && !in1) return mid;  // (every value excluded: not at a fixpoint, see above)
+    const uint32_t h = held(c0, c1);
+    if (in0 && !(h & 1u)) return c0;
+    if (in1 && !(h & 2u)) return c1;
+  }
+}
+
+// ENUM (DFS && EXCL, pcp_dfs_forest_device_neq_enum): the same step under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate>
+// (enumerate.rs:33-60, brancher.rs:52-71).  The children are x = v and x != v.  The right child x != v takes the parent's row: folded into
+// the bound v sits at (one word of the row), else the row as it is and the entry (var, v) as the row's row_excl; either way row_base = n, the
+// parent's list.  The left child x = v is one LDS cell and the node to continue with, the path unchanged.  A row that stays on the stack as
+// the node it is (error 1 or 3, the left child at the end of a launch) has its list in the path already: row_base = n and no entry.
+template <bool PACKED, bool ENUM, class Tile>
 __device__ __forceinline__ void neq_dfs_step(const Tile& tl, const NeqArgs& a, NeqDfsRegs& r, const bool last_step) {
   const bool failed = (tl.misc[N_FAIL] & 1u) != 0, refused = (tl.misc[N_OOB] & 1u) != 0, open = (tl.misc[N_UNK] & 1u) != 0;
   r.resume_var = 0xFFFFFFFFu;
@@ -680,6 +736,8 @@ __device__ __forceinline__ void neq_dfs_step(const Tile& tl, const NeqArgs& a, N
     key = best[0];
     for (uint32_t w = 1; w < tl.nwv; ++w) key = min(key, best[w]);
     __syncthreads();
+    if constexpr (ENUM)  // (errors 3 and 1 below: the node stays on the stack as it is, its list in the path already)
+      if ((key == ~0ull || r.sp >= a.dfs.capacity) && tl.tid == 0) { a.en.row_base[r.sp - 1] = r.n; a.en.row_excl[r.sp - 1] = pcp_excl{kNeqNoExcl, 0}; }
     if (key == ~0ull) {
       r.err = 3; r.stop = 1;  // Unknown, yet nothing to branch on: the reference panics (first_smallest_var.rs:36)
       new_sp = r.sp;
@@ -690,13 +748,28 @@ __device__ __forceinline__ void neq_dfs_step(const Tile& tl, const NeqArgs& a, N
       ++r.nodes;
       const uint32_t var = (uint32_t)key;
       const int2 d = cell_bounds<PACKED>(tl.dom[tl.rowof(var)]);
-      const int val = (int)(((long long)d.x + (long long)d.y) / 2);  // MiddleVal (middle_val.rs:25-27: `/` truncates toward zero)
-      // the right child x > val takes the parent's row (which holds the fixpoint: written back above if it changed)
-      if (tl.tid == 0) a.lb_out[var] = max(d.x, val + 1);
-      if (tl.tid == 0 && a.dfs.dirty) { a.dfs.dirty[r.sp - 1] = var; a.dfs.dirty[r.sp] = var; }  // both children differ from this fixpoint in `var`
-      // the left child x <= val: one bound of one LDS cell, and its row on top of the stack
-      if (tl.tid == 0) {
-        if constexpr (PACKED) tl.dom[tl.rowof(var)] = pack16(d.x, min(d.y, val)); else tl.dom[tl.rowof(var)] = make_int2(-d.x, min(d.y, val));
+      if constexpr (ENUM) {
+        const int v = neq_enum_value(tl, a, r.n, var, d.x, d.y);
+        const bool at_lb = v == d.x, at_ub = v == d.y;  // (never both: the variable has more than one value)
+        if (tl.tid == 0) {
+          // the right child x != v over the parent's row (which holds the fixpoint: written back above if it changed)
+          if (at_lb) a.lb_out[var] = v + 1; else if (at_ub) a.ub_out[var] = v - 1;
+          a.en.row_base[r.sp - 1] = r.n;
+          a.en.row_excl[r.sp - 1] = (at_lb || at_ub) ? pcp_excl{kNeqNoExcl, 0} : pcp_excl{var, v};
+          // both children differ from this fixpoint in `var` (an interior x != v by one entry that narrows nothing)
+          if (a.dfs.dirty) { a.dfs.dirty[r.sp - 1] = var; a.dfs.dirty[r.sp] = var; }
+          // the left child x = v: one LDS cell
+          if constexpr (PACKED) tl.dom[tl.rowof(var)] = pack16(v, v); else tl.dom[tl.rowof(var)] = make_int2(-v, v);
+        }
+      } else {
+        const int val = (int)(((long long)d.x + (long long)d.y) / 2);  // MiddleVal (middle_val.rs:25-27: `/` truncates toward zero)
+        // the right child x > val takes the parent's row (which holds the fixpoint: written back above if it changed)
+        if (tl.tid == 0) a.lb_out[var] = max(d.x, val + 1);
+        if (tl.tid == 0 && a.dfs.dirty) { a.dfs.dirty[r.sp - 1] = var; a.dfs.dirty[r.sp] = var; }  // both children differ from this fixpoint in `var`
+        // the left child x <= val: one bound of one LDS cell, and its row on top of the stack
+        if (tl.tid == 0) {
+          if constexpr (PACKED) tl.dom[tl.rowof(var)] = pack16(d.x, min(d.y, val)); else tl.dom[tl.rowof(var)] = make_int2(-d.x, min(d.y, val));
+        }
       }
       __syncthreads();
       // The left child is the next node of this very loop and is propagated from LDS; the write-back of ITS fixpoint puts its row on the
@@ -707,6 +780,8 @@ __device__ __forceinline__ void neq_dfs_step(const Tile& tl, const NeqArgs& a, N
         int32_t* l0 = a.lb_out + tl.V;
         int32_t* u0 = a.ub_out + tl.V;
         for (uint32_t v = tl.tid; v < tl.V; v += tl.nth) { const int2 c = cell_bounds<PACKED>(tl.dom[tl.rowof(v)]); l0[v] = c.x; u0[v] = c.y; }
+        if constexpr (ENUM)
+          if (tl.tid == 0) { a.en.row_base[r.sp] = r.n; a.en.row_excl[r.sp] = pcp_excl{kNeqNoExcl, 0}; }
       } else {
         r.stale = 1u;
       }
@@ -1623,7 +1698,13 @@ __device__ __forceinline__ void neq_stage_tile(const Tile& tl, const NeqArgs& a,
 // not a run-time test: the ticket's registers cost the 16 384-node headline launch — which never draws — 16 B of scratch per lane in round 5.
 // EXCL: the nodes carry value exclusions of their own (NeqArgs::excl_off / excl, pcp_propagate_device_excl): neq_excl_sweep at the top of every
 // round, neq_excl_status behind the status scan.  Everything it adds sits under `if constexpr (EXCL)`; instantiated for batch launches with a
-// run-time tile size, int32 rows and a fixed tile stride only (DFS = false, BT = 0, CELLS = false, TICKETS = false).
+// run-time tile size, int32 rows and a fixed tile stride (DFS = false, BT = 0, CELLS = false, TICKETS = false), and
+// DFS && EXCL: the search loop under Brancher<FirstSmallestVar, MiddleVal | MinVal, Enumerate> (search/branching/enumerate.rs:33-60,
+// brancher.rs:52-71; pcp_dfs_forest_device_neq_enum), for int2 cells and both payload formats.  A tree keeps ONE exclusion path in HBM and
+// two words per stack row (NeqArgs::en — the state of row_dfs<.., ENUM, ..>, pcp_rowdfs.hpp): a popped row's entry is appended at
+// path[row_base], so the current node's list is the contiguous slice path[0 .. dfs.n) and the sweep and the status read it from there instead
+// of excl_off[nid].  The step chooses Enumerate's value against that list (neq_enum_value) and writes the children's row words (neq_dfs_step).
+// Everything it adds sits under `if constexpr (DFS && EXCL)` resp. the TREE / ENUM flags of the functions it calls.
 template <bool PACKED, bool PAY4, bool DFS, int BT, bool CELLS = false, bool TICKETS = false, bool EXCL = false>
 __global__ void __launch_bounds__(DFS ? 512 : 1024) __attribute__((amdgpu_waves_per_eu(4))) neqfix_kernel(const NeqArgs a_in) {  // (four wavefronts per SIMD: the forest runs 16 per CU)
   NeqArgs a = a_in;
@@ -1712,6 +1793,10 @@ __global__ void __launch_bounds__(DFS ? 512 : 1024) __attribute__((amdgpu_waves_
     a.dfs.sp += blockIdx.x; a.dfs.stop += blockIdx.x; a.dfs.counters += (size_t)blockIdx.x * 5;
     if (a.dfs.first_solution) a.dfs.first_solution += (size_t)blockIdx.x * V;
     if (a.dfs.dirty) a.dfs.dirty += tree_row0;
+    if constexpr (EXCL) {  // the tree's exclusion path — the list source of the sweep and of the status (a.excl[0 .. dfs.n)) — and its rows' two words
+      a.en.path += (size_t)blockIdx.x * a_in.en.path_capacity; a.excl = a.en.path;
+      a.en.row_base += tree_row0; a.en.row_excl += tree_row0;
+    }
   }
   unsigned long long acc_steps = 0, acc_narrow = 0, acc_ev = 0, acc_full = 0, acc_waves = 0, acc_nodes = 0, acc_failed = 0;  // DFS: pcp_stats, per launch
   if constexpr (DFS) { dfs.sp = *a.dfs.sp; dfs.stop = *a.dfs.stop; dfs.nodes = a.dfs.counters[0]; dfs.sols = a.dfs.counters[1]; dfs.fail = a.dfs.counters[2]; }
@@ -1753,6 +1838,32 @@ __global__ void __launch_bounds__(DFS ? 512 : 1024) __attribute__((amdgpu_waves_
     // a popped row: the variable it was branched on, if the stack keeps them (pcp_dfs_state.dirty) — it is a propagated parent with that
     // one variable moved, so its first round is that variable's lists (the rows of this very launch are read past the L1, like the bounds)
     dfs.hint = (!resume && a.dfs.dirty) ? __hip_atomic_load(a.dfs.dirty + (dfs.sp - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xFFFFFFFFu;
+    if constexpr (EXCL) {
+      // Enumerate: a popped row's list is the path prefix it inherits plus its own entry, appended at path[row_base] (the left child in LDS
+      // keeps its parent's list: nothing to do).  Every thread reads the same two words (past the L1, like the rows), so the checks are
+      // workgroup-uniform, and they come BEFORE anything is staged or stored: a refused pop leaves HBM untouched.  The entry's store is
+      // followed by the zeroing barrier and the staging barrier below before the first sweep reads the path.
+      if (!resume) {
+        const uint32_t top = dfs.sp - 1;
+        const uint32_t* const ow = reinterpret_cast<const uint32_t*>(a.en.row_excl + top);
+        const uint32_t base = __hip_atomic_load(a.en.row_base + top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t ovar = __hip_atomic_load(ow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), oval = __hip_atomic_load(ow + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (base > a.en.path_capacity || (ovar != kNeqNoExcl && ovar >= V)) {
+          // malformed, never used as an index: the node is counted and popped, the tree stops (error 2, the sticky flag)
+          if (tid == 0) atomicMax(a.violation, 1u);
+          ++dfs.nodes; dfs.err = 2; dfs.stop = 1; dfs.sp = top;
+          break;
+        }
+        if (ovar != kNeqNoExcl) {
+          // 5: the exclusion path is full — the row stays on the stack, uncounted: a caller that resumes with a larger path runs it then
+          if (base == a.en.path_capacity) { dfs.err = 5; dfs.stop = 1; break; }
+          if (tid == 0) a.en.path[base] = pcp_excl{ovar, (int32_t)oval};
+          dfs.n = base + 1;
+        } else {
+          dfs.n = base;
+        }
+      }
+    }
   }
   if (tid < (uint32_t)N_WORDS) misc[tid] = 0;
   if (tid == (uint32_t)N_R0OVF || (tid >= (uint32_t)N_VOTE && tid < (uint32_t)N_VOTE + 3u)) misc[tid] = 0;
@@ -1911,7 +2022,7 @@ __global__ void __launch_bounds__(DFS ? 512 : 1024) __attribute__((amdgpu_waves_
     // — except the jumps (neq_apply_jumps may land a bound on an excluded value, without a mark when the jump was quiet): they are followed
     // by another round, i.e. by another sweep.  The kMaxRounds refusal above stands.
     if constexpr (EXCL) {
-      neq_excl_sweep<PACKED>(NeqTile<PACKED>{dom, chg, misc, adjo, list, win, V, Wv, B, sh, nb, tid, lane, wv, nwv, nth}, a, ctr, ev0, round == 0);
+      neq_excl_sweep<PACKED, DFS>(NeqTile<PACKED>{dom, chg, misc, adjo, list, win, V, Wv, B, sh, nb, tid, lane, wv, nwv, nth}, a, ctr, ev0, round == 0, dfs.n);
       bar();
       inert = misc[N_FAIL] | misc[N_OOB];
     }
@@ -1986,7 +2097,7 @@ __global__ void __launch_bounds__(DFS ? 512 : 1024) __attribute__((amdgpu_waves_
   // chains one after the other in every wavefront.
   if (fstate != 3u) {
     neq_status_scan<PACKED, DFS>(tl, pay, (a.debug & 2u) != 0);
-    if constexpr (EXCL) neq_excl_status<PACKED>(tl, a);  // (a node with an exclusion whose value is still inside its variable's domain is Unknown)
+    if constexpr (EXCL) neq_excl_status<PACKED, DFS>(tl, a, dfs.n);  // (a node with an exclusion whose value is still inside its variable's domain is Unknown)
     if constexpr (!DFS && TICKETS) { if (tid == nth - 64u && draws()) misc_base[kNextTileWord] = neq_karg<uint32_t>(offsetof(NeqArgs, tile_static)) * gridDim.x + 8u * ticket + (blockIdx.x & 7u); }
   }
 
@@ -2031,7 +2142,9 @@ __global__ void __launch_bounds__(DFS ? 512 : 1024) __attribute__((amdgpu_waves_
     const unsigned long long s2 = (unsigned long long)active_nodes * a.m.n_recs + *reinterpret_cast<unsigned long long*>(&misc[N_STEPS]);
     const unsigned long long sev = *reinterpret_cast<unsigned long long*>(&misc[N_EV]), sfu = *reinterpret_cast<unsigned long long*>(&misc[N_FULL]);
     const uint32_t nf = __popc(misc[N_FAIL] & (nb >= 32 ? 0xFFFFFFFFu : ((1u << nb) - 1u)));
-    if constexpr (EXCL) {  // the initial schedule of a node holds its own exclusions too: one step each (the later tests are in N_STEPS / tot_later)
+    if constexpr (EXCL && DFS) {  // (the tree's current node: its list is the path, dfs.n entries)
+      if (!(misc[N_OOB] & 1u)) acc_steps += dfs.n;
+    } else if constexpr (EXCL) {  // the initial schedule of a node holds its own exclusions too: one step each (the later tests are in N_STEPS / tot_later)
       unsigned long long xs = 0;
       for (uint32_t b = 0; b < nb; ++b)
         if (!((misc[N_OOB] >> b) & 1u)) xs += a.excl_off[misc[N_NID + b] + 1] - a.excl_off[misc[N_NID + b]];
@@ -2084,7 +2197,7 @@ __global__ void __launch_bounds__(DFS ? 512 : 1024) __attribute__((amdgpu_waves_
   } else {
     // ---- the search step on the node just propagated (what dfs_step_kernel does for the generic kernels) ---------------------
     bar();
-    neq_dfs_step<PACKED>(NeqTile<PACKED>{dom, chg, misc, adjo, list, win, V, Wv, B, sh, nb, tid, lane, wv, nwv, nth}, a, dfs, dfs_it + 1u >= a.dfs.n_steps);
+    neq_dfs_step<PACKED, EXCL>(NeqTile<PACKED>{dom, chg, misc, adjo, list, win, V, Wv, B, sh, nb, tid, lane, wv, nwv, nth}, a, dfs, dfs_it + 1u >= a.dfs.n_steps);
     bar();
   }
   }  // the DFS loop / the tile loop
@@ -2241,6 +2354,12 @@ hipError_t launch_neqfix(const NeqArgs& a, const LaunchPlan& p, hipStream_t stre
   if (a.nodes_per_block == 0 || a.nodes_per_block > 16 || a.m.n_slots >= 65536u || !a.m.adjp) return hipErrorInvalidValue;
   if (a.dfs.n_steps) {
     if (a.nodes_per_block != 1 || p.grid < 1 || !a.dfs.sp || !a.dfs.stop || !a.dfs.counters) return hipErrorInvalidValue;  // (grid = trees)
+    if (a.en.row_base) {
+      // ... under Enumerate (pcp_dfs_forest_device_neq_enum): the two DFS && EXCL kernels — int2 cells, which is what the search loop is
+      // launched with (launch_neq_dfs, pcp_api.hip), and either payload format
+      if (a.packed || !a.en.row_excl || (a.en.path_capacity && !a.en.path) || a.excl_off) return hipErrorInvalidValue;
+      return a.adjp4 ? launch_neq_t<false, true, true, 1, false, false, true>(a, p, stream) : launch_neq_t<false, false, true, 1, false, false, true>(a, p, stream);
+    }
     return launch_neq_d<true, 1>(a, p, stream);
   }
   if (a.excl_off) {

@@ -28,7 +28,7 @@ ERRORS = {-1: "PCP_ERR_ARG", -2: "PCP_ERR_CONTRACT", -3: "PCP_ERR_HIP", -4: "PCP
 ABI_SYMBOLS = [
     "pcp_ctx_create", "pcp_ctx_destroy", "pcp_last_error", "pcp_strerror", "pcp_abi_version",
     "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull",
-    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_form_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_set_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
+    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_form_enum", "pcp_dfs_forest_device_neq_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_set_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
 ]
 
 
@@ -269,6 +269,7 @@ def load_library():
     L.pcp_dfs_forest_device_small_bnb.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestObjective), u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_small_enum.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestExcl), C.POINTER(ForestObjective), u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_form_enum.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestExcl), C.POINTER(ForestObjective), u32, u32, C.c_uint64, vp]
+    L.pcp_dfs_forest_device_neq_enum.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestExcl), C.POINTER(ForestObjective), u32, u32, C.c_uint64, vp]
     L.pcp_solution_sink_set.argtypes = [vp, C.POINTER(PcpSolutionSink)]
     L.pcp_set_solution_sink_set.argtypes = [vp, C.POINTER(PcpSetSolutionSink)]
     L.pcp_stats_reset.argtypes = [vp, vp]
@@ -278,7 +279,7 @@ def load_library():
     L.pcp_last_plan.argtypes = [vp, C.POINTER(PcpPlan)]
     L.pcp_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
     for f in ("pcp_ctx_create", "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull", "pcp_model_set_hull",
-              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_form_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_set_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
+              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_form_enum", "pcp_dfs_forest_device_neq_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_set_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
         getattr(L, f).restype = i32
     _lib = L
     return L
@@ -353,6 +354,32 @@ def scoped_var_select(refuse=None):
     return deco
 
 
+def _const_operands(props) -> list:
+    """Per filter of a lowered table, the values of its Constant operands (var == PCP_CONST: the value is the operand's offset)."""
+    is_const = props["var"] == 0xFFFFFFFF
+    return [tuple(int(o) for o, c in zip(off, cst) if c) for off, cst in zip(props["off"], is_const)] if is_const.any() else [()] * len(props)
+
+
+FOREST_KINDS = (None, "neq", "small", "form")  # dfs_forest_enum / forest_enumerate(forest=): chosen by the store, or one entry forced
+
+
+def _neq_enum_forest(a) -> str:
+    """The refusal of dfs_forest_enum / forest_enumerate under InputOrder when the all-XNeqY forest is asked for by name."""
+    if a.get("forest") != "neq":
+        return ""
+    return "is not served by the all-XNeqY forest (pcp_dfs_forest_device_neq_enum selects FirstSmallestVar only): forest='small' runs an all-XNeqY store within the small-store limits"
+
+
+def _check_neq_enum(who, objective, collect_solutions, var_select):
+    """What the all-XNeqY Enumerate forest (pcp_dfs_forest_device_neq_enum) does not do, raised before anything runs."""
+    if objective is not None:
+        raise ValueError(f"{who}: there is no branch and bound in the all-XNeqY forest (forest='small' runs one over a store within the small-store limits)")
+    if collect_solutions:
+        raise ValueError(f"{who}: the all-XNeqY forest writes into no solution sink (forest='small' collects the solutions of a store within the small-store limits)")
+    if var_select == "input_order":
+        raise ValueError(f"{who}: var_select='input_order' " + _neq_enum_forest({"forest": "neq"}))
+
+
 def _xneq_forest(a) -> str:
     """The refusal of dfs_forest / forest_search under InputOrder: neither ``formulas`` nor ``small`` (nor the Enumerate forest chosen by the
     store) is the all-XNeqY in-kernel forest, pcp_dfs_forest_device."""
@@ -382,6 +409,7 @@ class Context:
         self.supports_set_enumerate = True  # pcp_branch_device_set_enum / pcp_dfs_forest_device_set_enum: Enumerate over set-mode stores
         self._neq_flags = []  # per elementary filter pushed: an XNeqY outside a formula with a variable among its operands (all_neq)
         self._form_flags = []  # per elementary filter pushed: a leaf of a formula unit, or a Boolean / BooleanNeg (has_formulas)
+        self._const_ops = []  # per elementary filter pushed: the values of its Constant operands (each distinct value is one interned slot: beyond_small_limits)
         for kv in filter(None, os.environ.get("PCP_SET_OPTIONS", "").split(",")):  # experiments: pcp_set_option on every new context (k=v,k=v)
             k_, v_ = kv.split("=")
             self.set_option(k_, int(v_))
@@ -406,7 +434,7 @@ class Context:
         self._check(self._L.pcp_model_reset(self._h, n_vars, int(set_words)))
         self.n_vars = int(n_vars)
         self.set_words = int(set_words)
-        self._neq_flags, self._form_flags = [], []
+        self._neq_flags, self._form_flags, self._const_ops = [], [], []
         for members in (sums or []):  # term::Sum views, numbered in order (pcp_model_push_sum)
             mv = np.ascontiguousarray(members, np.uint32)
             t = C.c_uint32()
@@ -421,13 +449,14 @@ class Context:
             plain = lambda v: (v < 0xC0000000) | (v == 0xFFFFFFFF)  # a variable or a Constant: no term::Sum view (PCP_SUM)
             self._neq_flags += ((props["kind"] == 0) & plain(x) & plain(y) & ((x < 0xC0000000) | (y < 0xC0000000))).tolist()
             self._form_flags += (props["kind"] >= 7).tolist()  # PCP_BOOL, PCP_NBOOL
+            self._const_ops += _const_operands(props)
         self._refresh()
 
     # ---- the push interface pcp_amd.model.push_model drives (stores with formula propagators) ------------------------------
     def reset_model(self, n_vars: int, set_words: int = 0):
         self._check(self._L.pcp_model_reset(self._h, n_vars, int(set_words)))
         self.n_vars, self.set_words = int(n_vars), int(set_words)
-        self._neq_flags, self._form_flags = [], []
+        self._neq_flags, self._form_flags, self._const_ops = [], [], []
         self._refresh()
 
     def push_sum(self, members) -> int:
@@ -444,6 +473,7 @@ class Context:
         self._check(self._L.pcp_model_push_formula(self._h, len(nodes), _np_ptr(nodes), len(leaves), _np_ptr(leaves)))
         self._neq_flags += [False] * len(leaves)
         self._form_flags += [True] * len(leaves)
+        self._const_ops += _const_operands(leaves)
         self._refresh()
 
     def set_hull(self, lo: int, hi: int):
@@ -461,12 +491,20 @@ class Context:
         self.words = (self.n_units + 63) // 64
         del self._neq_flags[self.n_props:]  # (truncate keeps a prefix of the filters)
         del self._form_flags[self.n_props:]
+        del self._const_ops[self.n_props:]
 
     @property
     def all_neq(self) -> bool:
         """Every elementary filter of the store is a plain XNeqY with a variable among its operands: the models the assignment-driven kernel
         takes (pcp_propagate_device_excl).  The search drivers choose between that entry and pcp_propagate_device_small_excl by it."""
         return bool(self._neq_flags) and len(self._neq_flags) == self.n_props and all(self._neq_flags)
+
+    @property
+    def beyond_small_limits(self) -> bool:
+        """The store is larger than the small-store kernels take — more than 128 slots (variables and distinct Constant operands) or more
+        than 2048 elementary filters: what pcp_dfs_forest_device_small_enum answers with PCP_ERR_UNSUPPORTED, decided here from the store's
+        shape so that dfs_forest_enum need not launch to find out."""
+        return self.n_vars + len({c for ops in self._const_ops for c in ops}) > 128 or self.n_props > 2048
 
     @property
     def has_formulas(self) -> bool:
@@ -762,7 +800,8 @@ class Context:
         status = torch.zeros((T, capacity), dtype=torch.uint8, device=dev)
         counters = torch.zeros((T, 5), dtype=torch.int64, device=dev)
         sol = torch.zeros((T, V), dtype=torch.int32, device=dev) if want_solution else None
-        dirty = torch.full((T, capacity), -1, dtype=torch.int32, device=dev) if (hints and not formulas and not small) else None  # pcp_dfs_state.dirty: one word per stack row
+        # pcp_dfs_state.dirty: one word per stack row — the all-XNeqY forest's, under either distributor (the small-store and formula-store forests keep none)
+        dirty = torch.full((T, capacity), -1, dtype=torch.int32, device=dev) if (hints and not formulas and not small) else None
         from .search_forest import ForestStacks, run_forest_loop
         stream = torch.cuda.current_stream(dev).cuda_stream
         box = {}
@@ -876,11 +915,11 @@ class Context:
         out["best_solution"] = tree_row[int(winners[0])].cpu().numpy() if len(winners) else None
         return out
 
-    @scoped_var_select()
+    @scoped_var_select(refuse=_neq_enum_forest)
     def dfs_forest_enum(self, root_lb, root_ub, val: str = "middle", objective=None, best0=None, root_excl=None, path_capacity: int = 64, max_path: int = 1 << 20,
                         collect_solutions: bool = False, sink_capacity: int = 4096, stop_on_solution: bool = False, node_limit_per_tree: int = 0,
                         steps_per_launch: int = 256, capacity: int = 2048, max_launches: int = 1 << 30, node_budget: int = 0, want_solution: bool = False,
-                        rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0):
+                        rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0, forest=None, hints: bool = True):
         """The Enumerate forest over this context's Interval store, chosen by what the store IS (as search.dfs_enumerate and DeviceSearch
         dispatch): pcp_dfs_forest_device_form_enum when it holds formula units (``has_formulas`` — schedules, what Cumulative.join builds),
         else pcp_dfs_forest_device_small_enum.  The trees run under Enumerate on MiddleVal (``val="middle"``) or MinVal (``"min"``); roots,
@@ -889,18 +928,33 @@ class Context:
         under branch and bound, ``best0`` a known bound to start from; the result then also holds the keys of dfs_forest_bnb (``best``,
         ``best_solution``, ``tree_best``), and ``stop_on_solution`` / ``want_solution`` do not apply.  One rank: ``dist`` is a ValueError,
         as are a ``val`` other than "middle" / "min", ``collect_solutions`` with an objective, and a ``root_excl`` whose length is not the
-        number of roots."""
+        number of roots.
+        ``forest`` (None / "neq" / "small" / "form"; anything else a ValueError): None chooses by the store — "form" with formula units, "neq"
+        for an all-XNeqY store beyond the small-store limits (``all_neq`` and ``beyond_small_limits``: decided on the host from the store's
+        shape, nothing is launched to find out), else "small"; a name forces that entry.  "neq" is the all-XNeqY in-kernel forest,
+        pcp_dfs_forest_device_neq_enum: one workgroup per tree, any all-XNeqY store the in-kernel search takes (N-queens-1000; forced, small
+        N-queens too), the stack rows with their ``dirty`` words (``hints=False``: without them — the same tree), which grow and are stolen
+        together with ``row_base``, ``row_excl`` and the path prefix.  It has no branch and bound, writes into no solution sink and selects
+        FirstSmallestVar only: ``objective``, ``collect_solutions`` and ``var_select="input_order"`` are a ValueError before anything runs."""
+        if forest not in FOREST_KINDS:
+            raise ValueError(f"dfs_forest_enum: forest must be None, 'neq', 'small' or 'form', not {forest!r}")
         if dist is not None:
             raise ValueError("dfs_forest_enum: Enumerate does not run on several ranks (moving exclusion lists between ranks is not built)")
         if val not in VAL_MODES:
             raise ValueError(f"dfs_forest_enum: val must be 'middle' or 'min', not {val!r}")
         if collect_solutions and objective is not None:
             raise ValueError("dfs_forest_enum: collect_solutions does not go with an objective (branch and bound keeps best_solution; its entries refuse a solution sink)")
-        form = self.has_formulas
-        entry = self._L.pcp_dfs_forest_device_form_enum if form else self._L.pcp_dfs_forest_device_small_enum
+        if forest == "neq":
+            _check_neq_enum("dfs_forest_enum", objective, collect_solutions, None)
+        if forest is None:
+            forest = "form" if self.has_formulas else "neq" if (self.all_neq and self.beyond_small_limits) else "small"
+        if forest == "neq":
+            _check_neq_enum("dfs_forest_enum", objective, collect_solutions, self.var_select)
+        form = forest == "form"
+        entry = {"form": self._L.pcp_dfs_forest_device_form_enum, "small": self._L.pcp_dfs_forest_device_small_enum, "neq": self._L.pcp_dfs_forest_device_neq_enum}[forest]
         kw = dict(node_limit_per_tree=node_limit_per_tree, steps_per_launch=steps_per_launch, capacity=capacity, max_launches=max_launches, node_budget=node_budget,
-                  rebalance=rebalance, info=info, max_capacity=max_capacity, small=not form, brancher="enumerate", val=val, root_excl=root_excl,
-                  path_capacity=path_capacity, max_path=max_path, _enum_entry=entry)
+                  rebalance=rebalance, info=info, max_capacity=max_capacity, small=forest == "small", brancher="enumerate", val=val, root_excl=root_excl,
+                  path_capacity=path_capacity, max_path=max_path, _enum_entry=entry, **(dict(hints=hints) if forest == "neq" else {}))
         if objective is not None:
             return self.dfs_forest_bnb(root_lb, root_ub, objective, best0=best0, **kw)
         return self.dfs_forest(root_lb, root_ub, stop_on_solution=stop_on_solution, want_solution=want_solution, formulas=form,
@@ -1142,7 +1196,7 @@ def _check_forest_brancher(who, brancher, val, small, dist, root_excl=None) -> b
     _check_brancher(brancher, val)
     enum = brancher == "enumerate"
     if enum and not small:
-        raise ValueError(f"{who}: brancher='enumerate' needs small=True here (the small-store forest; the all-XNeqY forest stays on BinarySplit) — Context.dfs_forest_enum / search_forest.forest_enumerate run Enumerate over either Interval store, the formula-store forest included")
+        raise ValueError(f"{who}: brancher='enumerate' needs small=True here (the small-store forest) — Context.dfs_forest_enum / search_forest.forest_enumerate run Enumerate over every Interval store: the formula-store forest and the all-XNeqY in-kernel forest included")
     if enum and dist is not None:
         raise ValueError(f"{who}: brancher='enumerate' does not run on several ranks (moving exclusion lists between ranks is not built)")
     if root_excl is not None and not enum:

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .engine import _xneq_forest, scoped_var_select
+from .engine import _neq_enum_forest, _xneq_forest, scoped_var_select
 
 
 def share_of_budget(node_limit: int, seeded_nodes: int, rank: int, world: int) -> int:
@@ -576,10 +576,10 @@ def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: i
     return out
 
 
-@scoped_var_select()
+@scoped_var_select(refuse=_neq_enum_forest)
 def forest_enumerate(ctx, lb0, ub0, val: str = "middle", objective=None, n_trees: int = 256, steps_per_launch: int = 512, best0=None, collect_solutions: bool = False,
                      sink_capacity: int = 4096, info: dict | None = None, capacity: int = 128, max_capacity: int = 1 << 16, path_capacity: int = 64, rebalance: bool = True,
-                     dist=None) -> dict:
+                     dist=None, forest=None) -> dict:
     """Enumerate over the context's Interval store, whichever forest it belongs to — the formula-store forest (``ctx.has_formulas``:
     schedules, what Cumulative.join builds) or the small-store one: the root is expanded breadth-first under
     DeviceSearch(brancher="enumerate", val=, objective=) to at least ``n_trees`` open nodes (seed_roots_interval), each becomes a tree of
@@ -588,17 +588,30 @@ def forest_enumerate(ctx, lb0, ub0, val: str = "middle", objective=None, n_trees
     (``collect_solutions`` / ``sink_capacity``: every solution as a box, the expansion's first); with ``objective`` = (var, "min" | "max") it
     is forest_bnb(brancher="enumerate") and returns its dict (``best0``: a known bound to start from).  ``capacity`` / ``max_capacity``: a tree's stack rows, at first and at most; ``path_capacity``: its
     exclusion path at first (both grow on demand).  One rank: ``dist`` is a
-    ValueError, as are a ``val`` other than "middle" / "min" and ``collect_solutions`` with an objective."""
-    from .engine import VAL_MODES
+    ValueError, as are a ``val`` other than "middle" / "min" and ``collect_solutions`` with an objective.
+    ``forest`` (None / "neq" / "small" / "form"): the keyword and the choice of Context.dfs_forest_enum — None sends an all-XNeqY store
+    beyond the small-store limits (N-queens-1000) to the all-XNeqY in-kernel forest, pcp_dfs_forest_device_neq_enum, "neq" any all-XNeqY
+    store; the expansion runs under DeviceSearch(brancher="enumerate") as for the others and the roots keep their lists.  That forest takes
+    no ``objective``, no ``collect_solutions`` and no ``var_select="input_order"``: a ValueError before anything runs."""
+    from .engine import FOREST_KINDS, VAL_MODES, _check_neq_enum
+    if forest not in FOREST_KINDS:
+        raise ValueError(f"forest_enumerate: forest must be None, 'neq', 'small' or 'form', not {forest!r}")
     if dist is not None:
         raise ValueError("forest_enumerate: Enumerate does not run on several ranks (moving exclusion lists between ranks is not built)")
     if val not in VAL_MODES:
         raise ValueError(f"forest_enumerate: val must be 'middle' or 'min', not {val!r}")
     if collect_solutions and objective is not None:
         raise ValueError("forest_enumerate: collect_solutions does not go with an objective (branch and bound returns best_solution)")
-    form = ctx.has_formulas
+    if forest == "neq":
+        _check_neq_enum("forest_enumerate", objective, collect_solutions, None)
+    if forest is None:  # (the choice of Context.dfs_forest_enum, made here so that the refusals come before the expansion runs)
+        forest = "form" if ctx.has_formulas else "neq" if (ctx.all_neq and ctx.beyond_small_limits) else "small"
+    if forest == "neq":
+        _check_neq_enum("forest_enumerate", objective, collect_solutions, ctx.var_select)
+    form = forest == "form"
+    by_store = dict(path_capacity=path_capacity, rebalance=rebalance, forest=forest)
     if objective is not None:
         return forest_bnb(ctx, lb0, ub0, objective, n_trees=n_trees, steps_per_launch=steps_per_launch, best0=best0, capacity=capacity, max_capacity=max_capacity,
-                          info=info, formulas=form, small=not form, brancher="enumerate", val=val, _by_store=dict(path_capacity=path_capacity, rebalance=rebalance))
-    return forest_search(ctx, lb0, ub0, n_trees=n_trees, steps_per_launch=steps_per_launch, capacity=capacity, info=info, formulas=form, small=not form,
-                         brancher="enumerate", val=val, collect_solutions=collect_solutions, sink_capacity=sink_capacity, _by_store=dict(path_capacity=path_capacity, rebalance=rebalance))
+                          info=info, formulas=form, small=not form, brancher="enumerate", val=val, _by_store=by_store)
+    return forest_search(ctx, lb0, ub0, n_trees=n_trees, steps_per_launch=steps_per_launch, capacity=capacity, info=info, formulas=form, small=forest == "small",
+                         brancher="enumerate", val=val, collect_solutions=collect_solutions, sink_capacity=sink_capacity, _by_store=by_store)
