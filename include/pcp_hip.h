@@ -152,7 +152,7 @@ uint32_t pcp_abi_version(void);
  *     formula trees, and return PCP_ERR_UNSUPPORTED for a store with formula propagators; pcp_dfs_forest_device_setform and _setform_bnb
  *     search exactly those stores and return it for a store without one.  pcp_dfs_forest_split_set serves both.
  *   THE SEARCH FORESTS, one row per kind of store:
- *     all-XNeqY, Interval            pcp_dfs_forest_device, pcp_dfs_forest_device_neq_enum (any size the in-kernel search takes: N-queens-1000)
+ *     all-XNeqY, Interval            pcp_dfs_forest_device, pcp_dfs_forest_device_neq_enum, _neq_sink (any size the in-kernel search takes: N-queens-1000)
  *     formula units, Interval        pcp_dfs_forest_device_form, _form_bnb, _form_enum (what Cumulative::join builds: XEqYMulZ and Sum keep it here)
  *     records, IntervalSet           pcp_dfs_forest_device_set, _set_enum, _set_bnb
  *     formula units, IntervalSet     pcp_dfs_forest_device_setform, _setform_bnb
@@ -788,7 +788,9 @@ int32_t pcp_dfs_forest_device_neq_enum(pcp_ctx* ctx, const pcp_dfs_state* st, ui
  * after any number of such hand-backs nodes / solutions / failed of every tree are what a sink that never fills leaves, and no solution is
  * lost or written twice.  Rows are in ticket order, which between trees is an order in time.
  * With a sink attached the branch-and-bound entries (pcp_dfs_forest_device_form_bnb, _small_bnb, _small_enum and _form_enum with obj != NULL: they keep
- * tree_row), the all-XNeqY forest pcp_dfs_forest_device / pcp_dfs_forest_device_neq_enum and every set-mode forest entry (pcp_dfs_forest_device_set, _set_enum, _set_bnb,
+ * tree_row), the all-XNeqY entries pcp_dfs_forest_device / pcp_dfs_forest_device_neq_enum — that forest writes its solutions through
+ * pcp_dfs_forest_device_neq_sink, below, which takes its sink as an argument and refuses an attached one like them — and every set-mode forest
+ * entry (pcp_dfs_forest_device_set, _set_enum, _set_bnb,
  * _setform, _setform_bnb) return PCP_ERR_UNSUPPORTED and launch nothing; with none attached every entry does what it did before.  (THIS
  * sink, of (lb, ub) rows, is meant: the set-mode forests write into a sink of their own, pcp_set_solution_sink below.)
  * A null lb, ub or count, capacity == 0, reserved != 0: PCP_ERR_ARG, and the sink attached before stays. */
@@ -801,6 +803,31 @@ typedef struct {
   uint32_t reserved;
 } pcp_solution_sink;
 int32_t pcp_solution_sink_set(pcp_ctx* ctx, const pcp_solution_sink* sink);
+/* Every solution of the all-XNeqY forest — the visitor of AllSolution (search/engine/all_solution.rs) inside the assignment-driven kernel,
+ * one WORKGROUP per tree.  The sink is an ARGUMENT OF THE CALL: the struct is read at the call and nothing is retained, the context's own
+ * attachment (pcp_solution_sink_set) keeps its meaning, and this entry refuses it as pcp_dfs_forest_device and
+ * pcp_dfs_forest_device_neq_enum do — one rule for every all-XNeqY entry.
+ * ex == NULL: BinarySplit — stores, trees, node order, counters, StopNode, first_solution, stop_on_solution and errors 1, 2, 3 are those of
+ *   pcp_dfs_forest_device.  ex != NULL: Enumerate — all of that, the exclusion state and error 5 are those of
+ *   pcp_dfs_forest_device_neq_enum (with obj == NULL: there is no branch and bound in this forest).
+ * THE PROTOCOL is pcp_solution_sink's, above.  A True node (not the StopNode limit node, which is none and draws no ticket:
+ *   stop_node.rs:57-62) draws slot = (*count)++ BEFORE it is counted.  slot < capacity: the WHOLE node goes to row slot — in interval mode a
+ *   True node of an all-XNeqY store is a box (x in [0,1], y in [3,4], x != y is entailed at the root), every point of it a solution —,
+ *   tree[slot] = t, and the step goes on as without a sink.  slot >= capacity: error 6 in counters[t][3] — nothing is counted, the node stays
+ *   on the stack as row sp - 1 at its fixpoint (under Enumerate its row_base names the list it ran under, row_excl no entry, as for errors 1
+ *   and 3), stop[t] is raised.  A caller that copies the rows out, zeroes *count, clears that tree's error and stop and calls again runs the
+ *   node again — propagating a fixpoint changes nothing, its `dirty` word is still valid — and it is counted and appended then.  After any
+ *   number of such hand-backs nodes / solutions / failed of every tree are those of pcp_dfs_forest_device resp. _neq_enum on the same roots,
+ *   and no solution is lost or written twice.  The valid rows are min(*count, capacity), in ticket order; rows beyond them are not touched.
+ * REFUSALS (nothing is launched; pcp_last_error names the reason).  PCP_ERR_ARG: a null sink, lb, ub or count, capacity == 0,
+ *   reserved != 0; a null st or stack buffer, n_trees == 0, capacity < 2; a set-mode model; with ex: val > PCP_VAL_MIN, a null row_base or
+ *   row_excl, a null path with path_capacity > 0.  PCP_ERR_UNSUPPORTED: an Interval solution sink attached to the context; option
+ *   var_select = PCP_VAR_INPUT_ORDER; explicit-active nodes (option "implicit_active" 0); a store that is not all-XNeqY (their forests write
+ *   into the context's sink) or does not fit the in-kernel search.  n_steps == 0: PCP_OK, nothing is launched.
+ * (Added without a new PCP_ABI_VERSION: a symbol more, no layout changed, every call that ran before runs as it did.) */
+int32_t pcp_dfs_forest_device_neq_sink(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex,
+                                       const pcp_solution_sink* sink, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
+                                       void* hip_stream);
 /* TWO SINKS.  pcp_solution_sink, above, is the Interval forests': rows of (lb, ub).  While it is attached every set-mode forest entry
  * returns PCP_ERR_UNSUPPORTED, as said there — its rows cannot hold a set.  pcp_set_solution_sink, here, is the set-mode forests': every
  * solution of pcp_dfs_forest_device_set, _set_enum and _setform (both distributors), not only their number and the first one's lower

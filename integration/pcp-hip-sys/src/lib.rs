@@ -296,6 +296,9 @@ extern "C" {
     pub fn pcp_dfs_forest_device_neq_enum(ctx: *mut pcp_ctx, st: *const pcp_dfs_state, n_trees: u32, ex: *const pcp_forest_excl,
                                           obj: *const pcp_forest_objective, n_steps: u32, stop_on_solution: u32, node_limit: u64,
                                           hip_stream: *mut c_void) -> i32; // Enumerate in the all-XNeqY forest, one workgroup per tree; obj must be null
+    pub fn pcp_dfs_forest_device_neq_sink(ctx: *mut pcp_ctx, st: *const pcp_dfs_state, n_trees: u32, ex: *const pcp_forest_excl,
+                                          sink: *const pcp_solution_sink, n_steps: u32, stop_on_solution: u32, node_limit: u64,
+                                          hip_stream: *mut c_void) -> i32; // the all-XNeqY forest writing every solution into the sink of the call; ex null: BinarySplit
     pub fn pcp_dfs_forest_device_set(ctx: *mut pcp_ctx, st: *const pcp_forest_state, n_steps: u32, stop_on_solution: u32, node_limit: u64,
                                      hip_stream: *mut c_void) -> i32;
     pub fn pcp_dfs_forest_device_set_enum(ctx: *mut pcp_ctx, st: *const pcp_forest_state, val: u32, n_steps: u32, stop_on_solution: u32,

@@ -1172,8 +1172,9 @@ int32_t pcp_dfs_forest_split_set(pcp_ctx* c, const pcp_forest_state* st, uint32_
 // The search loop of an all-XNeqY model inside the kernel (neqfix_kernel<.., DFS>): workgroup t runs tree t, n_steps nodes per launch.
 // Returns 1 when launched, 0 when this model / store cannot take the path, < 0 on error.
 // ex != nullptr: under Enumerate (pcp_dfs_forest_device_neq_enum: neqfix_kernel<.., DFS, .., EXCL>), each tree with its exclusion path.
+// sink != nullptr: every solution goes to the call's sink (pcp_dfs_forest_device_neq_sink: neqfix_kernel<.., DFS, .., SINK>).
 static int32_t launch_neq_dfs(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, hipStream_t stream,
-                              const pcp_forest_excl* ex = nullptr) {
+                              const pcp_forest_excl* ex = nullptr, const pcp_solution_sink* sink = nullptr) {
   if (!(c->neq_model && c->opt_neq_path && c->opt_neq_dfs)) return 0;
   const uint32_t S = c->n_slots, V = c->n_vars;
   // 32-bit cells: a one-node tile has LDS to spare, and the 16-bit-cell instantiation of the search loop needs 147 VGPRs — one
@@ -1200,6 +1201,7 @@ static int32_t launch_neq_dfs(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_tr
   a.dfs.dirty = c->opt_neq_hint ? st->dirty : nullptr;
   a.dfs.capacity = st->capacity; a.dfs.n_steps = n_steps; a.dfs.stop_on_solution = stop_on_solution; a.dfs.node_limit = node_limit;
   if (ex) { a.en.path = ex->path; a.en.row_base = ex->row_base; a.en.row_excl = ex->row_excl; a.en.path_capacity = ex->path_capacity; a.en.val = ex->val; }
+  if (sink) a.sink = SinkDev{sink->lb, sink->ub, sink->tree, sink->count, sink->capacity};
   LaunchPlan plan;
   plan.grid = n_trees; plan.block = c->opt_neq_dfs_block ? (uint32_t)c->opt_neq_dfs_block : (n_trees > 1 ? (many ? 128u : 256u) : 512u); plan.lds_bytes = lds;
   c->last_plan = pcp_plan{1u, 1u, packed ? 1u : 0u, 0u, 0u, 0u, 1u, 0u, n_trees, plan.block, (uint32_t)plan.lds_bytes, S, 1u};
@@ -1248,6 +1250,39 @@ int32_t pcp_dfs_forest_device_neq_enum(pcp_ctx* c, const pcp_dfs_state* st, uint
   if (!c->opt_implicit) return fail(c, PCP_ERR_UNSUPPORTED, who + " searches implicit nodes: explicit-active nodes (option implicit_active 0) are not served by the in-kernel search");
   if (c->opt_force_path) return fail(c, PCP_ERR_UNSUPPORTED, who + ": force_path is set");
   const int32_t rc = launch_neq_dfs(c, st, n_trees, n_steps, stop_on_solution, node_limit, reinterpret_cast<hipStream_t>(hip_stream), ex);
+  if (rc < 0) return rc;
+  if (rc == 0 && n_steps) return fail(c, PCP_ERR_UNSUPPORTED, who + " needs an all-XNeqY model whose variable store fits the in-kernel search (options neq_path / neq_dfs on)");
+  return PCP_OK;
+}
+
+// Every solution of the all-XNeqY forest (the visitor of AllSolution, search/engine/all_solution.rs): the checks of pcp_dfs_forest_device
+// (ex == NULL) resp. pcp_dfs_forest_device_neq_enum and of the sink, which is an argument of the call — the context's own sink keeps being
+// refused by every all-XNeqY entry, this one included; then launch_neq_dfs with the sink.
+int32_t pcp_dfs_forest_device_neq_sink(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex, const pcp_solution_sink* sink,
+                                       uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit, void* hip_stream) {
+  if (!c || !st) return c ? fail(c, PCP_ERR_ARG, "pcp_dfs_forest_device_neq_sink: null state") : PCP_ERR_ARG;
+  const std::string who = "pcp_dfs_forest_device_neq_sink";
+  if (!sink) return fail(c, PCP_ERR_ARG, who + ": null sink (pcp_dfs_forest_device / pcp_dfs_forest_device_neq_enum count without one)");
+  if (!sink->lb || !sink->ub || !sink->count) return fail(c, PCP_ERR_ARG, who + ": the sink's lb, ub and count are required");
+  if (!sink->capacity) return fail(c, PCP_ERR_ARG, who + ": the sink's capacity must be at least one row");
+  if (sink->reserved) return fail(c, PCP_ERR_ARG, who + ": the sink's reserved must be 0");
+  if (c->sink.lb) return refuse_sink(c, who, "the all-XNeqY forest does not write into it (this entry writes into the sink of the call)");
+  if (c->set_words) return fail(c, PCP_ERR_ARG, who + " runs interval-mode models (sets: pcp_dfs_forest_device_set with pcp_set_solution_sink_set)");
+  if (c->opt_var_select != PCP_VAR_FIRST_SMALLEST)
+    return fail(c, PCP_ERR_UNSUPPORTED, who + ": option var_select = PCP_VAR_INPUT_ORDER is not served by the all-XNeqY in-kernel search (pcp_dfs_forest_device_small takes an all-XNeqY store within its limits)");
+  if (!n_trees || !st->lb || !st->ub || !st->sp || !st->stop || !st->status || !st->counters || st->capacity < 2)
+    return fail(c, PCP_ERR_ARG, who + ": null buffer / no tree / capacity < 2");
+  if (ex) {
+    if (ex->val > PCP_VAL_MIN) return fail(c, PCP_ERR_ARG, who + ": val must be PCP_VAL_MIDDLE or PCP_VAL_MIN");
+    if (!ex->row_base || !ex->row_excl || (ex->path_capacity && !ex->path)) return fail(c, PCP_ERR_ARG, who + ": null row_base / row_excl / path");
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  { const int32_t rcf = finalize_model(c); if (rcf) return rcf; }
+  if (c->has_formulas) return fail(c, PCP_ERR_UNSUPPORTED, who + " searches all-XNeqY stores: a store with formula propagators writes its solutions through pcp_solution_sink_set and pcp_dfs_forest_device_form");
+  if (!c->neq_model) return fail(c, PCP_ERR_UNSUPPORTED, who + " searches all-XNeqY stores: a small store of plain propagators of other kinds writes its solutions through pcp_solution_sink_set and pcp_dfs_forest_device_small");
+  if (!c->opt_implicit) return fail(c, PCP_ERR_UNSUPPORTED, who + " searches implicit nodes: explicit-active nodes (option implicit_active 0) are not served by the in-kernel search");
+  if (c->opt_force_path) return fail(c, PCP_ERR_UNSUPPORTED, who + ": force_path is set");
+  const int32_t rc = launch_neq_dfs(c, st, n_trees, n_steps, stop_on_solution, node_limit, reinterpret_cast<hipStream_t>(hip_stream), ex, sink);
   if (rc < 0) return rc;
   if (rc == 0 && n_steps) return fail(c, PCP_ERR_UNSUPPORTED, who + " needs an all-XNeqY model whose variable store fits the in-kernel search (options neq_path / neq_dfs on)");
   return PCP_OK;

@@ -5,6 +5,18 @@
 
 namespace pcp {
 
+// The solution sink of a context (pcp_solution_sink_set) or of one call (pcp_dfs_forest_device_neq_sink): an append buffer of (lb, ub) rows
+// every tree of an Interval forest writes its solutions into.  A solution draws a ticket from *count BEFORE it is counted; a ticket >= capacity hands the node back to the caller
+// (error kDfsSinkFull, the contract of error 1).  The SINK = false instantiations never read the struct.
+struct SinkDev {
+  int32_t* lb;        // [capacity][n_vars]
+  int32_t* ub;
+  uint32_t* tree;     // [capacity] or null: the tree that wrote the row
+  uint32_t* count;    // tickets drawn since the caller last zeroed it
+  uint32_t capacity;
+};
+constexpr uint32_t kDfsSinkFull = 6;  // counters[t][3]: the sink was full — the node stays on the stack, propagated and uncounted
+
 // Assignment-driven fixpoint of all-XNeqY models, implicit-active nodes (pcp_neq.hip): no sweep over the record table — round 0
 // walks the adjacency lists of the variables that are singletons in the staged domains.
 struct NeqArgs {
@@ -51,7 +63,9 @@ struct NeqArgs {
     pcp_excl* row_excl;         //   [trees][dfs.capacity]: the entry appended when the row is popped (var 0xFFFFFFFF: none)
     uint32_t path_capacity;
     uint32_t val;               //   PCP_VAL_MIDDLE / PCP_VAL_MIN
-  } en;                         // (the last member: the kernel arguments in front of it keep their offsets)
+  } en;
+  SinkDev sink;                 // pcp_dfs_forest_device_neq_sink (the DFS && SINK kernels): the call's solution sink; sink.lb == null: none
+                                // (the last member: the kernel arguments in front of it keep their offsets)
 };
 size_t lds_bytes_neq(uint32_t n_slots, uint32_t n_vars, uint32_t nodes_per_block, bool packed, uint32_t wgs = 2);
 hipError_t launch_neqfix(const NeqArgs& a, const LaunchPlan& p, hipStream_t stream);
@@ -125,18 +139,6 @@ struct FormExclArgs {
   uint8_t* empty;             //   [n_nodes]: receives 1 where the fold would empty the node (PCP_FALSE, row unchanged), else 0: bnb_reduce_kernel's input
 };
 hipError_t launch_formexcl(const FormExclArgs& a, const LaunchPlan& p, hipStream_t stream);
-
-// The solution sink of a context (pcp_solution_sink_set): an append buffer of (lb, ub) rows every tree of an Interval forest writes its
-// solutions into.  A solution draws a ticket from *count BEFORE it is counted; a ticket >= capacity hands the node back to the caller
-// (error kDfsSinkFull, the contract of error 1).  The SINK = false instantiations never read the struct.
-struct SinkDev {
-  int32_t* lb;        // [capacity][n_vars]
-  int32_t* ub;
-  uint32_t* tree;     // [capacity] or null: the tree that wrote the row
-  uint32_t* count;    // tickets drawn since the caller last zeroed it
-  uint32_t capacity;
-};
-constexpr uint32_t kDfsSinkFull = 6;  // counters[t][3]: the sink was full — the node stays on the stack, propagated and uncounted
 
 // What the two row-stack search forests of Interval stores share (row_dfs, pcp_rowdfs.hpp): one tree per WAVEFRONT on its own stack of
 // (lb, ub) rows, a pcp_dfs_state laid out as for pcp_dfs_forest_device.  Embedded as `d` in FormDfsArgs and SmallDfsArgs, as SetDfsArgs is in

@@ -699,7 +699,14 @@ __device__ __forceinline__ int neq_enum_value(const Tile& tl, const NeqArgs& a, 
 // the bound v sits at (one word of the row), else the row as it is and the entry (var, v) as the row's row_excl; either way row_base = n, the
 // parent's list.  The left child x = v is one LDS cell and the node to continue with, the path unchanged.  A row that stays on the stack as
 // the node it is (error 1 or 3, the left child at the end of a launch) has its list in the path already: row_base = n and no entry.
-template <bool PACKED, bool ENUM, class Tile>
+// SINK (DFS && SINK, pcp_dfs_forest_device_neq_sink): a solution draws a ticket from the call's sink (NeqArgs::sink) BEFORE it is counted — the
+// visitor of AllSolution (search/engine/all_solution.rs).  A ticket inside the sink: the whole node, a box, goes from the LDS cells to row
+// `slot`, and the step goes on as without a sink.  A ticket beyond it: error kDfsSinkFull — nothing is counted and the node stays on the
+// stack as row sp - 1, which holds its fixpoint (neq_write_back ran before the step, in full for a stale left child), under ENUM with
+// row_base = n and no entry like errors 1 and 3: a caller that drains the sink and resumes runs it again, and it is counted and appended then.
+// The StopNode limit node is no solution and draws no ticket.  The branch is workgroup-uniform (status words read behind a barrier,
+// replicated registers), so its two barriers are reached by every wavefront or by none; the slot travels through the idle round list.
+template <bool PACKED, bool ENUM, bool SINK, class Tile>
 __device__ __forceinline__ void neq_dfs_step(const Tile& tl, const NeqArgs& a, NeqDfsRegs& r, const bool last_step) {
   const bool failed = (tl.misc[N_FAIL] & 1u) != 0, refused = (tl.misc[N_OOB] & 1u) != 0, open = (tl.misc[N_UNK] & 1u) != 0;
   r.resume_var = 0xFFFFFFFFu;
@@ -714,12 +721,37 @@ __device__ __forceinline__ void neq_dfs_step(const Tile& tl, const NeqArgs& a, N
     ++r.nodes;
     if (!last) ++r.fail;
   } else if (!open) {  // True: a solution (monitor.rs:19-68); the first one is kept
-    ++r.nodes;
-    if (!last) {
-      if (r.sols == 0 && a.dfs.first_solution)
-        for (uint32_t v = tl.tid; v < tl.V; v += tl.nth) a.dfs.first_solution[v] = cell_bounds<PACKED>(tl.dom[tl.rowof(v)]).x;
-      ++r.sols;
-      if (a.dfs.stop_on_solution) r.stop = 1;
+    bool sink_full = false;
+    if constexpr (SINK) {
+      if (!last) {
+        uint32_t* const ticket = reinterpret_cast<uint32_t*>(tl.list);  // (the round list is idle here)
+        if (tl.tid == 0) ticket[0] = __hip_atomic_fetch_add(a.sink.count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        const uint32_t slot = ticket[0];
+        __syncthreads();
+        if (slot < a.sink.capacity) {
+          int32_t* const sl = a.sink.lb + (size_t)slot * tl.V;
+          int32_t* const su = a.sink.ub + (size_t)slot * tl.V;
+          for (uint32_t v = tl.tid; v < tl.V; v += tl.nth) { const int2 c = cell_bounds<PACKED>(tl.dom[tl.rowof(v)]); sl[v] = c.x; su[v] = c.y; }
+          if (tl.tid == 0 && a.sink.tree) a.sink.tree[slot] = blockIdx.x;
+        } else {
+          sink_full = true;
+        }
+      }
+    }
+    if (sink_full) {
+      r.err = kDfsSinkFull; r.stop = 1;  // sink full: the node stays on the stack, propagated and uncounted
+      new_sp = r.sp;
+      if constexpr (ENUM)
+        if (tl.tid == 0) { a.en.row_base[r.sp - 1] = r.n; a.en.row_excl[r.sp - 1] = pcp_excl{kNeqNoExcl, 0}; }
+    } else {
+      ++r.nodes;
+      if (!last) {
+        if (r.sols == 0 && a.dfs.first_solution)
+          for (uint32_t v = tl.tid; v < tl.V; v += tl.nth) a.dfs.first_solution[v] = cell_bounds<PACKED>(tl.dom[tl.rowof(v)]).x;
+        ++r.sols;
+        if (a.dfs.stop_on_solution) r.stop = 1;
+      }
     }
   } else {
     // Brancher<FirstSmallestVar, MiddleVal, BinarySplit>::enter (brancher.rs:52-71): the first variable of minimal size > 1
@@ -1705,7 +1737,9 @@ __device__ __forceinline__ void neq_stage_tile(const Tile& tl, const NeqArgs& a,
 // path[row_base], so the current node's list is the contiguous slice path[0 .. dfs.n) and the sweep and the status read it from there instead
 // of excl_off[nid].  The step chooses Enumerate's value against that list (neq_enum_value) and writes the children's row words (neq_dfs_step).
 // Everything it adds sits under `if constexpr (DFS && EXCL)` resp. the TREE / ENUM flags of the functions it calls.
-template <bool PACKED, bool PAY4, bool DFS, int BT, bool CELLS = false, bool TICKETS = false, bool EXCL = false>
+// DFS && SINK: the search loop appends every solution to the sink of the call (NeqArgs::sink; pcp_dfs_forest_device_neq_sink) — neq_dfs_step's
+// SINK flag, nothing else; instantiated for int2 cells, both payload formats, EXCL false (BinarySplit) and true (Enumerate).
+template <bool PACKED, bool PAY4, bool DFS, int BT, bool CELLS = false, bool TICKETS = false, bool EXCL = false, bool SINK = false>
 __global__ void __launch_bounds__(DFS ? 512 : 1024) __attribute__((amdgpu_waves_per_eu(4))) neqfix_kernel(const NeqArgs a_in) {  // (four wavefronts per SIMD: the forest runs 16 per CU)
   NeqArgs a = a_in;
   a.stats += blockIdx.x & (kStatSlots - 1);
@@ -2197,7 +2231,7 @@ __global__ void __launch_bounds__(DFS ? 512 : 1024) __attribute__((amdgpu_waves_
   } else {
     // ---- the search step on the node just propagated (what dfs_step_kernel does for the generic kernels) ---------------------
     bar();
-    neq_dfs_step<PACKED, EXCL>(NeqTile<PACKED>{dom, chg, misc, adjo, list, win, V, Wv, B, sh, nb, tid, lane, wv, nwv, nth}, a, dfs, dfs_it + 1u >= a.dfs.n_steps);
+    neq_dfs_step<PACKED, EXCL, SINK>(NeqTile<PACKED>{dom, chg, misc, adjo, list, win, V, Wv, B, sh, nb, tid, lane, wv, nwv, nth}, a, dfs, dfs_it + 1u >= a.dfs.n_steps);
     bar();
   }
   }  // the DFS loop / the tile loop
@@ -2245,13 +2279,13 @@ size_t lds_bytes_neq(uint32_t n_slots, uint32_t n_vars, uint32_t nodes_per_block
   return c.total <= 160 * 1024 ? c.total : 0;
 }
 
-template <bool PACKED, bool PAY4, bool DFS, int BT, bool CELLS, bool TICKETS, bool EXCL = false>
+template <bool PACKED, bool PAY4, bool DFS, int BT, bool CELLS, bool TICKETS, bool EXCL = false, bool SINK = false>
 static hipError_t launch_neq_t(const NeqArgs& a, const LaunchPlan& p, hipStream_t stream) {
   if (p.lds_bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(neqfix_kernel<PACKED, PAY4, DFS, BT, CELLS, TICKETS, EXCL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(neqfix_kernel<PACKED, PAY4, DFS, BT, CELLS, TICKETS, EXCL, SINK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((neqfix_kernel<PACKED, PAY4, DFS, BT, CELLS, TICKETS, EXCL>), dim3(p.grid), dim3(p.block), p.lds_bytes, stream, a);
+  hipLaunchKernelGGL((neqfix_kernel<PACKED, PAY4, DFS, BT, CELLS, TICKETS, EXCL, SINK>), dim3(p.grid), dim3(p.block), p.lds_bytes, stream, a);
   return hipGetLastError();
 }
 template <bool PACKED, bool PAY4, bool DFS, int BT, bool CELLS = false>
@@ -2354,12 +2388,17 @@ hipError_t launch_neqfix(const NeqArgs& a, const LaunchPlan& p, hipStream_t stre
   if (a.nodes_per_block == 0 || a.nodes_per_block > 16 || a.m.n_slots >= 65536u || !a.m.adjp) return hipErrorInvalidValue;
   if (a.dfs.n_steps) {
     if (a.nodes_per_block != 1 || p.grid < 1 || !a.dfs.sp || !a.dfs.stop || !a.dfs.counters) return hipErrorInvalidValue;  // (grid = trees)
+    // ... with the call's solution sink (pcp_dfs_forest_device_neq_sink): the DFS && SINK kernels, int2 cells like the Enumerate ones
+    const bool sink = a.sink.lb != nullptr;
+    if (sink && (a.packed || !a.sink.ub || !a.sink.count || !a.sink.capacity)) return hipErrorInvalidValue;
     if (a.en.row_base) {
       // ... under Enumerate (pcp_dfs_forest_device_neq_enum): the two DFS && EXCL kernels — int2 cells, which is what the search loop is
       // launched with (launch_neq_dfs, pcp_api.hip), and either payload format
       if (a.packed || !a.en.row_excl || (a.en.path_capacity && !a.en.path) || a.excl_off) return hipErrorInvalidValue;
+      if (sink) return a.adjp4 ? launch_neq_t<false, true, true, 1, false, false, true, true>(a, p, stream) : launch_neq_t<false, false, true, 1, false, false, true, true>(a, p, stream);
       return a.adjp4 ? launch_neq_t<false, true, true, 1, false, false, true>(a, p, stream) : launch_neq_t<false, false, true, 1, false, false, true>(a, p, stream);
     }
+    if (sink) return a.adjp4 ? launch_neq_t<false, true, true, 1, false, false, false, true>(a, p, stream) : launch_neq_t<false, false, true, 1, false, false, false, true>(a, p, stream);
     return launch_neq_d<true, 1>(a, p, stream);
   }
   if (a.excl_off) {

@@ -28,7 +28,7 @@ ERRORS = {-1: "PCP_ERR_ARG", -2: "PCP_ERR_CONTRACT", -3: "PCP_ERR_HIP", -4: "PCP
 ABI_SYMBOLS = [
     "pcp_ctx_create", "pcp_ctx_destroy", "pcp_last_error", "pcp_strerror", "pcp_abi_version",
     "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull",
-    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_form_enum", "pcp_dfs_forest_device_neq_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_set_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
+    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_form_enum", "pcp_dfs_forest_device_neq_enum", "pcp_dfs_forest_device_neq_sink", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_set_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
 ]
 
 
@@ -270,6 +270,7 @@ def load_library():
     L.pcp_dfs_forest_device_small_enum.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestExcl), C.POINTER(ForestObjective), u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_form_enum.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestExcl), C.POINTER(ForestObjective), u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_neq_enum.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestExcl), C.POINTER(ForestObjective), u32, u32, C.c_uint64, vp]
+    L.pcp_dfs_forest_device_neq_sink.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestExcl), C.POINTER(PcpSolutionSink), u32, u32, C.c_uint64, vp]
     L.pcp_solution_sink_set.argtypes = [vp, C.POINTER(PcpSolutionSink)]
     L.pcp_set_solution_sink_set.argtypes = [vp, C.POINTER(PcpSetSolutionSink)]
     L.pcp_stats_reset.argtypes = [vp, vp]
@@ -375,7 +376,7 @@ def _check_neq_enum(who, objective, collect_solutions, var_select):
     if objective is not None:
         raise ValueError(f"{who}: there is no branch and bound in the all-XNeqY forest (forest='small' runs one over a store within the small-store limits)")
     if collect_solutions:
-        raise ValueError(f"{who}: the all-XNeqY forest writes into no solution sink (forest='small' collects the solutions of a store within the small-store limits)")
+        raise ValueError(f"{who}: the all-XNeqY entry behind it refuses the context's solution sink — Context.dfs_forest_neq_solutions / search_forest.forest_solutions return that forest's solutions (forest='small' collects those of a store within the small-store limits)")
     if var_select == "input_order":
         raise ValueError(f"{who}: var_select='input_order' " + _neq_enum_forest({"forest": "neq"}))
 
@@ -733,7 +734,7 @@ class Context:
         """pcp_solution_sink_set: attach a solution sink — a SolutionSink or a PcpSolutionSink over device buffers — to this context, or
         detach the one attached (None).  While one is attached the forests dfs_forest(formulas=True), dfs_forest(small=True) and dfs_forest_enum append every
         solution to it as an (lb, ub) row and hand a node back with error 6 (SINK_FULL) when it is full; every other forest entry refuses to
-        run (PCP_ERR_UNSUPPORTED).  The struct is copied; the buffers must outlive the attachment."""
+        run (PCP_ERR_UNSUPPORTED) — the all-XNeqY forest returns its solutions through dfs_forest_neq_solutions, whose sink is the call's.  The struct is copied; the buffers must outlive the attachment."""
         st = sink.struct() if isinstance(sink, SolutionSink) else sink
         self._check(self._L.pcp_solution_sink_set(self._h, None if st is None else C.byref(st)))
 
@@ -750,7 +751,7 @@ class Context:
                    max_launches: int = 1 << 30, node_budget: int = 0, want_solution: bool = False, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
                    sp0=None, hints: bool = True, formulas: bool = False, small: bool = False, _call=None, brancher: str = "split", val: str = "middle",
                    root_excl=None, path_capacity: int = 64, max_path: int = 1 << 20, _obj=None, collect_solutions: bool = False, sink_capacity: int = 4096,
-                   _enum_entry=None):
+                   _enum_entry=None, _neq_sink: int = 0):
         """pcp_dfs_forest_device: the reference's search loop (interval mode, all-XNeqY models) on many subtrees at once, one workgroup per
         tree, each exactly a pcp_dfs_device instance.  root_lb / root_ub: [n_trees, n_vars] int32 (numpy or CUDA tensors): the roots, not yet
         propagated.  Launches of steps_per_launch nodes per tree are repeated until every stack is empty, a tree stopped (solution with
@@ -783,7 +784,8 @@ class Context:
         if small and formulas:
             raise ValueError("dfs_forest: small=True and formulas=True name two different forests (a store has formula units or it has none)")
         # (_enum_entry: dfs_forest_enum's — the Enumerate entry of the forest the store belongs to, in place of the small-store one)
-        enum = _check_forest_brancher("dfs_forest", brancher, val, small or _enum_entry is not None, dist, root_excl)
+        # (_neq_sink: dfs_forest_neq_solutions' — the rows of a sink of the CALL, through pcp_dfs_forest_device_neq_sink under either brancher)
+        enum = _check_forest_brancher("dfs_forest", brancher, val, small or _enum_entry is not None or _neq_sink > 0, dist, root_excl)
         _check_collect("dfs_forest", collect_solutions, sink_capacity, small, formulas, dist, _call is not None or _obj is not None)
         dev = torch.device("cuda", self.device)
         V = self.n_vars
@@ -835,7 +837,10 @@ class Context:
         entry = self._L.pcp_dfs_forest_device_small if small else (self._L.pcp_dfs_forest_device_form if formulas else self._L.pcp_dfs_forest_device)
 
         def launch():
-            if enum:  # (_obj: dfs_forest_bnb's objective)
+            if _neq_sink:  # (the sink is an argument of the call: nothing is attached to the context)
+                self._check(self._L.pcp_dfs_forest_device_neq_sink(self._h, C.byref(box["st"]), T, C.byref(box["ex"]) if enum else None, C.byref(box["sink"]),
+                                                                   int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit_per_tree), C.c_void_p(stream)))
+            elif enum:  # (_obj: dfs_forest_bnb's objective)
                 self._check((_enum_entry or self._L.pcp_dfs_forest_device_small_enum)(self._h, C.byref(box["st"]), T, C.byref(box["ex"]), C.byref(_obj) if _obj is not None else None,
                                                                                      int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit_per_tree), C.c_void_p(stream)))
             elif _call is not None:  # (dfs_forest_bnb: the same loop over another entry point)
@@ -843,7 +848,13 @@ class Context:
             else:
                 self._check(entry(self._h, C.byref(box["st"]), T, int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit_per_tree), C.c_void_p(stream)))
 
-        if collect_solutions:
+        if _neq_sink:
+            sink = SolutionSink(_neq_sink, V, dev)
+            box["sink"] = sink.struct()
+            loop = run_forest_loop(launch, fs, stop_on_solution=stop_on_solution, node_budget=node_budget,
+                                   rebalance=rebalance and not node_limit_per_tree, max_launches=max_launches, dist=dist, sink=sink)
+            sink.drain()
+        elif collect_solutions:
             # the sink is the context's for the duration of the loop only: drained behind the last launch, detached on every way out
             sink = SolutionSink(sink_capacity, V, dev)
             self.solution_sink_set(sink)
@@ -867,9 +878,46 @@ class Context:
         out = {"nodes": int(cn[:, 0].sum()), "solutions": int(cn[:, 1].sum()), "failed": int(cn[:, 2].sum()), "error": int(cn[:, 3].max()),
                "open": int(sp.sum().item()), "launches": launches, "per_tree": cn, "trees": T, "steals": steals,
                "first_solutions": sol.cpu().numpy() if want_solution else None}
-        if collect_solutions:
+        if collect_solutions or _neq_sink:
             out["solutions_lb"], out["solutions_ub"], out["solution_tree"] = sink.rows()
         return out
+
+    def dfs_forest_neq_solutions(self, root_lb, root_ub, brancher: str = "split", val: str = "middle", root_excl=None, sink_capacity: int = 4096,
+                                 objective=None, var_select=None, dist=None, path_capacity: int = 64, max_path: int = 1 << 20, stop_on_solution: bool = False,
+                                 node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048, max_launches: int = 1 << 30, node_budget: int = 0,
+                                 want_solution: bool = False, rebalance: bool = True, info: dict | None = None, max_capacity: int = 0, sp0=None, hints: bool = True):
+        """pcp_dfs_forest_device_neq_sink: every solution of the all-XNeqY in-kernel forest, not only their number — the visitor of AllSolution
+        (search/engine/all_solution.rs) on the trees of dfs_forest (``brancher="split"``) or of dfs_forest_enum(forest="neq")
+        (``brancher="enumerate"`` on ``val`` "middle" / "min", with ``root_excl`` / ``path_capacity`` / ``max_path`` as there).  It is
+        dfs_forest's loop: stacks and paths grow, finished trees steal, and a tree that finds the sink full hands its node back (error 6),
+        the loop drains the sink and resumes it.  The sink — a SolutionSink of ``sink_capacity`` rows — is an argument of every launch;
+        nothing is attached to the context, whose own sink (solution_sink_set) the all-XNeqY entries keep refusing.  Returns dfs_forest's
+        dict plus ``solutions_lb`` / ``solutions_ub`` ([n, n_vars] int32: a solution is a BOX of the interval store, every point of it
+        satisfies the model) and ``solution_tree`` ([n]); ``info`` receives ``drains``.  The counters are those of the counting entry on
+        the same roots.  An ``objective`` (there is no branch and bound in this forest), ``var_select="input_order"`` (given, or the
+        context's), ``sink_capacity`` < 1 and a ``dist`` are a ValueError before anything runs."""
+        who = "dfs_forest_neq_solutions"
+        _check_brancher(brancher, val)
+        if objective is not None:
+            raise ValueError(f"{who}: there is no branch and bound in the all-XNeqY forest (dfs_forest_bnb(small=True) runs one over a store within the small-store limits)")
+        if var_select is not None and var_select not in VAR_SELECTS:
+            raise ValueError(f"{who}: var_select must be 'first_smallest' or 'input_order', not {var_select!r}")
+        if var_select == "input_order":
+            raise ValueError(f"{who}: var_select='input_order' is not served by the all-XNeqY forest (pcp_dfs_forest_device_neq_sink selects FirstSmallestVar only): "
+                             "dfs_forest(small=True, collect_solutions=True) runs an all-XNeqY store within the small-store limits")
+        if int(sink_capacity) < 1:
+            raise ValueError(f"{who}: sink_capacity must be at least 1, not {sink_capacity}")
+        if dist is not None:
+            raise ValueError(f"{who}: collecting solutions does not run on several ranks (gathering the sinks is not built)")
+        if root_excl is not None and brancher != "enumerate":
+            raise ValueError(f"{who}: root_excl needs brancher='enumerate'")
+        with var_select_scope(self, var_select):
+            if self.var_select == "input_order":
+                raise ValueError(f"{who}: the context's var_select is 'input_order', which the all-XNeqY forest does not serve (var_select='first_smallest' for this call)")
+            return self.dfs_forest(root_lb, root_ub, stop_on_solution=stop_on_solution, node_limit_per_tree=node_limit_per_tree, steps_per_launch=steps_per_launch,
+                                   capacity=capacity, max_launches=max_launches, node_budget=node_budget, want_solution=want_solution, rebalance=rebalance, info=info,
+                                   max_capacity=max_capacity, sp0=sp0, hints=hints, _neq_sink=int(sink_capacity),
+                                   **(dict(brancher="enumerate", val=val, root_excl=root_excl, path_capacity=path_capacity, max_path=max_path) if brancher == "enumerate" else {}))
 
     @scoped_var_select()
     def dfs_forest_bnb(self, root_lb, root_ub, objective, best0=None, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
@@ -934,8 +982,8 @@ class Context:
         shape, nothing is launched to find out), else "small"; a name forces that entry.  "neq" is the all-XNeqY in-kernel forest,
         pcp_dfs_forest_device_neq_enum: one workgroup per tree, any all-XNeqY store the in-kernel search takes (N-queens-1000; forced, small
         N-queens too), the stack rows with their ``dirty`` words (``hints=False``: without them — the same tree), which grow and are stolen
-        together with ``row_base``, ``row_excl`` and the path prefix.  It has no branch and bound, writes into no solution sink and selects
-        FirstSmallestVar only: ``objective``, ``collect_solutions`` and ``var_select="input_order"`` are a ValueError before anything runs."""
+        together with ``row_base``, ``row_excl`` and the path prefix.  It has no branch and bound, refuses the context's solution sink
+        (dfs_forest_neq_solutions returns its solutions through a sink of the call) and selects FirstSmallestVar only: ``objective``, ``collect_solutions`` and ``var_select="input_order"`` are a ValueError before anything runs."""
         if forest not in FOREST_KINDS:
             raise ValueError(f"dfs_forest_enum: forest must be None, 'neq', 'small' or 'form', not {forest!r}")
         if dist is not None:
@@ -1221,7 +1269,7 @@ def _check_collect(who, collect_solutions, sink_capacity, small, formulas, dist,
     if bnb:
         raise ValueError(f"{who}: collect_solutions does not go with branch and bound (it keeps best_solution; the entries refuse a solution sink)")
     if not small and not formulas:
-        raise ValueError(f"{who}: collect_solutions needs formulas=True or small=True (the all-XNeqY forest writes into no solution sink; small=True takes an all-XNeqY store within its limits)")
+        raise ValueError(f"{who}: collect_solutions needs formulas=True or small=True (the all-XNeqY entry behind it refuses the context's solution sink — Context.dfs_forest_neq_solutions / search_forest.forest_solutions return that forest's solutions; small=True takes an all-XNeqY store within its limits)")
     if dist is not None:
         raise ValueError(f"{who}: collect_solutions does not run on several ranks (gathering the sinks is not built)")
     if int(sink_capacity) < 1:

@@ -527,6 +527,67 @@ def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_
     return out
 
 
+def forest_solutions(ctx, lb0, ub0, brancher: str = "split", val: str = "middle", n_trees: int = 256, forest=None, sink_capacity: int = 4096,
+                     steps_per_launch: int = 512, capacity: int = 128, max_capacity: int = 1 << 16, path_capacity: int = 64, rebalance: bool = True,
+                     info: dict | None = None, objective=None, var_select=None, dist=None) -> dict:
+    """AllSolution (search/engine/all_solution.rs) over the context's Interval store: EVERY solution below (lb0, ub0), as boxes, whichever
+    forest the store belongs to.  The root is expanded breadth-first under DeviceSearch (``brancher`` "split" | "enumerate" on ``val``
+    "middle" | "min") to at least ``n_trees`` open nodes, each becomes a tree of the forest, and the result is forest_search's dict with
+    ``solutions_lb`` / ``solutions_ub`` ([n, n_vars] int32), ``solution_tree`` ([n]; -1: a solution the expansion found, they come first)
+    and ``seeded_solutions``.
+    ``forest`` (None / "neq" / "small" / "form"; anything else a ValueError): None chooses by the store with forest_enumerate's rule — "form"
+    with formula units, "neq" for an all-XNeqY store beyond the small-store limits, else "small"; a name forces that forest.  "neq" is the
+    all-XNeqY in-kernel forest through Context.dfs_forest_neq_solutions (pcp_dfs_forest_device_neq_sink: the sink is an argument of every
+    launch, nothing is attached to the context): any all-XNeqY store the in-kernel search takes (N-queens-1000; forced, small N-queens
+    too) — on a store that is not all-XNeqY a ValueError.  "small" and "form" are forest_search(collect_solutions=True), unchanged.
+    One rank; ``objective``, ``var_select="input_order"`` with the "neq" forest, ``sink_capacity`` < 1 and ``dist`` are a ValueError before
+    anything runs."""
+    from .engine import FOREST_KINDS, VAR_SELECTS, _check_brancher, var_select_scope
+    who = "forest_solutions"
+    if forest not in FOREST_KINDS:
+        raise ValueError(f"{who}: forest must be None, 'neq', 'small' or 'form', not {forest!r}")
+    _check_brancher(brancher, val)
+    if objective is not None:
+        raise ValueError(f"{who}: every solution is returned, none is preferred (forest_bnb / forest_enumerate(objective=) run branch and bound)")
+    if dist is not None:
+        raise ValueError(f"{who}: collecting solutions does not run on several ranks (gathering the sinks is not built)")
+    if int(sink_capacity) < 1:
+        raise ValueError(f"{who}: sink_capacity must be at least 1, not {sink_capacity}")
+    if var_select is not None and var_select not in VAR_SELECTS:
+        raise ValueError(f"{who}: var_select must be 'first_smallest' or 'input_order', not {var_select!r}")
+    if forest == "neq" and var_select == "input_order":
+        raise ValueError(f"{who}: var_select='input_order' " + _neq_enum_forest({"forest": "neq"}).replace("_neq_enum", "_neq_sink"))
+    if forest is None:
+        forest = "form" if ctx.has_formulas else "neq" if (ctx.all_neq and ctx.beyond_small_limits) else "small"
+    if forest != "neq":
+        kw = dict(n_trees=n_trees, steps_per_launch=steps_per_launch, capacity=capacity, info=info, formulas=forest == "form", small=forest == "small",
+                  collect_solutions=True, sink_capacity=sink_capacity, **(dict(var_select=var_select) if var_select is not None else {}))
+        if brancher == "enumerate":
+            return forest_search(ctx, lb0, ub0, brancher="enumerate", val=val, _by_store=dict(path_capacity=path_capacity, rebalance=rebalance, forest=forest), **kw)
+        return forest_search(ctx, lb0, ub0, **kw)
+    if not ctx.all_neq:
+        raise ValueError(f"{who}: forest='neq' is the all-XNeqY in-kernel forest and this store is not all-XNeqY (forest=None chooses by the store)")
+    with var_select_scope(ctx, var_select):
+        if ctx.var_select == "input_order":
+            raise ValueError(f"{who}: var_select='input_order' " + _neq_enum_forest({"forest": "neq"}).replace("_neq_enum", "_neq_sink"))
+        enum = brancher == "enumerate"
+        rl, ru, st, *rest = seed_roots_interval(ctx, lb0, ub0, n_trees, collect_solutions=True, **(dict(brancher=brancher, val=val) if enum else {}))
+        lists, boxes = (rest[0], rest[1]) if enum else (None, rest[0])
+        out = {"seeded_nodes": st.num_nodes, "trees": int(rl.shape[0]), "launches": 0, "nodes": st.num_nodes, "solutions": st.num_solution,
+               "failed": st.num_failed_node, "error": 0, "solutions_lb": boxes[0], "solutions_ub": boxes[1],
+               "solution_tree": np.full(len(boxes[0]), -1, np.int32), "seeded_solutions": len(boxes[0])}
+        if rl.shape[0] == 0:  # the expansion finished the tree
+            return out
+        r = ctx.dfs_forest_neq_solutions(rl.contiguous(), ru.contiguous(), brancher=brancher, val=val, root_excl=lists, sink_capacity=sink_capacity,
+                                         steps_per_launch=steps_per_launch, capacity=capacity, max_capacity=max(max_capacity, capacity), path_capacity=path_capacity,
+                                         rebalance=rebalance, info=info)
+    out["nodes"] += r["nodes"]; out["solutions"] += r["solutions"]; out["failed"] += r["failed"]
+    out["error"] = r["error"]; out["launches"] = r["launches"]
+    for k in ("solutions_lb", "solutions_ub", "solution_tree"):
+        out[k] = np.concatenate([out[k], r[k]])
+    return out
+
+
 @scoped_var_select()
 def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: int = 512, best0=None, capacity: int = 128, max_capacity: int = 1 << 16,
                info: dict | None = None, formulas: bool = True, small: bool = False, brancher: str = "split", val: str = "middle",
@@ -592,7 +653,8 @@ def forest_enumerate(ctx, lb0, ub0, val: str = "middle", objective=None, n_trees
     ``forest`` (None / "neq" / "small" / "form"): the keyword and the choice of Context.dfs_forest_enum — None sends an all-XNeqY store
     beyond the small-store limits (N-queens-1000) to the all-XNeqY in-kernel forest, pcp_dfs_forest_device_neq_enum, "neq" any all-XNeqY
     store; the expansion runs under DeviceSearch(brancher="enumerate") as for the others and the roots keep their lists.  That forest takes
-    no ``objective``, no ``collect_solutions`` and no ``var_select="input_order"``: a ValueError before anything runs."""
+    no ``objective``, no ``collect_solutions`` (forest_solutions returns its solutions) and no ``var_select="input_order"``: a ValueError
+    before anything runs."""
     from .engine import FOREST_KINDS, VAL_MODES, _check_neq_enum
     if forest not in FOREST_KINDS:
         raise ValueError(f"forest_enumerate: forest must be None, 'neq', 'small' or 'form', not {forest!r}")
