@@ -828,6 +828,34 @@ int32_t pcp_solution_sink_set(pcp_ctx* ctx, const pcp_solution_sink* sink);
 int32_t pcp_dfs_forest_device_neq_sink(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex,
                                        const pcp_solution_sink* sink, uint32_t n_steps, uint32_t stop_on_solution, uint64_t node_limit,
                                        void* hip_stream);
+/* Between two calls of any Interval forest entry — pcp_dfs_forest_device, _form, _small, their _bnb and _enum forms, _neq_enum and _neq_sink:
+ * idle trees take work from trees that have some, on the device.  What pcp_dfs_forest_split_set is to the set-mode forests; here the state
+ * is a stack of rows, and the work handed over is the donor's BOTTOM row — its oldest open node, the subtree nearest its root.
+ *   st, n_trees : the forest's state as its entries take it; rows are the context's n_vars wide.  Only lb, ub, sp, capacity and dirty
+ *                 (nullable) are used.
+ *   ex          : the exclusion state of the Enumerate forests, or NULL for the BinarySplit ones; `val` is ignored.
+ *   pairs       : n_pairs x (donor, receiver) tree indices, device uint32
+ *   done        : [n_pairs] device uint32: done[i] = 1 if pair i was carried out, else 0 and nothing belonging to that pair changes
+ * A pair is VALID when donor != receiver, both are < n_trees, sp[receiver] == 0, 2 <= sp[donor] <= capacity and, with ex,
+ * row_base[donor][0] <= path_capacity.  Validity is decided on the state as it was when the call was enqueued: a valid pair earlier in the
+ * array does not change the verdict on a later one.  A tree may appear in at most ONE valid pair and in any number of invalid ones; no
+ * index taken from an invalid pair is ever used to address memory.
+ * A VALID PAIR (d, r), with k = sp[d] before the call:
+ *   - row 0 of d — lb, ub and, when st->dirty is there, its dirty word — becomes row 0 of r;
+ *   - with ex: the first nb = row_base[d][0] entries of d's path are copied to r's path, row_base[r][0] = nb, row_excl[r][0] = row_excl[d][0];
+ *     d's path stays as it is (its other rows use that prefix);
+ *   - rows 1 .. k-1 of d move down to 0 .. k-2, in lb, ub, dirty, row_base and row_excl;
+ *   - sp[d] = k - 1, sp[r] = 1.
+ * Counters, stop, status, first_solution and the per-tree branch-and-bound words are untouched, so the sum over the trees stays the
+ * search's.  Nothing is specified for rows at or above a tree's new sp, or for entries of r's path at or beyond nb.  Trees in no valid pair
+ * are untouched, bit for bit.
+ * The entry does not look at the store kind: it works on the state alone.  Enqueued on hip_stream, not synchronised, no host read-back.
+ * A set-mode model (pcp_dfs_forest_split_set serves those), a null st, lb, ub or sp, null pairs or done with n_pairs > 0, n_trees == 0,
+ * capacity < 2, with ex a null row_base or row_excl or a null path with path_capacity > 0: PCP_ERR_ARG.  n_pairs == 0: PCP_OK, nothing is
+ * launched.
+ * (Added without a new PCP_ABI_VERSION: a symbol more, no layout changed, every call that ran before runs as it did.) */
+int32_t pcp_dfs_forest_steal(pcp_ctx* ctx, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex /* NULL: BinarySplit forests */,
+                             uint32_t n_pairs, const uint32_t* pairs, uint32_t* done, void* hip_stream);
 /* TWO SINKS.  pcp_solution_sink, above, is the Interval forests': rows of (lb, ub).  While it is attached every set-mode forest entry
  * returns PCP_ERR_UNSUPPORTED, as said there — its rows cannot hold a set.  pcp_set_solution_sink, here, is the set-mode forests': every
  * solution of pcp_dfs_forest_device_set, _set_enum and _setform (both distributors), not only their number and the first one's lower

@@ -311,6 +311,8 @@ extern "C" {
                                              n_steps: u32, node_limit: u64, hip_stream: *mut c_void) -> i32;
     pub fn pcp_dfs_forest_split_set(ctx: *mut pcp_ctx, st: *const pcp_forest_state, n_pairs: u32, pairs: *const u32, done: *mut u32,
                                     hip_stream: *mut c_void) -> i32; // pairs = n_pairs x (donor, receiver), device memory
+    pub fn pcp_dfs_forest_steal(ctx: *mut pcp_ctx, st: *const pcp_dfs_state, n_trees: u32, ex: *const pcp_forest_excl, n_pairs: u32, pairs: *const u32,
+                                done: *mut u32, hip_stream: *mut c_void) -> i32; // Interval forests, between launches: an idle receiver takes the donor's bottom row; ex null: BinarySplit
     pub fn pcp_solution_sink_set(ctx: *mut pcp_ctx, sink: *const pcp_solution_sink) -> i32; // null detaches; honoured by _form, _small, _small_enum and _form_enum (obj null)
     pub fn pcp_set_solution_sink_set(ctx: *mut pcp_ctx, sink: *const pcp_set_solution_sink) -> i32; // null detaches; set-mode contexts only; honoured by _set, _set_enum and _setform, refused by their _bnb entries
     pub fn pcp_dfs_device(ctx: *mut pcp_ctx, st: *const pcp_dfs_state, n_steps: u32, stop_on_solution: u32, node_limit: u64,

@@ -1288,6 +1288,28 @@ int32_t pcp_dfs_forest_device_neq_sink(pcp_ctx* c, const pcp_dfs_state* st, uint
   return PCP_OK;
 }
 
+// Between two launches of any Interval forest: idle trees take the bottom row of trees with two or more open nodes (pcp_steal.hip).  The
+// entry works on the state alone — rows of the context's n_vars — and does not look at the store kind, so the model is not finalised.
+int32_t pcp_dfs_forest_steal(pcp_ctx* c, const pcp_dfs_state* st, uint32_t n_trees, const pcp_forest_excl* ex, uint32_t n_pairs, const uint32_t* pairs,
+                             uint32_t* done, void* hip_stream) {
+  if (!c) return PCP_ERR_ARG;
+  const std::string who = "pcp_dfs_forest_steal";
+  if (c->set_words) return fail(c, PCP_ERR_ARG, who + " moves rows of interval-mode stacks (sets: pcp_dfs_forest_split_set)");
+  if (!st || !st->lb || !st->ub || !st->sp) return fail(c, PCP_ERR_ARG, who + ": null state / lb / ub / sp");
+  if (!n_trees || st->capacity < 2) return fail(c, PCP_ERR_ARG, who + ": no tree / capacity < 2");
+  if (n_pairs && (!pairs || !done)) return fail(c, PCP_ERR_ARG, who + ": null pairs / done");
+  if (ex && (!ex->row_base || !ex->row_excl || (ex->path_capacity && !ex->path))) return fail(c, PCP_ERR_ARG, who + ": null row_base / row_excl / path");
+  if (!n_pairs) return PCP_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  StealArgs a;
+  memset(&a, 0, sizeof(a));
+  a.lb = st->lb; a.ub = st->ub; a.sp = st->sp; a.dirty = st->dirty;
+  if (ex) { a.path = ex->path_capacity ? ex->path : nullptr; a.row_base = ex->row_base; a.row_excl = ex->row_excl; a.path_capacity = ex->path_capacity; }
+  a.n_trees = n_trees; a.capacity = st->capacity; a.n_vars = c->n_vars; a.n_pairs = n_pairs;
+  HIP_TRY(c, launch_forest_steal(a, pairs, done, reinterpret_cast<hipStream_t>(hip_stream)));
+  return PCP_OK;
+}
+
 // What a launch of either row-stack search forest of Interval stores (row_dfs, pcp_rowdfs.hpp) checks, `who` being the entry point and
 // `sets` the entry that takes the same store in set mode: the sink, the mode, the stacks, the exclusion path (ex != nullptr: under
 // Enumerate), the objective (obj != nullptr: under branch and bound); then the model is finalised.

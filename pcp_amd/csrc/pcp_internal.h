@@ -163,6 +163,22 @@ size_t lds_bytes_set_dfs(uint32_t n_vars, uint32_t n_slots, uint32_t set_words, 
 hipError_t launch_setdfs(const SetDfsArgs& a, const SetSinkDev& sink, bool enumerate, bool bnb, hipStream_t stream);
 hipError_t launch_setdfs_split(const SetDfsArgs& a, uint32_t n_pairs, const uint32_t* pairs, uint32_t* done, hipStream_t stream);
 
+// Interval forests, between two launches (pcp_steal.hip, pcp_dfs_forest_steal): idle trees take the bottom row of trees with two or more
+// open nodes.  The state of pcp_dfs_state / pcp_forest_excl as the steal reads it; the store is not looked at.
+struct StealArgs {
+  int32_t* lb;          // [n_trees][capacity][n_vars]
+  int32_t* ub;
+  uint32_t* sp;         // [n_trees]
+  uint32_t* dirty;      // [n_trees][capacity] or null
+  pcp_excl* path;       // [n_trees][path_capacity]; null without exclusions, or with path_capacity == 0
+  uint32_t* row_base;   // [n_trees][capacity]; null = no exclusion state (BinarySplit forests)
+  pcp_excl* row_excl;   // [n_trees][capacity], with row_base
+  uint32_t n_trees, capacity, n_vars, path_capacity, n_pairs;
+  uint32_t col_slices;  // set by the launcher: blocks per pair that move columns
+};
+// pairs: n_pairs x (donor, receiver); done[i] = 1 where pair i was valid on the state the call found and was carried out, else 0.
+hipError_t launch_forest_steal(const StealArgs& a, const uint32_t* pairs, uint32_t* done, hipStream_t stream);
+
 hipError_t launch_branch_scan(uint32_t n_nodes, const uint8_t* status, uint32_t* child_base, uint32_t* counts, hipStream_t stream);
 // Set-mode branching: FirstSmallestVar by CARDINALITY (or InputOrder: the first variable of cardinality > 1), MiddleVal on the bounds, BinarySplit on the sets.
 hipError_t launch_set_branch(uint32_t n_nodes, uint32_t n_vars, uint32_t set_words, int32_t base, uint32_t words, const uint64_t* bits, const int32_t* lb,

@@ -28,7 +28,7 @@ ERRORS = {-1: "PCP_ERR_ARG", -2: "PCP_ERR_CONTRACT", -3: "PCP_ERR_HIP", -4: "PCP
 ABI_SYMBOLS = [
     "pcp_ctx_create", "pcp_ctx_destroy", "pcp_last_error", "pcp_strerror", "pcp_abi_version",
     "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull",
-    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_form_enum", "pcp_dfs_forest_device_neq_enum", "pcp_dfs_forest_device_neq_sink", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_set_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
+    "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_form_enum", "pcp_dfs_forest_device_neq_enum", "pcp_dfs_forest_device_neq_sink", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_dfs_forest_steal", "pcp_solution_sink_set", "pcp_set_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option",
 ]
 
 
@@ -262,6 +262,7 @@ def load_library():
     L.pcp_dfs_forest_device_setform.argtypes = [vp, C.POINTER(ForestState), u32, u32, u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_setform_bnb.argtypes = [vp, C.POINTER(ForestState), C.POINTER(ForestObjective), u32, u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_split_set.argtypes = [vp, C.POINTER(ForestState), u32, vp, vp, vp]
+    L.pcp_dfs_forest_steal.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestExcl), u32, vp, vp, vp]
     L.pcp_dfs_forest_device.argtypes = [vp, C.POINTER(DfsState), u32, u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_form.argtypes = [vp, C.POINTER(DfsState), u32, u32, u32, C.c_uint64, vp]
     L.pcp_dfs_forest_device_form_bnb.argtypes = [vp, C.POINTER(DfsState), u32, C.POINTER(ForestObjective), u32, C.c_uint64, vp]
@@ -280,7 +281,7 @@ def load_library():
     L.pcp_last_plan.argtypes = [vp, C.POINTER(PcpPlan)]
     L.pcp_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
     for f in ("pcp_ctx_create", "pcp_model_reset", "pcp_model_push_props", "pcp_model_push_formula", "pcp_model_push_sum", "pcp_model_truncate", "pcp_model_n_units", "pcp_model_set_hull", "pcp_model_set_hull",
-              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_form_enum", "pcp_dfs_forest_device_neq_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_solution_sink_set", "pcp_set_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
+              "pcp_propagate", "pcp_propagate_device", "pcp_propagate_device_units", "pcp_propagate_device_excl", "pcp_propagate_device_small_excl", "pcp_propagate_device_form_excl", "pcp_propagate_device_bnb", "pcp_branch_device", "pcp_branch_device_hint", "pcp_pack_rows", "pcp_unpack_rows", "pcp_branch_device_cells", "pcp_branch_device_set", "pcp_branch_device_set_enum", "pcp_branch_device_excl", "pcp_dfs_device", "pcp_dfs_forest_device", "pcp_dfs_forest_device_form", "pcp_dfs_forest_device_form_bnb", "pcp_dfs_forest_device_small", "pcp_dfs_forest_device_small_bnb", "pcp_dfs_forest_device_small_enum", "pcp_dfs_forest_device_form_enum", "pcp_dfs_forest_device_neq_enum", "pcp_dfs_forest_device_set", "pcp_dfs_forest_device_set_enum", "pcp_dfs_forest_device_set_bnb", "pcp_dfs_forest_device_setform", "pcp_dfs_forest_device_setform_bnb", "pcp_dfs_forest_split_set", "pcp_dfs_forest_steal", "pcp_solution_sink_set", "pcp_set_solution_sink_set", "pcp_stats_reset", "pcp_stats_read", "pcp_debug_counters", "pcp_last_kernel_ms", "pcp_last_plan", "pcp_set_option"):
         getattr(L, f).restype = i32
     _lib = L
     return L
@@ -746,12 +747,23 @@ class Context:
         st = sink.struct() if isinstance(sink, SetSolutionSink) else sink
         self._check(self._L.pcp_set_solution_sink_set(self._h, None if st is None else C.byref(st)))
 
+    def forest_steal(self, st, n_trees: int, ex, pairs, done, n_pairs=None):
+        """pcp_dfs_forest_steal: between two launches of an Interval forest, idle trees take the bottom row of trees with two or more open
+        nodes, on the device.  ``st``: the forest's DfsState; ``ex``: its ForestExcl under Enumerate, else None; ``pairs``: [n, 2] int32 device
+        tensor of (donor, receiver) trees; ``done``: [n] int32 device tensor, 1 where the pair was valid and carried out.  Enqueued on the
+        device's current stream; nothing is read back.  (``n_pairs``: the pair count when it is not ``pairs.shape[0]``.)"""
+        import torch
+        n = int(pairs.shape[0]) if n_pairs is None else int(n_pairs)
+        stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+        self._check(self._L.pcp_dfs_forest_steal(self._h, None if st is None else C.byref(st), int(n_trees), None if ex is None else C.byref(ex), n,
+                                                 _ptr(pairs), _ptr(done), C.c_void_p(stream)))
+
     @scoped_var_select(refuse=_xneq_forest)
     def dfs_forest(self, root_lb, root_ub, stop_on_solution: bool = False, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
                    max_launches: int = 1 << 30, node_budget: int = 0, want_solution: bool = False, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
                    sp0=None, hints: bool = True, formulas: bool = False, small: bool = False, _call=None, brancher: str = "split", val: str = "middle",
                    root_excl=None, path_capacity: int = 64, max_path: int = 1 << 20, _obj=None, collect_solutions: bool = False, sink_capacity: int = 4096,
-                   _enum_entry=None, _neq_sink: int = 0):
+                   _enum_entry=None, _neq_sink: int = 0, steal: str = "host"):
         """pcp_dfs_forest_device: the reference's search loop (interval mode, all-XNeqY models) on many subtrees at once, one workgroup per
         tree, each exactly a pcp_dfs_device instance.  root_lb / root_ub: [n_trees, n_vars] int32 (numpy or CUDA tensors): the roots, not yet
         propagated.  Launches of steps_per_launch nodes per tree are repeated until every stack is empty, a tree stopped (solution with
@@ -779,8 +791,14 @@ class Context:
         are those of the same call without it.  The result then also holds ``solutions_lb`` / ``solutions_ub`` ([n, n_vars] int32: a solution
         is a box of the interval store — every point of it satisfies the model; ``first_solutions`` keeps lower bounds only) and
         ``solution_tree`` ([n]: the tree that wrote each row); ``info`` receives ``drains``, the drains a full sink forced.  With the default
-        False the calls issued and the keys returned are those of before."""
+        False the calls issued and the keys returned are those of before.
+        ``steal`` ("host" | "device"; anything else a ValueError): how finished trees take work between launches.  "host", the default, is
+        search_forest.run_forest_loop's own loop over a host copy of ``sp`` and issues exactly the calls it issued before; "device" plans the
+        pairs with torch on the device (search_forest.plan_steal_pairs) and carries them out in one pcp_dfs_forest_steal call per launch,
+        with no copy to the host beyond the launch's summary.  Both leave the same state behind, so every tree's counters, ``launches`` and
+        ``steals`` are the same.  One rank: "device" with a ``dist`` of more than one rank is a ValueError."""
         import torch
+        _check_steal("dfs_forest", steal, dist)
         if small and formulas:
             raise ValueError("dfs_forest: small=True and formulas=True name two different forests (a store has formula units or it has none)")
         # (_enum_entry: dfs_forest_enum's — the Enumerate entry of the forest the store belongs to, in place of the small-store one)
@@ -848,11 +866,13 @@ class Context:
             else:
                 self._check(entry(self._h, C.byref(box["st"]), T, int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit_per_tree), C.c_void_p(stream)))
 
+        # (steal="device": the stealer reads the state where point() last put it, so a grown stack or path is the one it moves rows in)
+        skw = dict(steal=steal, stealer=lambda pairs, done: self.forest_steal(box["st"], T, box["ex"] if enum else None, pairs, done)) if steal != "host" else {}
         if _neq_sink:
             sink = SolutionSink(_neq_sink, V, dev)
             box["sink"] = sink.struct()
             loop = run_forest_loop(launch, fs, stop_on_solution=stop_on_solution, node_budget=node_budget,
-                                   rebalance=rebalance and not node_limit_per_tree, max_launches=max_launches, dist=dist, sink=sink)
+                                   rebalance=rebalance and not node_limit_per_tree, max_launches=max_launches, dist=dist, sink=sink, **skw)
             sink.drain()
         elif collect_solutions:
             # the sink is the context's for the duration of the loop only: drained behind the last launch, detached on every way out
@@ -860,13 +880,13 @@ class Context:
             self.solution_sink_set(sink)
             try:
                 loop = run_forest_loop(launch, fs, stop_on_solution=stop_on_solution, node_budget=node_budget,
-                                       rebalance=rebalance and not node_limit_per_tree, max_launches=max_launches, dist=dist, sink=sink)
+                                       rebalance=rebalance and not node_limit_per_tree, max_launches=max_launches, dist=dist, sink=sink, **skw)
                 sink.drain()
             finally:
                 self.solution_sink_set(None)
         else:
             loop = run_forest_loop(launch, fs, stop_on_solution=stop_on_solution, node_budget=node_budget,
-                                   rebalance=rebalance and not node_limit_per_tree, max_launches=max_launches, dist=dist)
+                                   rebalance=rebalance and not node_limit_per_tree, max_launches=max_launches, dist=dist, **skw)
         launches, steals = loop["launches"], loop["steals"]
         if info is not None:
             info.update(loop)
@@ -885,7 +905,8 @@ class Context:
     def dfs_forest_neq_solutions(self, root_lb, root_ub, brancher: str = "split", val: str = "middle", root_excl=None, sink_capacity: int = 4096,
                                  objective=None, var_select=None, dist=None, path_capacity: int = 64, max_path: int = 1 << 20, stop_on_solution: bool = False,
                                  node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048, max_launches: int = 1 << 30, node_budget: int = 0,
-                                 want_solution: bool = False, rebalance: bool = True, info: dict | None = None, max_capacity: int = 0, sp0=None, hints: bool = True):
+                                 want_solution: bool = False, rebalance: bool = True, info: dict | None = None, max_capacity: int = 0, sp0=None, hints: bool = True,
+                                 steal: str = "host"):
         """pcp_dfs_forest_device_neq_sink: every solution of the all-XNeqY in-kernel forest, not only their number — the visitor of AllSolution
         (search/engine/all_solution.rs) on the trees of dfs_forest (``brancher="split"``) or of dfs_forest_enum(forest="neq")
         (``brancher="enumerate"`` on ``val`` "middle" / "min", with ``root_excl`` / ``path_capacity`` / ``max_path`` as there).  It is
@@ -895,9 +916,10 @@ class Context:
         dict plus ``solutions_lb`` / ``solutions_ub`` ([n, n_vars] int32: a solution is a BOX of the interval store, every point of it
         satisfies the model) and ``solution_tree`` ([n]); ``info`` receives ``drains``.  The counters are those of the counting entry on
         the same roots.  An ``objective`` (there is no branch and bound in this forest), ``var_select="input_order"`` (given, or the
-        context's), ``sink_capacity`` < 1 and a ``dist`` are a ValueError before anything runs."""
+        context's), ``sink_capacity`` < 1 and a ``dist`` are a ValueError before anything runs.  ``steal``: as for dfs_forest."""
         who = "dfs_forest_neq_solutions"
         _check_brancher(brancher, val)
+        _check_steal(who, steal, dist)
         if objective is not None:
             raise ValueError(f"{who}: there is no branch and bound in the all-XNeqY forest (dfs_forest_bnb(small=True) runs one over a store within the small-store limits)")
         if var_select is not None and var_select not in VAR_SELECTS:
@@ -916,14 +938,14 @@ class Context:
                 raise ValueError(f"{who}: the context's var_select is 'input_order', which the all-XNeqY forest does not serve (var_select='first_smallest' for this call)")
             return self.dfs_forest(root_lb, root_ub, stop_on_solution=stop_on_solution, node_limit_per_tree=node_limit_per_tree, steps_per_launch=steps_per_launch,
                                    capacity=capacity, max_launches=max_launches, node_budget=node_budget, want_solution=want_solution, rebalance=rebalance, info=info,
-                                   max_capacity=max_capacity, sp0=sp0, hints=hints, _neq_sink=int(sink_capacity),
+                                   max_capacity=max_capacity, sp0=sp0, hints=hints, _neq_sink=int(sink_capacity), **(dict(steal=steal) if steal != "host" else {}),
                                    **(dict(brancher="enumerate", val=val, root_excl=root_excl, path_capacity=path_capacity, max_path=max_path) if brancher == "enumerate" else {}))
 
     @scoped_var_select()
     def dfs_forest_bnb(self, root_lb, root_ub, objective, best0=None, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
                        max_launches: int = 1 << 30, node_budget: int = 0, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
                        sp0=None, small: bool = False, brancher: str = "split", val: str = "middle", root_excl=None, path_capacity: int = 64,
-                       max_path: int = 1 << 20, collect_solutions: bool = False, _enum_entry=None):
+                       max_path: int = 1 << 20, collect_solutions: bool = False, _enum_entry=None, steal: str = "host"):
         """pcp_dfs_forest_device_form_bnb: branch and bound (branch_and_bound.rs:64-84) in the forest over an Interval store with formula
         propagators — the loop, stacks, growth and refill of dfs_forest(formulas=True), every popped row entered with the forest's incumbent
         (one device word) folded into the objective's bounds.  ``objective`` = (var, "min" | "max").  ``best0``: a known bound to start from
@@ -933,8 +955,10 @@ class Context:
         ``small``: the store is a small one of plain propagators (dfs_forest(small=True)): the same loop and result over
         pcp_dfs_forest_device_small_bnb.  ``brancher`` / ``val`` / ``root_excl`` / ``path_capacity`` / ``max_path``: as for dfs_forest
         (Enumerate needs ``small=True``: pcp_dfs_forest_device_small_enum with the objective; dfs_forest_enum(objective=) runs it over either store).  ``collect_solutions=True`` is a ValueError:
-        branch and bound keeps ``best_solution``, and its entries refuse a solution sink."""
+        branch and bound keeps ``best_solution``, and its entries refuse a solution sink.  ``steal``: as for dfs_forest (the per-tree
+        branch-and-bound words stay with their trees under both)."""
         import torch
+        _check_steal("dfs_forest_bnb", steal, dist)
         _check_forest_brancher("dfs_forest_bnb", brancher, val, small or _enum_entry is not None, dist, root_excl)
         _check_collect("dfs_forest_bnb", collect_solutions, 1, small, not small, None, bnb=True)
         var, mode = objective
@@ -953,7 +977,7 @@ class Context:
             return entry(self._h, C.byref(st), n_trees, C.byref(obj), int(steps_per_launch), int(node_limit_per_tree), C.c_void_p(stream))
 
         out = self.dfs_forest(root_lb, root_ub, node_limit_per_tree=node_limit_per_tree, steps_per_launch=steps_per_launch, capacity=capacity, max_launches=max_launches,
-                              node_budget=node_budget, rebalance=rebalance, info=info, dist=dist, max_capacity=max_capacity, sp0=sp0, formulas=not small, small=small, _call=call,
+                              node_budget=node_budget, rebalance=rebalance, info=info, dist=dist, max_capacity=max_capacity, sp0=sp0, formulas=not small, small=small, _call=call, **(dict(steal=steal) if steal != "host" else {}),
                               **(dict(brancher=brancher, val=val, root_excl=root_excl, path_capacity=path_capacity, max_path=max_path, _obj=obj, _enum_entry=_enum_entry) if brancher != "split" else {}))
         tb = tree_best.cpu().numpy()
         found = tb != none
@@ -967,7 +991,7 @@ class Context:
     def dfs_forest_enum(self, root_lb, root_ub, val: str = "middle", objective=None, best0=None, root_excl=None, path_capacity: int = 64, max_path: int = 1 << 20,
                         collect_solutions: bool = False, sink_capacity: int = 4096, stop_on_solution: bool = False, node_limit_per_tree: int = 0,
                         steps_per_launch: int = 256, capacity: int = 2048, max_launches: int = 1 << 30, node_budget: int = 0, want_solution: bool = False,
-                        rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0, forest=None, hints: bool = True):
+                        rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0, forest=None, hints: bool = True, steal: str = "host"):
         """The Enumerate forest over this context's Interval store, chosen by what the store IS (as search.dfs_enumerate and DeviceSearch
         dispatch): pcp_dfs_forest_device_form_enum when it holds formula units (``has_formulas`` — schedules, what Cumulative.join builds),
         else pcp_dfs_forest_device_small_enum.  The trees run under Enumerate on MiddleVal (``val="middle"``) or MinVal (``"min"``); roots,
@@ -983,7 +1007,9 @@ class Context:
         pcp_dfs_forest_device_neq_enum: one workgroup per tree, any all-XNeqY store the in-kernel search takes (N-queens-1000; forced, small
         N-queens too), the stack rows with their ``dirty`` words (``hints=False``: without them — the same tree), which grow and are stolen
         together with ``row_base``, ``row_excl`` and the path prefix.  It has no branch and bound, refuses the context's solution sink
-        (dfs_forest_neq_solutions returns its solutions through a sink of the call) and selects FirstSmallestVar only: ``objective``, ``collect_solutions`` and ``var_select="input_order"`` are a ValueError before anything runs."""
+        (dfs_forest_neq_solutions returns its solutions through a sink of the call) and selects FirstSmallestVar only: ``objective``, ``collect_solutions`` and ``var_select="input_order"`` are a ValueError before anything runs.
+        ``steal``: as for dfs_forest; a stolen row takes its ``row_base`` / ``row_excl`` words and its path prefix along under both."""
+        _check_steal("dfs_forest_enum", steal, dist)
         if forest not in FOREST_KINDS:
             raise ValueError(f"dfs_forest_enum: forest must be None, 'neq', 'small' or 'form', not {forest!r}")
         if dist is not None:
@@ -1002,7 +1028,8 @@ class Context:
         entry = {"form": self._L.pcp_dfs_forest_device_form_enum, "small": self._L.pcp_dfs_forest_device_small_enum, "neq": self._L.pcp_dfs_forest_device_neq_enum}[forest]
         kw = dict(node_limit_per_tree=node_limit_per_tree, steps_per_launch=steps_per_launch, capacity=capacity, max_launches=max_launches, node_budget=node_budget,
                   rebalance=rebalance, info=info, max_capacity=max_capacity, small=forest == "small", brancher="enumerate", val=val, root_excl=root_excl,
-                  path_capacity=path_capacity, max_path=max_path, _enum_entry=entry, **(dict(hints=hints) if forest == "neq" else {}))
+                  path_capacity=path_capacity, max_path=max_path, _enum_entry=entry, **(dict(hints=hints) if forest == "neq" else {}),
+                  **(dict(steal=steal) if steal != "host" else {}))
         if objective is not None:
             return self.dfs_forest_bnb(root_lb, root_ub, objective, best0=best0, **kw)
         return self.dfs_forest(root_lb, root_ub, stop_on_solution=stop_on_solution, want_solution=want_solution, formulas=form,
@@ -1229,6 +1256,17 @@ class Context:
         ms = C.c_float()
         self._check(self._L.pcp_last_kernel_ms(self._h, C.byref(ms)))
         return float(ms.value)
+
+
+STEAL_MODES = ("host", "device")
+
+
+def _check_steal(who, steal, dist=None):
+    """``steal`` of the Interval forest drivers: "host" or "device"; "device" runs on one rank."""
+    if steal not in STEAL_MODES:
+        raise ValueError(f"{who}: steal must be 'host' or 'device', not {steal!r}")
+    if steal == "device" and dist is not None and dist.get_world_size() > 1:
+        raise ValueError(f"{who}: steal='device' runs on one rank (the refill across ranks works from the host's copy of sp)")
 
 
 def _check_brancher(brancher, val):

@@ -279,8 +279,25 @@ class ForestStacks:
         return True
 
 
+def plan_steal_pairs(sp, n_pairs: int):
+    """The (donor, receiver) pairs of one steal round of the Interval forests, planned where ``sp`` lives: torch operations only, no copy to
+    the host.  ``sp``: [T] stack sizes.  Donors in the order of a stable sort of -sp (richest first, ties by index), receivers in the order of
+    a stable sort of sp != 0 (idle trees first, by index); pair i is (donor_order[i], receiver_order[i]).  Returns an int32 [n_pairs, 2]
+    tensor (``n_pairs`` <= T).  Where pair i is valid for pcp_dfs_forest_steal — its donor has two or more rows, its receiver none — it is
+    the i-th pair run_forest_loop's host steal forms from its two lists; the valid pairs are a prefix, and the entry drops the rest.  T minus
+    the number of live trees is an upper bound on the idle ones and so a sufficient ``n_pairs``."""
+    import torch
+    T, n = int(sp.shape[0]), int(n_pairs)
+    if not 0 <= n <= T:
+        raise ValueError(f"plan_steal_pairs: n_pairs must be between 0 and the number of trees ({T}), not {n_pairs}")
+    size = sp.to(torch.int64)
+    donors = torch.argsort(-size, stable=True)[:n]
+    receivers = torch.argsort((size != 0).to(torch.int8), stable=True)[:n]
+    return torch.stack([donors, receivers], dim=1).to(torch.int32)
+
+
 def run_forest_loop(launch, fs: ForestStacks, stop_on_solution: bool = False, node_budget: int = 0, rebalance: bool = True,
-                    max_launches: int = 1 << 30, dist=None, sink=None) -> dict:
+                    max_launches: int = 1 << 30, dist=None, sink=None, steal: str = "host", stealer=None) -> dict:
     """The host side of the interval forest (engine.Context.dfs_forest): ``launch()`` enqueues one launch of the forest kernel on the
     stacks ``fs``; between launches a tree whose stack is full gets more rows (ForestStacks.grow: memory follows the depth actually
     reached instead of being reserved for the worst case) and finished trees take work — from trees of this GPU, then (``dist``) from
@@ -293,13 +310,36 @@ def run_forest_loop(launch, fs: ForestStacks, stop_on_solution: bool = False, no
     each as (lb, ub, entries [k, 2]).
     ``sink`` (an engine.SolutionSink the caller attached to the context; one rank): a tree that reports error 6 found the sink full and kept
     its node, propagated and uncounted; the sink is drained, the error and ``stop`` of those trees are cleared, and they resume as trees with
-    error 1 do — counters are what a sink that never fills leaves.  The result then also names ``drains``, the drains a full sink forced."""
+    error 1 do — counters are what a sink that never fills leaves.  The result then also names ``drains``, the drains a full sink forced.
+    ``steal``: "host" — the loop below over a host copy of ``sp``, a handful of tensor copies per steal — or "device" (one rank; with a
+    ``dist`` of more than one rank a ValueError): one plan_steal_pairs and one ``stealer(pairs, done)`` call per launch, the caller's
+    pcp_dfs_forest_steal on the forest's CURRENT state (engine.Context.forest_steal; it is read at every call, so stacks and paths may have
+    grown).  Both leave the same state, so launches, steals and every tree's counters are the same.  The device path copies nothing to the
+    host beyond the launch's summary: the steals are added up on the device and read once behind the last launch.  Only ``first_steal``
+    costs more — until the first steal has happened, a launch that leaves idle trees reads three words back to learn whether it did."""
     import time
     import torch
+    if steal not in ("host", "device"):
+        raise ValueError(f"run_forest_loop: steal must be 'host' or 'device', not {steal!r}")
     T = int(fs.sp.shape[0])
     launches = steals = fatal = drains = 0
     enum = fs.path is not None
     first_steal = None
+    if steal == "device":
+        if dist is not None and dist.get_world_size() > 1:
+            raise ValueError("run_forest_loop: steal='device' runs on one rank (refill_across_ranks works from the host's copy of sp)")
+        if stealer is None:
+            raise ValueError("run_forest_loop: steal='device' needs a stealer (engine.Context.forest_steal on the forest's state)")
+    stolen = None  # steal="device": the steals so far, one device word
+
+    def first_valid(pairs):  # steal="device": (any, donor, receiver) of the first pair the entry will carry out, and the donor's bottom node — all on the device
+        d, r = pairs[:, 0].long(), pairs[:, 1].long()
+        size = fs.sp.long()
+        ok = (d != r) & (size[r] == 0) & (size[d] >= 2) & (size[d] <= fs.capacity) & (fs.row_base[:, 0].long()[d] <= fs.path_capacity)
+        i = ok.to(torch.int8).argmax().reshape(1)  # (the first of several maxima; 0 when no pair is valid: still a tree of the forest)
+        dd = d[i]
+        rows = [t[:, 0].index_select(0, dd)[0] for t in (fs.lb, fs.ub, fs.row_base, fs.row_excl)]
+        return torch.cat([ok.any().long().reshape(1), dd, r[i]]), rows + [fs.path.index_select(0, dd)[0]]
 
     def node_of(t):  # row 0 of tree t as (lb, ub, its list)
         nb = int(fs.row_base[t, 0])
@@ -364,7 +404,22 @@ def run_forest_loop(launch, fs: ForestStacks, stop_on_solution: bool = False, no
             continue
         lb, ub, sp = fs.lb, fs.ub, fs.sp
         spc = None
-        if mine[0] < T:
+        if mine[0] < T and steal == "device":
+            # The same steals, planned and carried out on the device: T - live is an upper bound on the idle trees, the entry drops every
+            # pair that is not (a tree with two or more rows, an idle tree).
+            pairs = plan_steal_pairs(sp, T - mine[0])
+            done = torch.empty(pairs.shape[0], dtype=torch.int32, device=sp.device)
+            watch = first_valid(pairs) if enum and first_steal is None else None
+            stealer(pairs, done)
+            stolen = done.sum() if stolen is None else stolen + done.sum()
+            if watch is not None:
+                some, d, r = watch[0].cpu().tolist()
+                if some:
+                    wl, wu, wb, we, wp = watch[1]
+                    own, ent = we.cpu().numpy(), wp[:int(wb)].cpu().numpy()
+                    before = wl.cpu().numpy(), wu.cpu().numpy(), (np.concatenate([ent, own[None]]) if own[0] != -1 else ent)
+                    first_steal = {"donor": d, "receiver": r, "before": before, "after": node_of(r)}
+        elif mine[0] < T:
             # Finished trees take work from the others: the BOTTOM row of a tree's stack is its oldest open node (the subtree nearest
             # its root); it moves to the finished tree's row 0 and the donor's stack shifts down by one row.  Counters stay per
             # tree, so their sum is the search's.  (With a per-tree node limit a tree that reached it must stay stopped.)
@@ -396,6 +451,8 @@ def run_forest_loop(launch, fs: ForestStacks, stop_on_solution: bool = False, no
                 spc = sp.cpu().numpy().copy()
             refill_across_ranks(lb, ub, sp, spc, dist, xinfo, dirty=fs.dirty)
             exchange_s += time.perf_counter() - t0
+    if stolen is not None:
+        steals += int(stolen.item())
     out = {"launches": launches, "steals": steals, "moved_rows": xinfo["moved_rows"], "moved_bytes": xinfo["moved_bytes"], "exchange_s": exchange_s,
            "grown": fs.grown, "capacity": fs.capacity}
     if enum:
@@ -448,7 +505,7 @@ STACK_BYTES_CAP = 64 << 30  # default ceiling of the forest's stack rows per GPU
 @scoped_var_select(refuse=_xneq_forest)
 def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_per_launch: int = 512, rank: int = 0, world: int = 1, capacity: int = 0,
                   dist=None, info: dict | None = None, stack_bytes: int = STACK_BYTES_CAP, formulas: bool = False, small: bool = False, brancher: str = "split",
-                  val: str = "middle", collect_solutions: bool = False, sink_capacity: int = 4096, _by_store=None) -> dict:
+                  val: str = "middle", collect_solutions: bool = False, sink_capacity: int = 4096, _by_store=None, steal: str = "host") -> dict:
     """Interval mode, all-XNeqY models: expansion + one in-kernel DFS per open node (pcp_dfs_forest_device).  formulas: the store holds
     formula propagators (what Cumulative.join builds): the trees run in pcp_dfs_forest_device_form, one per wavefront.  small: a small store of
     plain propagators of any kind (the Golomb network): pcp_dfs_forest_device_small, one tree per wavefront; with formulas=True a ValueError.  The node limit is checked
@@ -462,7 +519,11 @@ def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_
     expansion gave them, so that the expansion and the trees together are one Enumerate tree.
     collect_solutions / sink_capacity (formulas=True or small=True, one rank; otherwise a ValueError): as for Context.dfs_forest — the result
     also holds ``solutions_lb`` / ``solutions_ub`` ([n, n_vars] int32, every solution as a box) and ``solution_tree`` ([n]; -1: a solution the
-    expansion found, they come first), and ``seeded_solutions`` counts those."""
+    expansion found, they come first), and ``seeded_solutions`` counts those.
+    steal: "host" | "device", how finished trees take work between launches — as for Context.dfs_forest, which it is handed to; "device" with
+    a ``dist`` of more than one rank, or any other value, is a ValueError before anything runs."""
+    from .engine import _check_steal
+    _check_steal("forest_search", steal, dist if world > 1 else None)
     if small and formulas:
         raise ValueError("forest_search: small=True and formulas=True name two different forests (a store has formula units or it has none)")
     from .engine import _check_collect, _check_forest_brancher
@@ -518,7 +579,7 @@ def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_
                        node_budget=max(node_limit - st.num_nodes, 1) if multi else budget, dist=dist if multi else None, info=info,
                        **(dict(val=val, root_excl=lists, **_by_store) if _by_store is not None else dict(sp0=sp0, formulas=formulas, small=small)),
                        **(dict(brancher=brancher, val=val, root_excl=lists) if enum and _by_store is None else {}),
-                       **(dict(collect_solutions=True, sink_capacity=sink_capacity) if collect_solutions else {}))
+                       **(dict(collect_solutions=True, sink_capacity=sink_capacity) if collect_solutions else {}), **(dict(steal=steal) if steal != "host" else {}))
     out["nodes"] += r["nodes"]; out["solutions"] += r["solutions"]; out["failed"] += r["failed"]
     out["error"] = r["error"]; out["launches"] = r["launches"]
     if collect_solutions:
@@ -529,7 +590,7 @@ def forest_search(ctx, lb0, ub0, node_limit: int = 0, n_trees: int = 768, steps_
 
 def forest_solutions(ctx, lb0, ub0, brancher: str = "split", val: str = "middle", n_trees: int = 256, forest=None, sink_capacity: int = 4096,
                      steps_per_launch: int = 512, capacity: int = 128, max_capacity: int = 1 << 16, path_capacity: int = 64, rebalance: bool = True,
-                     info: dict | None = None, objective=None, var_select=None, dist=None) -> dict:
+                     info: dict | None = None, objective=None, var_select=None, dist=None, steal: str = "host") -> dict:
     """AllSolution (search/engine/all_solution.rs) over the context's Interval store: EVERY solution below (lb0, ub0), as boxes, whichever
     forest the store belongs to.  The root is expanded breadth-first under DeviceSearch (``brancher`` "split" | "enumerate" on ``val``
     "middle" | "min") to at least ``n_trees`` open nodes, each becomes a tree of the forest, and the result is forest_search's dict with
@@ -541,9 +602,10 @@ def forest_solutions(ctx, lb0, ub0, brancher: str = "split", val: str = "middle"
     launch, nothing is attached to the context): any all-XNeqY store the in-kernel search takes (N-queens-1000; forced, small N-queens
     too) — on a store that is not all-XNeqY a ValueError.  "small" and "form" are forest_search(collect_solutions=True), unchanged.
     One rank; ``objective``, ``var_select="input_order"`` with the "neq" forest, ``sink_capacity`` < 1 and ``dist`` are a ValueError before
-    anything runs."""
-    from .engine import FOREST_KINDS, VAR_SELECTS, _check_brancher, var_select_scope
+    anything runs.  ``steal``: "host" | "device", as for Context.dfs_forest."""
+    from .engine import FOREST_KINDS, VAR_SELECTS, _check_brancher, _check_steal, var_select_scope
     who = "forest_solutions"
+    _check_steal(who, steal)
     if forest not in FOREST_KINDS:
         raise ValueError(f"{who}: forest must be None, 'neq', 'small' or 'form', not {forest!r}")
     _check_brancher(brancher, val)
@@ -561,7 +623,7 @@ def forest_solutions(ctx, lb0, ub0, brancher: str = "split", val: str = "middle"
         forest = "form" if ctx.has_formulas else "neq" if (ctx.all_neq and ctx.beyond_small_limits) else "small"
     if forest != "neq":
         kw = dict(n_trees=n_trees, steps_per_launch=steps_per_launch, capacity=capacity, info=info, formulas=forest == "form", small=forest == "small",
-                  collect_solutions=True, sink_capacity=sink_capacity, **(dict(var_select=var_select) if var_select is not None else {}))
+                  collect_solutions=True, sink_capacity=sink_capacity, **(dict(var_select=var_select) if var_select is not None else {}), **(dict(steal=steal) if steal != "host" else {}))
         if brancher == "enumerate":
             return forest_search(ctx, lb0, ub0, brancher="enumerate", val=val, _by_store=dict(path_capacity=path_capacity, rebalance=rebalance, forest=forest), **kw)
         return forest_search(ctx, lb0, ub0, **kw)
@@ -580,7 +642,7 @@ def forest_solutions(ctx, lb0, ub0, brancher: str = "split", val: str = "middle"
             return out
         r = ctx.dfs_forest_neq_solutions(rl.contiguous(), ru.contiguous(), brancher=brancher, val=val, root_excl=lists, sink_capacity=sink_capacity,
                                          steps_per_launch=steps_per_launch, capacity=capacity, max_capacity=max(max_capacity, capacity), path_capacity=path_capacity,
-                                         rebalance=rebalance, info=info)
+                                         rebalance=rebalance, info=info, **(dict(steal=steal) if steal != "host" else {}))
     out["nodes"] += r["nodes"]; out["solutions"] += r["solutions"]; out["failed"] += r["failed"]
     out["error"] = r["error"]; out["launches"] = r["launches"]
     for k in ("solutions_lb", "solutions_ub", "solution_tree"):
@@ -591,7 +653,7 @@ def forest_solutions(ctx, lb0, ub0, brancher: str = "split", val: str = "middle"
 @scoped_var_select()
 def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: int = 512, best0=None, capacity: int = 128, max_capacity: int = 1 << 16,
                info: dict | None = None, formulas: bool = True, small: bool = False, brancher: str = "split", val: str = "middle",
-               collect_solutions: bool = False, _by_store=None) -> dict:
+               collect_solutions: bool = False, _by_store=None, steal: str = "host") -> dict:
     """Branch and bound over an Interval store with formula propagators (branch_and_bound.rs:64-84 around the loop of forest_search):
     minimize / maximize ``objective`` = (var, "min" | "max") below (lb0, ub0).  The root is expanded breadth-first under branch and bound
     (seed_roots_interval with DeviceSearch(objective=)) to at least ``n_trees`` open nodes; each becomes a tree of
@@ -601,7 +663,9 @@ def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: i
     ``small``: a small store of plain propagators instead (Context.dfs_forest_bnb(small=True) — model.golomb_ruler); it wins over
     ``formulas``, whose default is True.  brancher / val: as for forest_search — Enumerate needs ``small=True``; the expansion then
     runs under DeviceSearch(brancher="enumerate", val=, objective=) and the roots keep their exclusion lists.
-    collect_solutions=True is a ValueError: branch and bound returns ``best_solution``."""
+    collect_solutions=True is a ValueError: branch and bound returns ``best_solution``.  steal: "host" | "device", as for Context.dfs_forest."""
+    from .engine import _check_steal
+    _check_steal("forest_bnb", steal)
     if collect_solutions:
         raise ValueError("forest_bnb: collect_solutions does not go with branch and bound (it keeps best_solution; the entries refuse a solution sink)")
     if not formulas and not small:
@@ -623,11 +687,11 @@ def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: i
                "best": None, "best_solution": None}
     elif _by_store is not None:
         out = ctx.dfs_forest_enum(rl, ru, val=val, objective=(int(var), mode), best0=start, root_excl=lists, steps_per_launch=steps_per_launch, capacity=capacity,
-                                  max_capacity=max(max_capacity, capacity), info=info, **_by_store)
+                                  max_capacity=max(max_capacity, capacity), info=info, **_by_store, **(dict(steal=steal) if steal != "host" else {}))
     else:
         out = ctx.dfs_forest_bnb(rl, ru, (int(var), mode), best0=start, steps_per_launch=steps_per_launch, capacity=capacity,
                                  max_capacity=max(max_capacity, capacity), info=info, small=small,
-                                 **(dict(brancher=brancher, val=val, root_excl=lists) if enum else {}))
+                                 **(dict(brancher=brancher, val=val, root_excl=lists) if enum else {}), **(dict(steal=steal) if steal != "host" else {}))
     out["seeded_nodes"] = st.num_nodes
     out["nodes"] += st.num_nodes; out["solutions"] += st.num_solution; out["failed"] += st.num_failed_node
     # no tree beat the expansion's incumbent: it is the optimum, unless the caller's bound was already as good
@@ -640,7 +704,7 @@ def forest_bnb(ctx, lb0, ub0, objective, n_trees: int = 256, steps_per_launch: i
 @scoped_var_select(refuse=_neq_enum_forest)
 def forest_enumerate(ctx, lb0, ub0, val: str = "middle", objective=None, n_trees: int = 256, steps_per_launch: int = 512, best0=None, collect_solutions: bool = False,
                      sink_capacity: int = 4096, info: dict | None = None, capacity: int = 128, max_capacity: int = 1 << 16, path_capacity: int = 64, rebalance: bool = True,
-                     dist=None, forest=None) -> dict:
+                     dist=None, forest=None, steal: str = "host") -> dict:
     """Enumerate over the context's Interval store, whichever forest it belongs to — the formula-store forest (``ctx.has_formulas``:
     schedules, what Cumulative.join builds) or the small-store one: the root is expanded breadth-first under
     DeviceSearch(brancher="enumerate", val=, objective=) to at least ``n_trees`` open nodes (seed_roots_interval), each becomes a tree of
@@ -654,8 +718,9 @@ def forest_enumerate(ctx, lb0, ub0, val: str = "middle", objective=None, n_trees
     beyond the small-store limits (N-queens-1000) to the all-XNeqY in-kernel forest, pcp_dfs_forest_device_neq_enum, "neq" any all-XNeqY
     store; the expansion runs under DeviceSearch(brancher="enumerate") as for the others and the roots keep their lists.  That forest takes
     no ``objective``, no ``collect_solutions`` (forest_solutions returns its solutions) and no ``var_select="input_order"``: a ValueError
-    before anything runs."""
-    from .engine import FOREST_KINDS, VAL_MODES, _check_neq_enum
+    before anything runs.  ``steal``: "host" | "device", as for Context.dfs_forest."""
+    from .engine import FOREST_KINDS, VAL_MODES, _check_neq_enum, _check_steal
+    _check_steal("forest_enumerate", steal)
     if forest not in FOREST_KINDS:
         raise ValueError(f"forest_enumerate: forest must be None, 'neq', 'small' or 'form', not {forest!r}")
     if dist is not None:
@@ -674,6 +739,6 @@ def forest_enumerate(ctx, lb0, ub0, val: str = "middle", objective=None, n_trees
     by_store = dict(path_capacity=path_capacity, rebalance=rebalance, forest=forest)
     if objective is not None:
         return forest_bnb(ctx, lb0, ub0, objective, n_trees=n_trees, steps_per_launch=steps_per_launch, best0=best0, capacity=capacity, max_capacity=max_capacity,
-                          info=info, formulas=form, small=not form, brancher="enumerate", val=val, _by_store=by_store)
+                          info=info, formulas=form, small=not form, brancher="enumerate", val=val, _by_store=by_store, **(dict(steal=steal) if steal != "host" else {}))
     return forest_search(ctx, lb0, ub0, n_trees=n_trees, steps_per_launch=steps_per_launch, capacity=capacity, info=info, formulas=form, small=forest == "small",
-                         brancher="enumerate", val=val, collect_solutions=collect_solutions, sink_capacity=sink_capacity, _by_store=by_store)
+                         brancher="enumerate", val=val, collect_solutions=collect_solutions, sink_capacity=sink_capacity, _by_store=by_store, **(dict(steal=steal) if steal != "host" else {}))
