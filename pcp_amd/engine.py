@@ -12,6 +12,7 @@ import ctypes as C
 import functools
 import inspect
 import os
+from collections import namedtuple
 from typing import Optional
 
 import numpy as np
@@ -365,11 +366,32 @@ def _const_operands(props) -> list:
 FOREST_KINDS = (None, "neq", "small", "form")  # dfs_forest_enum / forest_enumerate(forest=): chosen by the store, or one entry forced
 
 
-def _neq_enum_forest(a) -> str:
-    """The refusal of dfs_forest_enum / forest_enumerate under InputOrder when the all-XNeqY forest is asked for by name."""
+def store_forest_kind(ctx) -> str:
+    """Context.forest_kind: the Interval forest a store belongs to, decided on the host from its shape — "form" with formula units, "neq" all-XNeqY beyond the small-store limits, else "small"."""
+    return "form" if ctx.has_formulas else "neq" if (ctx.all_neq and ctx.beyond_small_limits) else "small"
+
+
+# One entry point of the Interval forests and what it takes behind ``ctx, st, n_trees``: a pcp_forest_excl, a pcp_forest_objective, a
+# pcp_solution_sink, then ``n_steps``, a stop_on_solution word, then ``node_limit, stream``.  dirty: the forest keeps a hint word per stack row.
+ForestEntry = namedtuple("ForestEntry", "name excl objective sink stop dirty", defaults=(False, False, False, True, False))
+
+
+FOREST_ENTRIES = {  # (forest kind, "plain" | "enumerate" | "bnb" | "sink") -> ForestEntry; all-XNeqY stores have no objective to bound: no ("neq", "bnb")
+    ("neq", "plain"): ForestEntry("pcp_dfs_forest_device", dirty=True), ("form", "plain"): ForestEntry("pcp_dfs_forest_device_form"),
+    ("small", "plain"): ForestEntry("pcp_dfs_forest_device_small"),
+    ("form", "bnb"): ForestEntry("pcp_dfs_forest_device_form_bnb", objective=True, stop=False),
+    ("small", "bnb"): ForestEntry("pcp_dfs_forest_device_small_bnb", objective=True, stop=False),
+    ("neq", "enumerate"): ForestEntry("pcp_dfs_forest_device_neq_enum", excl=True, objective=True, dirty=True),
+    ("form", "enumerate"): ForestEntry("pcp_dfs_forest_device_form_enum", excl=True, objective=True),
+    ("small", "enumerate"): ForestEntry("pcp_dfs_forest_device_small_enum", excl=True, objective=True),
+    ("neq", "sink"): ForestEntry("pcp_dfs_forest_device_neq_sink", excl=True, sink=True, dirty=True)}  # the sink is the call's
+
+
+def _neq_enum_forest(a, entry=FOREST_ENTRIES["neq", "enumerate"]) -> str:
+    """The refusal of dfs_forest_enum / forest_enumerate (forest_solutions: of ``entry``) under InputOrder when the all-XNeqY forest is asked for by name."""
     if a.get("forest") != "neq":
         return ""
-    return "is not served by the all-XNeqY forest (pcp_dfs_forest_device_neq_enum selects FirstSmallestVar only): forest='small' runs an all-XNeqY store within the small-store limits"
+    return f"is not served by the all-XNeqY forest ({entry.name} selects FirstSmallestVar only): forest='small' runs an all-XNeqY store within the small-store limits"
 
 
 def _check_neq_enum(who, objective, collect_solutions, var_select):
@@ -382,10 +404,29 @@ def _check_neq_enum(who, objective, collect_solutions, var_select):
         raise ValueError(f"{who}: var_select='input_order' " + _neq_enum_forest({"forest": "neq"}))
 
 
+def _check_enum_forest(who, ctx, forest, dist, val, objective, collect_solutions, bnb) -> str:
+    """What dfs_forest_enum and forest_enumerate refuse, before anything runs; the forest kind — ``forest``, or the store's (None)."""
+    if forest not in FOREST_KINDS:
+        raise ValueError(f"{who}: forest must be None, 'neq', 'small' or 'form', not {forest!r}")
+    if dist is not None:
+        raise ValueError(f"{who}: Enumerate does not run on several ranks (moving exclusion lists between ranks is not built)")
+    if val not in VAL_MODES:
+        raise ValueError(f"{who}: val must be 'middle' or 'min', not {val!r}")
+    if collect_solutions and objective is not None:
+        raise ValueError(f"{who}: collect_solutions does not go with an objective (branch and bound {bnb})")
+    if forest == "neq":
+        _check_neq_enum(who, objective, collect_solutions, None)
+    if forest is None:
+        forest = store_forest_kind(ctx)
+    if forest == "neq":
+        _check_neq_enum(who, objective, collect_solutions, ctx.var_select)
+    return forest
+
+
 def _xneq_forest(a) -> str:
     """The refusal of dfs_forest / forest_search under InputOrder: neither ``formulas`` nor ``small`` (nor the Enumerate forest chosen by the
     store) is the all-XNeqY in-kernel forest, pcp_dfs_forest_device."""
-    if a.get("formulas") or a.get("small") or a.get("_call") is not None or a.get("_enum_entry") is not None or a.get("_by_store") is not None:
+    if a.get("formulas") or a.get("small"):
         return ""
     return "is not served by the all-XNeqY forest (pcp_dfs_forest_device selects FirstSmallestVar only): small=True runs an all-XNeqY store within the small-store limits"
 
@@ -513,6 +554,8 @@ class Context:
         """The store holds a formula unit or a Boolean / BooleanNeg filter: it runs the tree kernels (last_plan path 3).  The search drivers send
         such a store's Enumerate rounds to pcp_propagate_device_form_excl, every other store's where they went before."""
         return any(self._form_flags)
+
+    forest_kind = property(store_forest_kind)  # "form" | "neq" | "small": the Interval forest dfs_forest_enum / forest_enumerate / forest_solutions choose
 
     def set_option(self, key: str, value: int):
         self._check(self._L.pcp_set_option(self._h, key.encode(), int(value)))
@@ -758,12 +801,126 @@ class Context:
         self._check(self._L.pcp_dfs_forest_steal(self._h, None if st is None else C.byref(st), int(n_trees), None if ex is None else C.byref(ex), n,
                                                  _ptr(pairs), _ptr(done), C.c_void_p(stream)))
 
+    def _run_row_forest(self, entry: ForestEntry, root_lb, root_ub, val, *, root_excl, path_capacity, max_path, stop_on_solution, node_limit_per_tree, steps_per_launch,
+                        capacity, max_launches, node_budget, want_solution, rebalance, info, max_capacity, steal, objective=None, sink_mode=None, dist=None, sp0=None,
+                        hints=True, sink_capacity=0) -> dict:
+        """The host side of every Interval forest, behind dfs_forest, dfs_forest_bnb, dfs_forest_enum and dfs_forest_neq_solutions (which
+        validate and choose): the forest's buffers, launches of ``entry`` — marshalled by what the ForestEntry says it takes — through
+        search_forest.run_forest_loop, and the result dict.  ``val``: None under BinarySplit, else Enumerate's value selector, and the trees
+        carry exclusion paths.  ``objective``: a ForestObjective or None.  ``sink_mode``: None; "context" — a SolutionSink of ``sink_capacity``
+        rows is the context's for the duration of the loop, detached on every way out; "call" — it is an argument of every launch."""
+        import torch
+        from .search_forest import ForestStacks, run_forest_loop
+        enum, V = val is not None, self.n_vars
+        dev = torch.device("cuda", self.device)
+        to_dev = lambda x: (torch.from_numpy(np.ascontiguousarray(x, np.int32)) if isinstance(x, np.ndarray) else x).to(dev).reshape(-1, V)
+        rl, ru = to_dev(root_lb), to_dev(root_ub)
+        T = rl.shape[0]
+        rows = lambda name: ForestStacks.rows(name, T, capacity, V, dev)
+        lb, ub = rows("lb"), rows("ub")
+        lb[:, 0] = rl; ub[:, 0] = ru
+        # (sp0: trees that start with an empty stack — a rank that only takes part in the collectives until a refill reaches it)
+        sp = torch.ones(T, dtype=torch.int32, device=dev) if sp0 is None else torch.tensor(list(sp0), dtype=torch.int32, device=dev)
+        stop = torch.zeros(T, dtype=torch.int32, device=dev)
+        counters = torch.zeros((T, 5), dtype=torch.int64, device=dev)
+        sol = torch.zeros((T, V), dtype=torch.int32, device=dev) if want_solution else None
+        excl, box = {}, {}  # the Enumerate arrays of the stacks; the structs the launches and the stealer read
+        if enum:
+            lists = [np.ascontiguousarray(e, np.int32).reshape(-1, 2) for e in root_excl] if root_excl is not None else []
+            if lists and len(lists) != T:
+                raise ValueError(f"dfs_forest: root_excl names {len(lists)} roots, there are {T}")
+            path_capacity = max(int(path_capacity), max((len(e) for e in lists), default=0))
+            h_path = np.zeros((T, max(path_capacity, 1), 2), np.int32)
+            for t, e in enumerate(lists):
+                h_path[t, :len(e)] = e
+            excl = dict(path=torch.from_numpy(h_path).to(dev), row_base=rows("row_base"), row_excl=rows("row_excl"), path_capacity=path_capacity,
+                        max_path=max(int(max_path), path_capacity))
+            if lists:
+                excl["row_base"][:, 0] = torch.tensor([len(e) for e in lists], dtype=torch.int32, device=dev)
+
+        def point(fs):  # (re)build the pcp_dfs_state — and the pcp_forest_excl — over the forest's current buffers
+            box["st"] = DfsState(fs.lb.data_ptr(), fs.ub.data_ptr(), fs.capacity, sp.data_ptr(), stop.data_ptr(), fs.status.data_ptr(), counters.data_ptr(),
+                                 sol.data_ptr() if want_solution else None, fs.dirty.data_ptr() if fs.dirty is not None else None)
+            box["ex"] = ForestExcl(fs.path.data_ptr(), fs.row_base.data_ptr(), fs.row_excl.data_ptr(), fs.path_capacity, VAL_MODES[val]) if enum else None
+
+        # pcp_dfs_state.dirty: one word per stack row — the all-XNeqY forest's, under either distributor (the small-store and formula-store forests keep none)
+        fs = ForestStacks(lb, ub, rows("status"), sp, stop, counters, max_capacity=max(max_capacity, capacity), on_grow=point,
+                          dirty=rows("dirty") if (entry.dirty and hints) else None, **excl)
+        del lb, ub, excl
+        point(fs)
+        fn = getattr(self._L, entry.name)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        byref = lambda s: None if s is None else C.byref(s)
+
+        def launch():
+            args = [self._h, C.byref(box["st"]), T]
+            if entry.excl:
+                args.append(byref(box["ex"]))
+            if entry.objective:
+                args.append(byref(objective))
+            if entry.sink:
+                args.append(C.byref(box["sink"]))
+            args.append(int(steps_per_launch))
+            if entry.stop:
+                args.append(int(bool(stop_on_solution)))
+            self._check(fn(*args, int(node_limit_per_tree), C.c_void_p(stream)))
+
+        sink = SolutionSink(sink_capacity, V, dev) if sink_mode else None
+        with contextlib.ExitStack() as on_exit:
+            if sink_mode == "context":  # the context's for the duration of the loop only: detached on every way out
+                self.solution_sink_set(sink)
+                on_exit.callback(self.solution_sink_set, None)
+            box["sink"] = sink.struct() if entry.sink else None  # (an argument of every launch: nothing is attached to the context)
+            # (the stealer reads the state where point() last put it, so a grown stack or path is the one it moves rows in)
+            loop = run_forest_loop(launch, fs, stop_on_solution=stop_on_solution, node_budget=node_budget, rebalance=rebalance and not node_limit_per_tree,
+                                   max_launches=max_launches, dist=dist, sink=sink, steal=steal,
+                                   stealer=lambda pairs, done: self.forest_steal(box["st"], T, box["ex"], pairs, done))
+            if sink is not None:
+                sink.drain()  # (behind the last launch)
+        if info is not None:
+            info.update(loop)
+            spc = sp.cpu().tolist()  # the open nodes each tree left on its stack, bottom row first
+            info["rows"] = [(fs.lb[t, :spc[t]].cpu().numpy(), fs.ub[t, :spc[t]].cpu().numpy()) for t in range(T)] if T <= 64 else None
+            if enum:
+                info["path_grown"], info["path_capacity"] = fs.path_grown, fs.path_capacity
+        cn = counters.cpu().numpy()
+        out = {"nodes": int(cn[:, 0].sum()), "solutions": int(cn[:, 1].sum()), "failed": int(cn[:, 2].sum()), "error": int(cn[:, 3].max()),
+               "open": int(sp.sum().item()), "launches": loop["launches"], "per_tree": cn, "trees": T, "steals": loop["steals"],
+               "first_solutions": sol.cpu().numpy() if want_solution else None}
+        if sink is not None:
+            out["solutions_lb"], out["solutions_ub"], out["solution_tree"] = sink.rows()
+        return out
+
+    def _run_forest_bnb(self, entry: ForestEntry, root_lb, root_ub, objective, best0, val=None, **run):
+        """_run_row_forest under branch and bound: the forest's incumbent (one device word, ``best0`` or "no solution yet") and each tree's
+        best value and row, handed to ``entry`` as its pcp_forest_objective; the result gains ``best``, ``best_solution``, ``tree_best``
+        (``stop_on_solution`` / ``want_solution`` do not apply)."""
+        import torch
+        var, mode = objective
+        if mode not in OBJ_MODES:
+            raise ValueError(f"objective mode must be 'min' or 'max', not {mode!r}")
+        none = no_incumbent(mode)
+        dev = torch.device("cuda", self.device)
+        T = int(np.prod(root_lb.shape)) // max(self.n_vars, 1)
+        d_best = torch.full((1,), none if best0 is None else int(best0), dtype=torch.int32, device=dev)
+        tree_best = torch.full((T,), none, dtype=torch.int32, device=dev)
+        tree_row = torch.zeros((T, self.n_vars), dtype=torch.int32, device=dev)
+        obj = ForestObjective(int(var) & 0xFFFFFFFF, OBJ_MODES[mode], d_best.data_ptr(), tree_best.data_ptr(), tree_row.data_ptr())
+        out = self._run_row_forest(entry, root_lb, root_ub, val, objective=obj, **{**run, "stop_on_solution": False, "want_solution": False})
+        tb = tree_best.cpu().numpy()
+        found = tb != none
+        out["tree_best"] = tb
+        out["best"] = int(d_best.item()) if found.any() else None
+        winners = np.nonzero(found & (tb == int(d_best.item())))[0]
+        out["best_solution"] = tree_row[int(winners[0])].cpu().numpy() if len(winners) else None
+        return out
+
     @scoped_var_select(refuse=_xneq_forest)
     def dfs_forest(self, root_lb, root_ub, stop_on_solution: bool = False, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
                    max_launches: int = 1 << 30, node_budget: int = 0, want_solution: bool = False, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
-                   sp0=None, hints: bool = True, formulas: bool = False, small: bool = False, _call=None, brancher: str = "split", val: str = "middle",
-                   root_excl=None, path_capacity: int = 64, max_path: int = 1 << 20, _obj=None, collect_solutions: bool = False, sink_capacity: int = 4096,
-                   _enum_entry=None, _neq_sink: int = 0, steal: str = "host"):
+                   sp0=None, hints: bool = True, formulas: bool = False, small: bool = False, brancher: str = "split", val: str = "middle",
+                   root_excl=None, path_capacity: int = 64, max_path: int = 1 << 20, collect_solutions: bool = False, sink_capacity: int = 4096,
+                   steal: str = "host"):
         """pcp_dfs_forest_device: the reference's search loop (interval mode, all-XNeqY models) on many subtrees at once, one workgroup per
         tree, each exactly a pcp_dfs_device instance.  root_lb / root_ub: [n_trees, n_vars] int32 (numpy or CUDA tensors): the roots, not yet
         propagated.  Launches of steps_per_launch nodes per tree are repeated until every stack is empty, a tree stopped (solution with
@@ -774,133 +931,35 @@ class Context:
         ``max_capacity``, whenever a tree fills its stack (error 1 is only reported beyond that).  Returns dict(nodes, solutions, failed, error, open, launches,
         per_tree=[n_trees, 5], first_solutions) — this rank's counters.
         ``formulas``: the store holds formula propagators (Boolean / formula units — what Cumulative.join builds): the trees run in
-        pcp_dfs_forest_device_form, one per wavefront (last_plan: path 3, block = 64 x trees per workgroup); it keeps no ``dirty`` rows.
-        Stacks, growth, refill, ``dist`` and the result dict are the same.
-        ``small``: a small store of plain propagators of any kind (at most 128 slots and 2048 elementary filters, no formula units — the
-        Golomb network): the trees run in pcp_dfs_forest_device_small, one per wavefront (last_plan: path 4); no ``dirty`` rows either.
-        Together with ``formulas`` it is a ValueError: a store is one or the other.
-        ``brancher="enumerate"`` (``small=True`` only; otherwise, or with ``dist``, a ValueError): the trees run under Enumerate on MiddleVal
-        (``val="middle"``) or MinVal (``"min"``) in pcp_dfs_forest_device_small_enum.  ``root_excl``: a list of [k, 2] int32 arrays of (var, value),
-        one per root — the exclusions the root arrives with (None: no root has any); they are written into each tree's path.  A tree's path
-        holds ``path_capacity`` entries and is doubled, up to ``max_path``, when a tree reports error 5, as its stack is on error 1.  ``info``
-        also receives ``path_grown`` and ``path_capacity``.  The default ``brancher="split"`` issues exactly the calls it issued before.
-        (Enumerate over a store with formula units: dfs_forest_enum, which chooses the forest by what the store is.)
+        pcp_dfs_forest_device_form, one per wavefront (last_plan: path 3, block = 64 x trees per workgroup).  ``small``: a small store of plain
+        propagators of any kind (at most 128 slots and 2048 elementary filters, no formula units — the Golomb network): the trees run in
+        pcp_dfs_forest_device_small, one per wavefront (last_plan: path 4).  Neither keeps ``dirty`` rows; stacks, growth, refill, ``dist`` and
+        the result dict are the same.  Both together are a ValueError: a store is one or the other.
+        ``brancher="enumerate"`` (``small=True`` only; otherwise, or with ``dist``, a ValueError; dfs_forest_enum chooses the forest by what the
+        store is): the trees run under Enumerate on MiddleVal (``val="middle"``) or MinVal (``"min"``) in pcp_dfs_forest_device_small_enum.
+        ``root_excl``: a list of [k, 2] int32 arrays of (var, value), one per root — the exclusions the root arrives with (None: no root has
+        any); they are written into each tree's path, which holds ``path_capacity`` entries and is doubled, up to ``max_path``, when a tree
+        reports error 5, as its stack is on error 1.  ``info`` also receives ``path_grown`` and ``path_capacity``.
         ``collect_solutions`` (``formulas=True`` or ``small=True``, either brancher, one rank; otherwise a ValueError): every solution is
         returned, not only counted — a SolutionSink of ``sink_capacity`` rows is attached for the duration of the call, a tree that finds it
-        full hands its node back (error 6), the loop drains the sink and resumes that tree, as it grows a stack on error 1; the counters
-        are those of the same call without it.  The result then also holds ``solutions_lb`` / ``solutions_ub`` ([n, n_vars] int32: a solution
-        is a box of the interval store — every point of it satisfies the model; ``first_solutions`` keeps lower bounds only) and
-        ``solution_tree`` ([n]: the tree that wrote each row); ``info`` receives ``drains``, the drains a full sink forced.  With the default
-        False the calls issued and the keys returned are those of before.
-        ``steal`` ("host" | "device"; anything else a ValueError): how finished trees take work between launches.  "host", the default, is
-        search_forest.run_forest_loop's own loop over a host copy of ``sp`` and issues exactly the calls it issued before; "device" plans the
-        pairs with torch on the device (search_forest.plan_steal_pairs) and carries them out in one pcp_dfs_forest_steal call per launch,
-        with no copy to the host beyond the launch's summary.  Both leave the same state behind, so every tree's counters, ``launches`` and
-        ``steals`` are the same.  One rank: "device" with a ``dist`` of more than one rank is a ValueError."""
-        import torch
+        full hands its node back (error 6), the loop drains the sink and resumes that tree; the counters are those of the same call without
+        it.  The result then also holds ``solutions_lb`` / ``solutions_ub`` ([n, n_vars] int32: a solution is a box of the interval store —
+        every point of it satisfies the model; ``first_solutions`` keeps lower bounds only) and ``solution_tree`` ([n]: the tree that wrote
+        each row); ``info`` receives ``drains``, the drains a full sink forced.
+        ``steal`` ("host" | "device"; anything else a ValueError): how finished trees take work between launches — run_forest_loop's own loop
+        over a host copy of ``sp``, or pairs planned on the device (search_forest.plan_steal_pairs) and carried out in one pcp_dfs_forest_steal
+        call per launch, with no copy to the host beyond the launch's summary.  Both leave the same state behind, so every tree's counters,
+        ``launches`` and ``steals`` are the same.  One rank: "device" with a ``dist`` of more than one rank is a ValueError."""
         _check_steal("dfs_forest", steal, dist)
         if small and formulas:
             raise ValueError("dfs_forest: small=True and formulas=True name two different forests (a store has formula units or it has none)")
-        # (_enum_entry: dfs_forest_enum's — the Enumerate entry of the forest the store belongs to, in place of the small-store one)
-        # (_neq_sink: dfs_forest_neq_solutions' — the rows of a sink of the CALL, through pcp_dfs_forest_device_neq_sink under either brancher)
-        enum = _check_forest_brancher("dfs_forest", brancher, val, small or _enum_entry is not None or _neq_sink > 0, dist, root_excl)
-        _check_collect("dfs_forest", collect_solutions, sink_capacity, small, formulas, dist, _call is not None or _obj is not None)
-        dev = torch.device("cuda", self.device)
-        V = self.n_vars
-        to_dev = lambda x: (torch.from_numpy(np.ascontiguousarray(x, np.int32)) if isinstance(x, np.ndarray) else x).to(dev).reshape(-1, V)
-        rl, ru = to_dev(root_lb), to_dev(root_ub)
-        T = rl.shape[0]
-        lb = torch.empty((T, capacity, V), dtype=torch.int32, device=dev)
-        ub = torch.empty((T, capacity, V), dtype=torch.int32, device=dev)
-        lb[:, 0] = rl; ub[:, 0] = ru
-        sp = torch.ones(T, dtype=torch.int32, device=dev)
-        if sp0 is not None:  # (trees that start with an empty stack: a rank that only takes part in the collectives until a refill reaches it)
-            sp = torch.tensor(list(sp0), dtype=torch.int32, device=dev)
-        stop = torch.zeros(T, dtype=torch.int32, device=dev)
-        status = torch.zeros((T, capacity), dtype=torch.uint8, device=dev)
-        counters = torch.zeros((T, 5), dtype=torch.int64, device=dev)
-        sol = torch.zeros((T, V), dtype=torch.int32, device=dev) if want_solution else None
-        # pcp_dfs_state.dirty: one word per stack row — the all-XNeqY forest's, under either distributor (the small-store and formula-store forests keep none)
-        dirty = torch.full((T, capacity), -1, dtype=torch.int32, device=dev) if (hints and not formulas and not small) else None
-        from .search_forest import ForestStacks, run_forest_loop
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        box = {}
-
-        path = row_base = row_excl = None
-        if enum:
-            lists = [np.ascontiguousarray(e, np.int32).reshape(-1, 2) for e in root_excl] if root_excl is not None else []
-            if lists and len(lists) != T:
-                raise ValueError(f"dfs_forest: root_excl names {len(lists)} roots, there are {T}")
-            path_capacity = max(int(path_capacity), max((len(e) for e in lists), default=0))
-            h_path = np.zeros((T, max(path_capacity, 1), 2), np.int32)
-            h_base = np.zeros((T, capacity), np.int32)
-            for t, e in enumerate(lists):
-                h_path[t, :len(e)] = e
-                h_base[t, 0] = len(e)
-            path, row_base = torch.from_numpy(h_path).to(dev), torch.from_numpy(h_base).to(dev)
-            row_excl = torch.zeros((T, capacity, 2), dtype=torch.int32, device=dev)
-            row_excl[:, :, 0] = -1  # var 0xFFFFFFFF: the row appends nothing
-
-        def point(fs):  # (re)build the pcp_dfs_state — and the pcp_forest_excl — over the forest's current buffers
-            box["st"] = DfsState(fs.lb.data_ptr(), fs.ub.data_ptr(), fs.capacity, sp.data_ptr(), stop.data_ptr(), fs.status.data_ptr(), counters.data_ptr(),
-                                 sol.data_ptr() if want_solution else None, fs.dirty.data_ptr() if fs.dirty is not None else None)
-            if enum:
-                box["ex"] = ForestExcl(fs.path.data_ptr(), fs.row_base.data_ptr(), fs.row_excl.data_ptr(), fs.path_capacity, VAL_MODES[val])
-
-        fs = ForestStacks(lb, ub, status, sp, stop, counters, max_capacity=max(max_capacity, capacity), on_grow=point, dirty=dirty,
-                          **(dict(path=path, row_base=row_base, row_excl=row_excl, path_capacity=path_capacity, max_path=max(int(max_path), path_capacity)) if enum else {}))
-        del lb, ub, status, dirty, path, row_base, row_excl
-        point(fs)
-
-        entry = self._L.pcp_dfs_forest_device_small if small else (self._L.pcp_dfs_forest_device_form if formulas else self._L.pcp_dfs_forest_device)
-
-        def launch():
-            if _neq_sink:  # (the sink is an argument of the call: nothing is attached to the context)
-                self._check(self._L.pcp_dfs_forest_device_neq_sink(self._h, C.byref(box["st"]), T, C.byref(box["ex"]) if enum else None, C.byref(box["sink"]),
-                                                                   int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit_per_tree), C.c_void_p(stream)))
-            elif enum:  # (_obj: dfs_forest_bnb's objective)
-                self._check((_enum_entry or self._L.pcp_dfs_forest_device_small_enum)(self._h, C.byref(box["st"]), T, C.byref(box["ex"]), C.byref(_obj) if _obj is not None else None,
-                                                                                     int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit_per_tree), C.c_void_p(stream)))
-            elif _call is not None:  # (dfs_forest_bnb: the same loop over another entry point)
-                self._check(_call(box["st"], T, stream))
-            else:
-                self._check(entry(self._h, C.byref(box["st"]), T, int(steps_per_launch), int(bool(stop_on_solution)), int(node_limit_per_tree), C.c_void_p(stream)))
-
-        # (steal="device": the stealer reads the state where point() last put it, so a grown stack or path is the one it moves rows in)
-        skw = dict(steal=steal, stealer=lambda pairs, done: self.forest_steal(box["st"], T, box["ex"] if enum else None, pairs, done)) if steal != "host" else {}
-        if _neq_sink:
-            sink = SolutionSink(_neq_sink, V, dev)
-            box["sink"] = sink.struct()
-            loop = run_forest_loop(launch, fs, stop_on_solution=stop_on_solution, node_budget=node_budget,
-                                   rebalance=rebalance and not node_limit_per_tree, max_launches=max_launches, dist=dist, sink=sink, **skw)
-            sink.drain()
-        elif collect_solutions:
-            # the sink is the context's for the duration of the loop only: drained behind the last launch, detached on every way out
-            sink = SolutionSink(sink_capacity, V, dev)
-            self.solution_sink_set(sink)
-            try:
-                loop = run_forest_loop(launch, fs, stop_on_solution=stop_on_solution, node_budget=node_budget,
-                                       rebalance=rebalance and not node_limit_per_tree, max_launches=max_launches, dist=dist, sink=sink, **skw)
-                sink.drain()
-            finally:
-                self.solution_sink_set(None)
-        else:
-            loop = run_forest_loop(launch, fs, stop_on_solution=stop_on_solution, node_budget=node_budget,
-                                   rebalance=rebalance and not node_limit_per_tree, max_launches=max_launches, dist=dist, **skw)
-        launches, steals = loop["launches"], loop["steals"]
-        if info is not None:
-            info.update(loop)
-            spc = sp.cpu().tolist()  # the open nodes each tree left on its stack, bottom row first
-            info["rows"] = [(fs.lb[t, :spc[t]].cpu().numpy(), fs.ub[t, :spc[t]].cpu().numpy()) for t in range(T)] if T <= 64 else None
-            if enum:
-                info["path_grown"], info["path_capacity"] = fs.path_grown, fs.path_capacity
-        cn = counters.cpu().numpy()
-        out = {"nodes": int(cn[:, 0].sum()), "solutions": int(cn[:, 1].sum()), "failed": int(cn[:, 2].sum()), "error": int(cn[:, 3].max()),
-               "open": int(sp.sum().item()), "launches": launches, "per_tree": cn, "trees": T, "steals": steals,
-               "first_solutions": sol.cpu().numpy() if want_solution else None}
-        if collect_solutions or _neq_sink:
-            out["solutions_lb"], out["solutions_ub"], out["solution_tree"] = sink.rows()
-        return out
+        enum = _check_forest_brancher("dfs_forest", brancher, val, small, dist, root_excl)
+        _check_collect("dfs_forest", collect_solutions, sink_capacity, small, formulas, dist)
+        entry = FOREST_ENTRIES["small" if small else "form" if formulas else "neq", "enumerate" if enum else "plain"]
+        return self._run_row_forest(entry, root_lb, root_ub, val if enum else None, sink_mode="context" if collect_solutions else None, root_excl=root_excl,
+                                    path_capacity=path_capacity, max_path=max_path, stop_on_solution=stop_on_solution, node_limit_per_tree=node_limit_per_tree, steps_per_launch=steps_per_launch,
+                                    capacity=capacity, max_launches=max_launches, node_budget=node_budget, want_solution=want_solution, rebalance=rebalance, info=info, dist=dist,
+                                    max_capacity=max_capacity, sp0=sp0, hints=hints, sink_capacity=sink_capacity, steal=steal)
 
     def dfs_forest_neq_solutions(self, root_lb, root_ub, brancher: str = "split", val: str = "middle", root_excl=None, sink_capacity: int = 4096,
                                  objective=None, var_select=None, dist=None, path_capacity: int = 64, max_path: int = 1 << 20, stop_on_solution: bool = False,
@@ -936,16 +995,16 @@ class Context:
         with var_select_scope(self, var_select):
             if self.var_select == "input_order":
                 raise ValueError(f"{who}: the context's var_select is 'input_order', which the all-XNeqY forest does not serve (var_select='first_smallest' for this call)")
-            return self.dfs_forest(root_lb, root_ub, stop_on_solution=stop_on_solution, node_limit_per_tree=node_limit_per_tree, steps_per_launch=steps_per_launch,
-                                   capacity=capacity, max_launches=max_launches, node_budget=node_budget, want_solution=want_solution, rebalance=rebalance, info=info,
-                                   max_capacity=max_capacity, sp0=sp0, hints=hints, _neq_sink=int(sink_capacity), **(dict(steal=steal) if steal != "host" else {}),
-                                   **(dict(brancher="enumerate", val=val, root_excl=root_excl, path_capacity=path_capacity, max_path=max_path) if brancher == "enumerate" else {}))
+            return self._run_row_forest(FOREST_ENTRIES["neq", "sink"], root_lb, root_ub, val if brancher == "enumerate" else None, sink_mode="call",
+                                        root_excl=root_excl, path_capacity=path_capacity, max_path=max_path, stop_on_solution=stop_on_solution, node_limit_per_tree=node_limit_per_tree,
+                                        steps_per_launch=steps_per_launch, capacity=capacity, max_launches=max_launches, node_budget=node_budget, want_solution=want_solution,
+                                        rebalance=rebalance, info=info, max_capacity=max_capacity, sp0=sp0, hints=hints, sink_capacity=sink_capacity, steal=steal)
 
     @scoped_var_select()
     def dfs_forest_bnb(self, root_lb, root_ub, objective, best0=None, node_limit_per_tree: int = 0, steps_per_launch: int = 256, capacity: int = 2048,
                        max_launches: int = 1 << 30, node_budget: int = 0, rebalance: bool = True, info: dict | None = None, dist=None, max_capacity: int = 0,
                        sp0=None, small: bool = False, brancher: str = "split", val: str = "middle", root_excl=None, path_capacity: int = 64,
-                       max_path: int = 1 << 20, collect_solutions: bool = False, _enum_entry=None, steal: str = "host"):
+                       max_path: int = 1 << 20, collect_solutions: bool = False, steal: str = "host"):
         """pcp_dfs_forest_device_form_bnb: branch and bound (branch_and_bound.rs:64-84) in the forest over an Interval store with formula
         propagators — the loop, stacks, growth and refill of dfs_forest(formulas=True), every popped row entered with the forest's incumbent
         (one device word) folded into the objective's bounds.  ``objective`` = (var, "min" | "max").  ``best0``: a known bound to start from
@@ -954,38 +1013,17 @@ class Context:
         "no solution yet" value).
         ``small``: the store is a small one of plain propagators (dfs_forest(small=True)): the same loop and result over
         pcp_dfs_forest_device_small_bnb.  ``brancher`` / ``val`` / ``root_excl`` / ``path_capacity`` / ``max_path``: as for dfs_forest
-        (Enumerate needs ``small=True``: pcp_dfs_forest_device_small_enum with the objective; dfs_forest_enum(objective=) runs it over either store).  ``collect_solutions=True`` is a ValueError:
+        (Enumerate needs ``small=True``: pcp_dfs_forest_device_small_enum with the objective — the bnb entry is not called then;
+        dfs_forest_enum(objective=) runs it over either store).  ``collect_solutions=True`` is a ValueError:
         branch and bound keeps ``best_solution``, and its entries refuse a solution sink.  ``steal``: as for dfs_forest (the per-tree
         branch-and-bound words stay with their trees under both)."""
-        import torch
         _check_steal("dfs_forest_bnb", steal, dist)
-        _check_forest_brancher("dfs_forest_bnb", brancher, val, small or _enum_entry is not None, dist, root_excl)
+        enum = _check_forest_brancher("dfs_forest_bnb", brancher, val, small, dist, root_excl)
         _check_collect("dfs_forest_bnb", collect_solutions, 1, small, not small, None, bnb=True)
-        var, mode = objective
-        if mode not in OBJ_MODES:
-            raise ValueError(f"objective mode must be 'min' or 'max', not {mode!r}")
-        none = no_incumbent(mode)
-        dev = torch.device("cuda", self.device)
-        T = int(np.prod(root_lb.shape)) // max(self.n_vars, 1)
-        d_best = torch.full((1,), none if best0 is None else int(best0), dtype=torch.int32, device=dev)
-        tree_best = torch.full((T,), none, dtype=torch.int32, device=dev)
-        tree_row = torch.zeros((T, self.n_vars), dtype=torch.int32, device=dev)
-        obj = ForestObjective(int(var) & 0xFFFFFFFF, OBJ_MODES[mode], d_best.data_ptr(), tree_best.data_ptr(), tree_row.data_ptr())
-
-        def call(st, n_trees, stream):
-            entry = self._L.pcp_dfs_forest_device_small_bnb if small else self._L.pcp_dfs_forest_device_form_bnb
-            return entry(self._h, C.byref(st), n_trees, C.byref(obj), int(steps_per_launch), int(node_limit_per_tree), C.c_void_p(stream))
-
-        out = self.dfs_forest(root_lb, root_ub, node_limit_per_tree=node_limit_per_tree, steps_per_launch=steps_per_launch, capacity=capacity, max_launches=max_launches,
-                              node_budget=node_budget, rebalance=rebalance, info=info, dist=dist, max_capacity=max_capacity, sp0=sp0, formulas=not small, small=small, _call=call, **(dict(steal=steal) if steal != "host" else {}),
-                              **(dict(brancher=brancher, val=val, root_excl=root_excl, path_capacity=path_capacity, max_path=max_path, _obj=obj, _enum_entry=_enum_entry) if brancher != "split" else {}))
-        tb = tree_best.cpu().numpy()
-        found = tb != none
-        out["tree_best"] = tb
-        out["best"] = int(d_best.item()) if found.any() else None
-        winners = np.nonzero(found & (tb == int(d_best.item())))[0]
-        out["best_solution"] = tree_row[int(winners[0])].cpu().numpy() if len(winners) else None
-        return out
+        entry = FOREST_ENTRIES["small" if small else "form", "enumerate" if enum else "bnb"]
+        return self._run_forest_bnb(entry, root_lb, root_ub, objective, best0, val if enum else None, root_excl=root_excl, path_capacity=path_capacity, max_path=max_path,
+                                    node_limit_per_tree=node_limit_per_tree, steps_per_launch=steps_per_launch, capacity=capacity, max_launches=max_launches,
+                                    node_budget=node_budget, rebalance=rebalance, info=info, dist=dist, max_capacity=max_capacity, sp0=sp0, steal=steal)
 
     @scoped_var_select(refuse=_neq_enum_forest)
     def dfs_forest_enum(self, root_lb, root_ub, val: str = "middle", objective=None, best0=None, root_excl=None, path_capacity: int = 64, max_path: int = 1 << 20,
@@ -1001,39 +1039,22 @@ class Context:
         ``best_solution``, ``tree_best``), and ``stop_on_solution`` / ``want_solution`` do not apply.  One rank: ``dist`` is a ValueError,
         as are a ``val`` other than "middle" / "min", ``collect_solutions`` with an objective, and a ``root_excl`` whose length is not the
         number of roots.
-        ``forest`` (None / "neq" / "small" / "form"; anything else a ValueError): None chooses by the store — "form" with formula units, "neq"
-        for an all-XNeqY store beyond the small-store limits (``all_neq`` and ``beyond_small_limits``: decided on the host from the store's
-        shape, nothing is launched to find out), else "small"; a name forces that entry.  "neq" is the all-XNeqY in-kernel forest,
-        pcp_dfs_forest_device_neq_enum: one workgroup per tree, any all-XNeqY store the in-kernel search takes (N-queens-1000; forced, small
-        N-queens too), the stack rows with their ``dirty`` words (``hints=False``: without them — the same tree), which grow and are stolen
-        together with ``row_base``, ``row_excl`` and the path prefix.  It has no branch and bound, refuses the context's solution sink
-        (dfs_forest_neq_solutions returns its solutions through a sink of the call) and selects FirstSmallestVar only: ``objective``, ``collect_solutions`` and ``var_select="input_order"`` are a ValueError before anything runs.
-        ``steal``: as for dfs_forest; a stolen row takes its ``row_base`` / ``row_excl`` words and its path prefix along under both."""
+        ``forest`` (None / "neq" / "small" / "form"; anything else a ValueError): None chooses by the store (``forest_kind``); a name forces
+        that entry.  "neq" is the all-XNeqY in-kernel forest, pcp_dfs_forest_device_neq_enum: one workgroup per tree, any all-XNeqY store the
+        in-kernel search takes (N-queens-1000; forced, small N-queens too), the stack rows with their ``dirty`` words (``hints=False``: without
+        them — the same tree).  It has no branch and bound, refuses the context's solution sink (dfs_forest_neq_solutions returns its solutions)
+        and selects FirstSmallestVar only: ``objective``, ``collect_solutions`` and ``var_select="input_order"`` are a ValueError before anything runs.
+        ``steal``: as for dfs_forest; a stolen row takes its ``dirty``, ``row_base`` / ``row_excl`` words and its path prefix along under both."""
         _check_steal("dfs_forest_enum", steal, dist)
-        if forest not in FOREST_KINDS:
-            raise ValueError(f"dfs_forest_enum: forest must be None, 'neq', 'small' or 'form', not {forest!r}")
-        if dist is not None:
-            raise ValueError("dfs_forest_enum: Enumerate does not run on several ranks (moving exclusion lists between ranks is not built)")
-        if val not in VAL_MODES:
-            raise ValueError(f"dfs_forest_enum: val must be 'middle' or 'min', not {val!r}")
-        if collect_solutions and objective is not None:
-            raise ValueError("dfs_forest_enum: collect_solutions does not go with an objective (branch and bound keeps best_solution; its entries refuse a solution sink)")
-        if forest == "neq":
-            _check_neq_enum("dfs_forest_enum", objective, collect_solutions, None)
-        if forest is None:
-            forest = "form" if self.has_formulas else "neq" if (self.all_neq and self.beyond_small_limits) else "small"
-        if forest == "neq":
-            _check_neq_enum("dfs_forest_enum", objective, collect_solutions, self.var_select)
-        form = forest == "form"
-        entry = {"form": self._L.pcp_dfs_forest_device_form_enum, "small": self._L.pcp_dfs_forest_device_small_enum, "neq": self._L.pcp_dfs_forest_device_neq_enum}[forest]
-        kw = dict(node_limit_per_tree=node_limit_per_tree, steps_per_launch=steps_per_launch, capacity=capacity, max_launches=max_launches, node_budget=node_budget,
-                  rebalance=rebalance, info=info, max_capacity=max_capacity, small=forest == "small", brancher="enumerate", val=val, root_excl=root_excl,
-                  path_capacity=path_capacity, max_path=max_path, _enum_entry=entry, **(dict(hints=hints) if forest == "neq" else {}),
-                  **(dict(steal=steal) if steal != "host" else {}))
+        forest = _check_enum_forest("dfs_forest_enum", self, forest, dist, val, objective, collect_solutions, "keeps best_solution; its entries refuse a solution sink")
+        entry = FOREST_ENTRIES[forest, "enumerate"]
+        run = dict(root_excl=root_excl, path_capacity=path_capacity, max_path=max_path, node_limit_per_tree=node_limit_per_tree, steps_per_launch=steps_per_launch,
+                   capacity=capacity, max_launches=max_launches, node_budget=node_budget, rebalance=rebalance, info=info, max_capacity=max_capacity, hints=hints, steal=steal)
         if objective is not None:
-            return self.dfs_forest_bnb(root_lb, root_ub, objective, best0=best0, **kw)
-        return self.dfs_forest(root_lb, root_ub, stop_on_solution=stop_on_solution, want_solution=want_solution, formulas=form,
-                               collect_solutions=collect_solutions, sink_capacity=sink_capacity, **kw)
+            return self._run_forest_bnb(entry, root_lb, root_ub, objective, best0, val, **run)
+        _check_collect("dfs_forest", collect_solutions, sink_capacity, forest == "small", forest == "form", None)
+        return self._run_row_forest(entry, root_lb, root_ub, val, sink_mode="context" if collect_solutions else None, stop_on_solution=stop_on_solution,
+                                    want_solution=want_solution, sink_capacity=sink_capacity, **run)
 
     @scoped_var_select()
     def dfs_forest_set(self, root_bits, stop_on_solution: bool = False, node_limit: int = 0, steps_per_launch: int = 256,
@@ -1183,7 +1204,7 @@ class Context:
     @scoped_var_select()
     def dfs_forest_set_bnb(self, root_bits, objective, live=None, best0=None, brancher: str = "split", val: str = "middle", steps_per_launch: int = 256,
                            node_limit: int = 0, level_capacity: int = 0, trail_capacity: int = 0, rebalance: bool = True, info: dict | None = None,
-                           ramp_steps: int = 0, max_launches: int = 1 << 30, collect_solutions: bool = False, _entry: str = "pcp_dfs_forest_device_set_bnb"):
+                           ramp_steps: int = 0, max_launches: int = 1 << 30, collect_solutions: bool = False, formulas: bool = False):
         """pcp_dfs_forest_device_set_bnb: branch and bound (branch_and_bound.rs:64-84) in the set-mode forest — the loop of dfs_forest_set under
         either ``brancher``, every node entered with the forest's incumbent (one device word) folded into the set of the objective variable.
         ``objective`` = (var, "min" | "max").  ``live``: which trees start with a root ([n_trees] bool; None: all); the others start finished
@@ -1191,10 +1212,11 @@ class Context:
         ``ramp_steps``: see _run_forest_set.  Returns the counters of dfs_forest_set (first_solution: None) plus ``best`` (None: no solution and
         no ``best0``), ``best_solution`` (the row of the lowest tree whose value is ``best``; None when no tree found one) and ``tree_best`` ([n_trees], a tree
         without a solution: the "no solution yet" value).  ``collect_solutions=True`` is a ValueError: branch and bound keeps
-        ``best_solution``, and its entries refuse a set solution sink."""
+        ``best_solution``, and its entries refuse a set solution sink.  ``formulas``: pcp_dfs_forest_device_setform_bnb (dfs_forest_setform_bnb)."""
+        who, entry = ("dfs_forest_setform_bnb", "pcp_dfs_forest_device_setform_bnb") if formulas else ("dfs_forest_set_bnb", "pcp_dfs_forest_device_set_bnb")
         import torch
         _check_brancher(brancher, val)
-        _check_collect_set("dfs_forest_setform_bnb" if _entry.endswith("setform_bnb") else "dfs_forest_set_bnb", collect_solutions, 1, bnb=True)
+        _check_collect_set(who, collect_solutions, 1, bnb=True)
         var, mode = objective
         if mode not in OBJ_MODES:
             raise ValueError(f"objective mode must be 'min' or 'max', not {mode!r}")
@@ -1209,7 +1231,7 @@ class Context:
         obj = ForestObjective(int(var), OBJ_MODES[mode], d_best.data_ptr(), tree_best.data_ptr(), tree_row.data_ptr())
 
         def launch(st, steps, stream):
-            return getattr(self._L, _entry)(self._h, C.byref(st), C.byref(obj), 1 if brancher == "enumerate" else 0, VAL_MODES.get(val, VAL_MIDDLE), steps,
+            return getattr(self._L, entry)(self._h, C.byref(st), C.byref(obj), 1 if brancher == "enumerate" else 0, VAL_MODES.get(val, VAL_MIDDLE), steps,
                                             int(node_limit), C.c_void_p(stream))
 
         out = self._run_forest_set(root_bits, launch, node_limit=node_limit, steps_per_launch=steps_per_launch, level_capacity=level_capacity,
@@ -1226,7 +1248,7 @@ class Context:
     def dfs_forest_setform_bnb(self, root_bits, objective, **kw):
         """pcp_dfs_forest_device_setform_bnb: dfs_forest_set_bnb for a store WITH formula propagators (see dfs_forest_setform) — the same
         arguments and result dict."""
-        return self.dfs_forest_set_bnb(root_bits, objective, _entry="pcp_dfs_forest_device_setform_bnb", **kw)
+        return self.dfs_forest_set_bnb(root_bits, objective, formulas=True, **kw)
 
     def stats_reset(self, stream_ptr: int = 0):
         self._check(self._L.pcp_stats_reset(self._h, C.c_void_p(stream_ptr)))

@@ -169,3 +169,54 @@ def test_device_loop_on_cpu_tensors_with_a_reference_stealer():
                 assert np.array_equal(x, y), case
             for x, y in zip(a["before"], a["after"]):
                 assert np.array_equal(x, y), case
+
+
+# ------------------------------------------------------------------------------------------------ the shape of the Interval forest drivers
+def _sources():
+    import os
+    import pcp_amd
+    root = os.path.dirname(os.path.abspath(pcp_amd.__file__))
+    return {n: open(os.path.join(root, n)).read() for n in sorted(os.listdir(root)) if n.endswith(".py")}
+
+
+def test_no_public_forest_driver_has_a_private_keyword():
+    import inspect
+    import pcp_amd.engine as E
+    import pcp_amd.search_forest as SF
+    public = [(f"Context.{n}", f) for n, f in vars(E.Context).items() if callable(f) and not n.startswith("_")]
+    public += [(n, f) for n, f in vars(SF).items() if inspect.isfunction(f) and f.__module__ == SF.__name__ and not n.startswith("_")]
+    assert len(public) > 40
+    for name, fn in public:
+        private = [p for p in inspect.signature(fn).parameters if p.startswith("_")]
+        assert not private, (name, private)
+
+
+def test_the_back_doors_are_gone_and_the_loop_is_called_from_one_place():
+    import re
+    src = _sources()
+    # (as identifiers of their own: the entry point pcp_dfs_forest_device_neq_sink keeps its name)
+    for word in ("_by_store", "_enum_entry", "_neq_sink", "_call=", "_obj="):
+        assert not [n for n, s in src.items() if re.search(r"(?<![A-Za-z0-9])" + re.escape(word), s)], word
+    assert src["engine.py"].count("run_forest_loop(") == 1
+
+
+def test_grow_releases_each_old_array_before_it_allocates_the_next(monkeypatch):
+    """The peak of ForestStacks.grow is one old array next to the new ones, not all the old ones: when the new ``ub`` is allocated the old
+    ``lb`` is gone, and so on down the row arrays."""
+    import weakref
+    T, cap, V = 3, 2, 4
+    z = lambda *shape, dtype=torch.int32: torch.zeros(shape, dtype=dtype)
+    fs = ForestStacks(z(T, cap, V), z(T, cap, V), z(T, cap, dtype=torch.uint8), torch.ones(T, dtype=torch.int32), z(T), z(T, 5, dtype=torch.int64), max_capacity=8,
+                      dirty=z(T, cap), path=z(T, 1, 2), row_base=z(T, cap), row_excl=z(T, cap, 2), path_capacity=1)
+    names = [n for n in ForestStacks.ROWS]
+    old = {n: weakref.ref(getattr(fs, n)) for n in names}
+    alive_at, rows = {}, ForestStacks.rows
+
+    def watched(name, *a, **k):
+        alive_at[name] = [n for n in names if old[n]() is not None]
+        return rows(name, *a, **k)
+    monkeypatch.setattr(ForestStacks, "rows", staticmethod(watched))
+    assert fs.grow() and fs.capacity == 2 * cap
+    for i, n in enumerate(names):
+        assert alive_at[n] == names[i:], (n, alive_at[n])
+    assert all(r() is None for r in old.values())
